@@ -89,7 +89,7 @@ LINEAR_ISSUE = {"fp16": 1.0, "bf16": 1.0, "exact": 3.0, "mixed": 2.0, "mixed_x3"
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps of the headline leg (>= 1)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--mode", default="full", choices=["full", "backbone", "dinov2"])
     ap.add_argument("--batch", type=int, default=None, help="frames per GPU per step (full: 64, backbone: 32 = BASELINE configs[2] / [1])")
@@ -125,7 +125,13 @@ def parse():
     ap.add_argument("--no-overlap", action="store_true",
                     help="run every step on one stream (default: the backbone of step i+1 runs on a second HIP stream while "
                          "clustering / pooling / the MLP step of step i -- small kernels that do not fill the GPU -- finish)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline leg's last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32; at most 64 MB in all: a fixed, seeded sample of each array when larger; the result line's 'dumped_outputs' "
+                         "records every array's shape and whether it was sampled)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.batch is None:
         args.batch = {"full": 64, "backbone": 32, "dinov2": 16}[args.mode]
     if args.precision is None:
@@ -201,8 +207,9 @@ def make_pipeline(args, dev, precision=None, stego_reading=None):
     return fe, model, MlpTrainer(model)
 
 
-def hot_path_step(fe, trainer, img, labels_u, args, backbone_out=None):
-    """One pass: frames -> features/segments -> pooled rows -> one MLP optimisation step."""
+def hot_path_step(fe, trainer, img, labels_u, args, backbone_out=None, sink=None):
+    """One pass: frames -> features/segments -> pooled rows -> one MLP optimisation step.  ``sink`` (a dict, or None): receives
+    the device tensors the step hands its caller (no copy, no synchronisation)."""
     import torch
 
     from wild_visual_navigation_amd import ops
@@ -217,7 +224,11 @@ def hot_path_step(fe, trainer, img, labels_u, args, backbone_out=None):
         u = labels_u.reshape(B * S, 2)
     y_valid = u[:, 0] < 0.16  # 16 % labelled segments, like assets/graph/graph.pt (16 / 100)
     y = y_valid.float() * (0.5 + 0.5 * u[:, 1])
-    return trainer.train_step(x, y, y_valid, rows_dev=rows_dev), (rows_dev if rows_dev is not None else x.shape[0])
+    losses = trainer.train_step(x, y, y_valid, rows_dev=rows_dev)
+    if sink is not None:
+        sink.update(features=feat, segments=seg, n_segments=nseg, losses=losses,
+                    mlp_rows=rows_dev if rows_dev is not None else torch.tensor([x.shape[0]]))
+    return losses, (rows_dev if rows_dev is not None else x.shape[0])
 
 
 CU_SPLIT_DEFAULT = "none"   # "<a_hi>,<b_lo>[,rr|lin]" or "none": see TwoStreamPipeline
@@ -269,7 +280,7 @@ class TwoStreamPipeline:
             ready.record(self.a)
         return tok, ready
 
-    def step(self, img, labels_u, next_img=None):
+    def step(self, img, labels_u, next_img=None, sink=None):
         """Runs one step on ``img``; ``next_img`` (the following step's frames, None for the last step) gets its backbone
         stage enqueued FIRST (the tail itself no longer synchronises with the host: rows are compacted on the device)."""
         torch = self.torch
@@ -277,7 +288,7 @@ class TwoStreamPipeline:
         self.pending = self._enqueue_backbone(next_img) if next_img is not None else None
         with torch.cuda.stream(self.b):
             self.b.wait_event(ready)
-            out = hot_path_step(self.fe, self.trainer, img, labels_u, self.args, backbone_out=tok)
+            out = hot_path_step(self.fe, self.trainer, img, labels_u, self.args, backbone_out=tok, sink=sink)
             self.tail_done = torch.cuda.Event(enable_timing=True)
             self.tail_done.record(self.b)
             self.marks.append(self.tail_done)
@@ -474,9 +485,10 @@ DTYPE = {"fp16": "f16", "bf16": "bf16", "exact": "bf16x3 (hi+lo split operands, 
          "fp8": "fp8-e4m3 linears (per-token / per-channel scales), bf16 attention, fp32 residual"}
 
 
-def timed_leg(args, dev, world, rank, steps, warmup, precision, stego_reading, pool, labels, B):
+def timed_leg(args, dev, world, rank, steps, warmup, precision, stego_reading, pool, labels, B, capture=False):
     """`warmup` untimed steps, then exactly `steps` steps between barrier + synchronize pairs.  Returns the leg's figures (the
-    headline leg's go to the top level of the JSON line, the extra legs' into their own objects)."""
+    headline leg's go to the top level of the JSON line, the extra legs' into their own objects).  ``capture``: also return, as
+    host numpy arrays under "outputs", what the LAST timed step handed its caller (plus the MLP parameters after it)."""
     import torch
 
     from wild_visual_navigation_amd import distributed as D, ops
@@ -487,16 +499,18 @@ def timed_leg(args, dev, world, rank, steps, warmup, precision, stego_reading, p
     pipe = None if (args.no_overlap or backbone_only) else TwoStreamPipeline(fe, trainer, args, dev)
     marks = []
 
-    def run_step(i, last):
+    def run_step(i, last, sink=None):
         img, lab = pool[i % len(pool)], labels[i % len(pool)]
         if args.mode == "dinov2":
             out = (fe.backbone_stage(img), 0)          # ViT-B/14 + STEGO head -> 90-d code tokens
         elif backbone_only:
             out = (bb.forward_tokens(img), 0)
         elif pipe is None:
-            out = hot_path_step(fe, trainer, img, lab, args)
+            out = hot_path_step(fe, trainer, img, lab, args, sink=sink)
         else:
-            return pipe.step(img, lab, next_img=None if last else pool[(i + 1) % len(pool)])
+            return pipe.step(img, lab, next_img=None if last else pool[(i + 1) % len(pool)], sink=sink)
+        if sink is not None and backbone_only:
+            sink["tokens"] = out[0]
         e = torch.cuda.Event(enable_timing=True)
         e.record()
         marks.append(e)
@@ -517,8 +531,9 @@ def timed_leg(args, dev, world, rank, steps, warmup, precision, stego_reading, p
     start.record()
     t0 = time.perf_counter()
     rows, losses = 0, None
-    for i in range(steps):
-        losses, rows = run_step(i, i == steps - 1)   # exactly `steps` backbone stages and `steps` tails in the timed region
+    sink = {} if capture else None
+    for i in range(steps):   # exactly `steps` backbone stages and `steps` tails in the timed region
+        losses, rows = run_step(i, i == steps - 1, sink if i == steps - 1 else None)
     if pipe is not None:
         pipe.drain()
     torch.cuda.synchronize()
@@ -526,6 +541,11 @@ def timed_leg(args, dev, world, rank, steps, warmup, precision, stego_reading, p
     dt = time.perf_counter() - t0
     ops.prof_enable(False)
     prof = ops.prof_collect()
+    outputs = None
+    if capture:   # copied before anything else runs on this pipeline (the oracle parity legs reuse its buffers)
+        if not backbone_only:
+            sink["mlp_params"] = model.flat_params()
+        outputs = {k: v.detach().cpu().numpy() for k, v in sink.items()}
     dt = D.max_over_ranks(dt, dev)
     ends = pipe.marks if pipe is not None else marks
     step_ms, prev = [], start
@@ -597,7 +617,36 @@ def timed_leg(args, dev, world, rank, steps, warmup, precision, stego_reading, p
             "ms_per_step": round(dt / steps * 1e3, 3), "step_ms": percentiles(step_ms),
             "backbone_tflops": round(total_flops * passes * total_frames / dt / 1e12 / world, 1), "final_loss": loss_val,
             "roofline": roof, "kernel_ms": {k: {"ms_total": round(v[0], 3), "launches": v[1]} for k, v in prof.items()},
-            "allreduce_ms": comm_ms, "replicas_identical": replicas_ok, "steps": steps, "warmup": warmup}
+            "allreduce_ms": comm_ms, "replicas_identical": replicas_ok, "steps": steps, "warmup": warmup, "outputs": outputs}
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs, budget=DUMP_BUDGET_BYTES):
+    """Write ``outputs`` ({name: numpy array}) as path/<name>.npy in float32 (float64 arrays stay float64), ``budget`` bytes at
+    most in all.  Arrays of up to 256 KB are written whole; when the rest do not fit, each of them is replaced by a sample, its
+    share of the budget, at flat indices drawn with a fixed seed from the array's size (so two runs with the same arguments
+    sample the same elements).  Returns {name: shape, dtype, sampled} for the result line."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in outputs.items()}
+    small = 256 << 10
+    room = budget - (64 << 10) - sum(a.nbytes for a in arrs.values() if a.nbytes <= small)   # 64 KB: the .npy headers
+    large = sum(a.nbytes for a in arrs.values() if a.nbytes > small)
+    manifest = {}
+    for name, a in sorted(arrs.items()):
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": False}
+        if a.nbytes > small and large > room:
+            cap = (room * a.nbytes // large) // a.itemsize
+            if a.size > cap:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+                a = a.reshape(-1)[idx]
+                entry.update(sampled=True, sample_size=int(cap), sample_seed=0)
+        np.save(os.path.join(path, name + ".npy"), a)
+        manifest[name] = entry
+    return manifest
 
 
 def main():
@@ -634,7 +683,11 @@ def main():
     labels = [torch.rand(B, n_lab, 2, generator=gen).to(dev) for _ in range(len(pool))]
     backbone_only = args.mode in ("backbone", "dinov2")
 
-    head = timed_leg(args, dev, world, rank, args.steps, args.warmup, args.precision, args.stego_reading, pool, labels, B)
+    head = timed_leg(args, dev, world, rank, args.steps, args.warmup, args.precision, args.stego_reading, pool, labels, B,
+                     capture=args.dump_outputs is not None)
+    dumped = None
+    if rank == 0 and args.dump_outputs is not None:
+        dumped = dump_outputs(args.dump_outputs, head.pop("outputs"))
     # the two extra legs: the plain default run only (N = 1, configs[2], no A/B switch), the batches unchanged
     plain = (world == 1 and args.mode == "full" and args.segmentation == "stego" and args.stego_reading == "upstream"
              and not args.no_extra_legs and args.attn_variant is None
@@ -720,6 +773,8 @@ def main():
             "kernel_ms": head["kernel_ms"],
             "precision_mode": args.precision,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if head["allreduce_ms"] is not None:
             out["allreduce_ms"] = head["allreduce_ms"]
             if args.force_collectives and world == 1:
