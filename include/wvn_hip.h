@@ -629,6 +629,21 @@ int wvn_debug_attention_timing(long long* dbg);
  * per-tile max; the row sums raise the alarm and the tile is redone exactly -- the default), < 0 = back to the default.  Same
  * results within the kernel's tolerance; tests/test_gpu_attention_lazy.py runs both, bench.py --attn-variant A/Bs them. */
 int wvn_debug_attention_variant(int variant);
+/* The fp16-operand attention kernel exactly as WVN_PREC_MIX's wvn_vit_forward launches it, with the form of the two-plane q as an argument
+ * (no process setting is read or changed for it; form 0 runs the single-plane form wvn_debug_attention_variant selects).  q pre-scaled by softmax_scale * log2(e) (the kernel runs with scale = 0), q / q_lo / k
+ * fp16 [B * heads][npad][64], vt fp16 [B * heads][64][npad] in the token order of wvn_attention_bf16; rows [ntok, npad) finite.
+ * qsplit_form: 0 = one q plane (q_lo must be NULL), 1 = q + q_lo on fp16 MFMAs, 2 = q_lo as e5m2(q_lo * 2^12) on one scaled 8-bit MFMA
+ * per 32 keys (what ships).  Output row of query t of frame b: m = b * ntok_s + t (ntok <= ntok_s <= npad):
+ *   out_frag 0, out_lo NULL: out fp16 [B * ntok_s][heads * 64] row-major;
+ *   out_frag 0, out_lo set:  out / out_lo bf16 hi / lo planes (o = hi + lo), [B * ntok_s][heads * 64] row-major each;
+ *   out_frag 1 (heads = 6):  out / out_lo bf16 hi / lo planes, fragment-major [ceil(B * ntok_s / 32)][24 k-steps][64 lanes][8]
+ *                            (ops.unpack_row_fragments);
+ *   out_frag 2 (heads = 6):  the MX operand planes of wvn_debug_gemm_n384_mx: out = h fp16 [ceil(B * ntok_s / 32)][24][64][8], out_lo = l8
+ *                            [ceil(B * ntok_s / 32)][6][2][64][16] bytes (backbone.mx_fragments / mx_unfragments); rows t in [ntok, ntok_s)
+ *                            of every frame are written as zeros in both planes.
+ * Forms 0 / 1 write only rows t < ntok; no form writes rows past B * ntok_s.  WVN_ERR_ARG for any other combination. */
+int wvn_debug_attention_planes(const void* q, const void* q_lo, const void* k, const void* vt, void* out, void* out_lo, int B, int heads,
+                               int ntok, int ntok_s, int npad, int out_frag, int qsplit_form, void* stream);
 /* which assignment kernel subsequent wvn_kmeans_cosine_pixels calls use: -1 / 5 = the PACKED VALU form where it is eligible (K <= 20;
  * default): the fmaf chains of two clusters ride in the two halves of v_pk_fma_f32, the interpolation runs on channel pairs; 4 = packed
  * dot products, plain interpolation; 0 = the plain VALU form (one v_fma_f32 per cluster and channel); 1 = the SCREENED form where it is

@@ -136,14 +136,21 @@ def test_attention_f32(dev, ntok):
     assert (out.cpu().double() - ref).abs().max().item() < 2e-5
 
 
+@pytest.fixture
+def attention_variant():
+    """wvn_debug_attention_variant for the test; the default form again afterwards, whether the test passed or not."""
+    yield lib().wvn_debug_attention_variant
+    lib().wvn_debug_attention_variant(-1)
+
+
 @pytest.mark.parametrize("prescaled", [False, "exact-max", "lazy"])
 @pytest.mark.parametrize("ntok", [65, 197, 785, 130, 3137])
-def test_attention_bf16(dev, ntok, prescaled):
+def test_attention_bf16(dev, ntok, prescaled, attention_variant):
     """prescaled: q carries softmax_scale * log2(e) (what wvn_vit_forward's QKV epilogue writes) and the kernel is called
     with scale = 0 -- the variant with the running max as the S^T MFMA's C operand, in its two forms: a row max per tile
     ("exact-max") and the shipped default without it ("lazy": the row sums raise the alarm, tests/test_gpu_attention_lazy.py).
     The reference is computed from the q the kernel actually sees."""
-    lib().wvn_debug_attention_variant({"exact-max": 0, "lazy": 1}.get(prescaled, -1))
+    attention_variant({"exact-max": 0, "lazy": 1}.get(prescaled, -1))
     B, h, scale = (1, 2, 0.125) if ntok > 1000 else (2, 3, 0.125)
     q, k, v = (bf(torch.randn(B, h, ntok, 64, generator=g(s))) for s in (1, 2, 3))
     if ntok == 197:
@@ -174,7 +181,6 @@ def test_attention_bf16(dev, ntok, prescaled):
     v1[:, :, ntok:] = 0
     v1t = v1.transpose(-1, -2)[..., perm].contiguous().to(dev)
     check(lib().wvn_attention_bf16(ptr(qd), ptr(kd), ptr(v1t), ptr(out), B, h, ntok, npad, kscale, stream()))
-    lib().wvn_debug_attention_variant(-1)
     assert (out.float().cpu() - 1.0).abs().max().item() < 1e-2
 
 

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from wild_visual_navigation_amd import _lib
-from wild_visual_navigation_amd.backbone import mx_fragments, mx_matmul_reference, pack_n384_mx
+from wild_visual_navigation_amd.backbone import MX_RES_SCALE, mx_fragments, mx_matmul_reference, mx_unfragments, pack_n384_mx
 
 pytestmark = pytest.mark.gpu
 
@@ -48,19 +48,10 @@ def _ln_stats(x, eps=1e-6):
 
 
 def _unfrag(h, l8, h8, M, K):
-    """The inverse of backbone.mx_fragments: (h + l8 / 4096, h8) as [M][K] float64."""
-    from wild_visual_navigation_amd.backbone import MX_RES_SCALE, _swap23
-    R = h.shape[0]
-    sw = _swap23(16)
-    inv = torch.empty(16, dtype=torch.long)
-    inv[sw] = torch.arange(16)
-    hf = h.cpu().reshape(R, K // 16, 2, 32, 8).permute(0, 3, 1, 2, 4).reshape(R, 32, K // 16, 16)[..., inv].reshape(R * 32, K)
-    outs = []
-    for b8 in (l8, h8):
-        q = b8.cpu().view(torch.float8_e5m2).double().reshape(R, K // 64, 2, 2, 32, 2, 8)        # [R][c][x][hw][row][sp][j]
-        q = q.permute(0, 4, 1, 2, 5, 3, 6).reshape(R, 32, K // 16, 16)[..., inv].reshape(R * 32, K)
-        outs.append(q)
-    return (hf.double() + outs[0] / MX_RES_SCALE)[:M], outs[1][:M]
+    """(h + l8 / 4096, h8) as [M][K] float64 (backbone.mx_unfragments decodes the planes)."""
+    hv, l8v = mx_unfragments(h, l8, M, K)
+    f = lambda b: b.view(torch.float8_e5m2).double()   # noqa: E731
+    return hv.double() + f(l8v) / MX_RES_SCALE, f(mx_unfragments(h, h8, M, K)[1])
 
 
 @pytest.fixture(params=[2, 1], ids=["two-workgroups-per-cu", "one-wave-per-simd"])

@@ -90,3 +90,27 @@ def test_pack_a768_fp8_byte_for_byte():
     for _ in range(300):
         t, s, x, hi, row, j = (int(torch.randint(0, m, (1,), generator=gen)) for m in (N // 32, 12, 2, 2, 32, 16))
         assert int(p[t, s, x, hi, row, j]) == int(wq[32 * t + row, 64 * s + 32 * hi + 16 * x + j])
+
+
+def test_mx_unfragments_inverts_mx_fragments():
+    """backbone.mx_unfragments (the decoder of the MX operand planes the attention kernel and fc1 write) against mx_fragments: the round trip
+    gives fp16(a) and mx_split's residue byte in natural order, the rows past M of the last 32-row group are zero, and fragmenting the decoded
+    planes again reproduces every byte."""
+    from wild_visual_navigation_amd.backbone import MX_RES_SCALE, mx_fragments, mx_split, mx_unfragments
+    for M, K in ((70, 384), (32, 128), (5, 1536)):
+        a = torch.randn(M, K, generator=torch.Generator().manual_seed(M + K)) * 3
+        a[::3, ::7] *= 200.0                                        # residues of their own exponents
+        h, l8, h8 = mx_fragments(a)
+        hv, l8v = mx_unfragments(h, l8, M, K)
+        sh, sl8, sh8 = mx_split(a)
+        assert hv.dtype == torch.float16 and l8v.dtype == torch.uint8 and hv.shape == (M, K) == l8v.shape
+        assert torch.equal(hv, a.to(torch.float16)) and torch.equal(hv, sh)
+        assert torch.equal(l8v, sl8)
+        assert torch.equal(mx_unfragments(h, h8, M, K)[1], sh8)    # (an h8 plane decodes through the l8 argument)
+        R = (M + 31) // 32
+        hp, l8p = mx_unfragments(h, l8, 32 * R, K)
+        assert not hp[M:].any() and not l8p[M:].any()
+        # the decoded planes, fragmented again: the same bytes (l8 through mx_fragments' h8 plane, which has l8's layout: e5m2 of a value)
+        f8 = l8v.view(torch.float8_e5m2).float()
+        assert torch.equal(mx_fragments(hv.float())[0].view(torch.int16), h.view(torch.int16))
+        assert torch.equal(mx_fragments(f8)[2], l8)

@@ -114,6 +114,25 @@ def test_argument_validation_without_gpu():
         _lib.check(1002, "x")
 
 
+def test_attention_planes_refuses_what_the_kernel_does_not_support():
+    """wvn_debug_attention_planes returns WVN_ERR_ARG (1001) before any launch for combinations the forward pass never makes."""
+    h = _lib.lib()
+    p = 1 << 20   # (never dereferenced: every call below is refused first)
+
+    def call(q=p, q_lo=p, out_lo=p, heads=6, ntok=785, ntok_s=800, npad=896, out_frag=2, form=2):
+        return h.wvn_debug_attention_planes(q, q_lo, p, p, p, out_lo, 2, heads, ntok, ntok_s, npad, out_frag, form, None)
+
+    assert call(q=None) == 1001
+    assert call(form=0) == 1001                       # one plane: q_lo must be NULL
+    assert call(q_lo=None, form=1) == 1001 and call(q_lo=None, form=2) == 1001
+    assert call(form=3) == 1001 and call(form=-1) == 1001
+    assert call(out_frag=3) == 1001 and call(out_frag=-1) == 1001
+    assert call(out_lo=None, out_frag=2) == 1001 and call(out_lo=None, out_frag=1) == 1001
+    assert call(heads=12, out_frag=2) == 1001 and call(heads=12, out_frag=1) == 1001
+    assert call(ntok_s=784) == 1001 and call(ntok_s=900) == 1001
+    assert call(npad=800) == 1001                     # npad % 128 (the launcher's own check)
+
+
 def test_no_cpu_fallback():
     import torch
 

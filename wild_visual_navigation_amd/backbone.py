@@ -174,6 +174,18 @@ def mx_fragments(a: torch.Tensor):
     return tuple(outs)
 
 
+def mx_unfragments(h: torch.Tensor, l8: torch.Tensor, M: int, K: int):
+    """The inverse of mx_fragments for one (h, l8) pair: h fp16 [R][K / 16][64][8] and l8 uint8 [R][K / 64][2][64][16] (any shapes of those
+    sizes, on any device) -> (h fp16 [M][K], l8 uint8 [M][K]) in natural row / column order, on the CPU.  The value is h + e5m2(l8) / 2^12;
+    an h8 plane decodes through the l8 argument."""
+    R = (M + 31) // 32
+    inv = torch.argsort(_swap23(16))                   # (an involution: inv == _swap23(16))
+    hf = h.detach().cpu().reshape(R, K // 16, 2, 32, 8).permute(0, 3, 1, 2, 4).reshape(R, 32, K // 16, 16)[..., inv]
+    q = l8.detach().cpu().view(torch.uint8).reshape(R, K // 64, 2, 2, 32, 2, 8)        # [R][c][x][hw][row][sp][j]
+    q = q.permute(0, 4, 1, 2, 5, 3, 6).reshape(R, 32, K // 16, 16)[..., inv]
+    return hf.reshape(R * 32, K)[:M].contiguous(), q.reshape(R * 32, K)[:M].contiguous()
+
+
 def mx_matmul_reference(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """float64 statement of what an MX kernel computes for a [M][K] x w [N][K]^T (the operand roundings exactly, the sums in float64)."""
     ah, al8, _ = mx_split(a)

@@ -431,7 +431,7 @@ static int vit_forward_impl(const wvn_vit_model* m, const void* img, int img_u8,
     }
     {
       Span s(4, st);
-      if (bf) RET_IF(opk.attention((const bf16_t*)w.q, (const bf16_t*)w.k, (const bf16_t*)w.v, (bf16_t*)w.xn, d.B, d.H, d.ntok, d.ntok_s, d.npad, 0.f, st, nullptr, nullptr, 0));
+      if (bf) RET_IF(opk.attention((const bf16_t*)w.q, (const bf16_t*)w.k, (const bf16_t*)w.v, (bf16_t*)w.xn, d.B, d.H, d.ntok, d.ntok_s, d.npad, 0.f, st, nullptr, nullptr, 0, -1));
       else if (mix && mx) RET_IF(wvn_attention_bf16_launch_f16((const bf16_t*)w.q, (const bf16_t*)w.k, (const bf16_t*)w.v, (bf16_t*)w.xn, d.B, d.H, d.ntok, d.ntok_s, d.npad, 0.f, st, (bf16_t*)xn_l8, qsplit ? lo(w.q, pl_qkv) : nullptr, 2));
       else if (mix) RET_IF(wvn_attention_bf16_launch_f16((const bf16_t*)w.q, (const bf16_t*)w.k, (const bf16_t*)w.v, (bf16_t*)w.xn, d.B, d.H, d.ntok, d.ntok_s, d.npad, 0.f, st, lo(w.xn, pl_xn), qsplit ? lo(w.q, pl_qkv) : nullptr, attn_frag ? 1 : 0));
       else if (x3) RET_IF(wvn_attention_x3_launch((const bf16_t*)w.q, lo(w.q, pl_qkv), (const bf16_t*)w.k, lo(w.k, pl_qkv), (const bf16_t*)w.v, lo(w.v, pl_qkv), (bf16_t*)w.xn, lo(w.xn, pl_xn), d.B, d.H, d.ntok, d.ntok_s, d.npad, scale, st));
@@ -782,6 +782,15 @@ int wvn_debug_n384_pair(int on) {
 int wvn_debug_kmeans_screen_stats(unsigned long long* out, int reset) { return out ? wvn_kmeans_pixels_screen_stats(out, reset) : WVN_ERR_ARG; }
 int wvn_debug_kmeans_assign_form(int form) { wvn_kmeans_pixels_set_assign_form(form); return WVN_OK; }
 int wvn_debug_attention_variant(int v) { wvn_attention_bf16_set_variant(v); wvn_attention_bf16_set_variant_f16(v); return WVN_OK; }
+int wvn_debug_attention_planes(const void* q, const void* q_lo, const void* k, const void* vt, void* out, void* out_lo, int B, int heads, int ntok,
+                               int ntok_s, int npad, int out_frag, int qsplit_form, void* stream) {
+  // the combinations wvn_vit_forward launches in WVN_PREC_MIX (plus the single row-major output of wvn_attention_f16), nothing else
+  if (!q || !k || !vt || !out || B < 1 || heads < 1 || ntok < 1 || ntok_s < ntok || ntok_s > npad) return WVN_ERR_ARG;
+  if (qsplit_form < 0 || qsplit_form > 2 || (qsplit_form == 0) != (q_lo == nullptr)) return WVN_ERR_ARG;
+  if (out_frag < 0 || out_frag > 2 || (out_frag != 0 && (!out_lo || heads != 6))) return WVN_ERR_ARG;
+  return wvn_attention_bf16_launch_f16((const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)out, B, heads, ntok, ntok_s, npad, 0.f,
+                                       (hipStream_t)stream, (bf16_t*)out_lo, (const bf16_t*)q_lo, out_frag, qsplit_form);
+}
 
 int wvn_debug_gemm_bf16_timed(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, int M,
                               int N, int K, int epi, long long* dbg, void* stream) {

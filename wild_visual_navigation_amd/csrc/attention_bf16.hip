@@ -595,12 +595,14 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
 long long* g_attn_dbg = nullptr;  // set by wvn_debug_attention_timing (scripts/attn_timing.py)
 
 constexpr int ATTN_DEFAULT = 1;
-int g_attn_variant = ATTN_DEFAULT;
-int g_attn_qsplit_form = 2;   // two-plane q: 2 = the second plane on a scaled e5m2 MFMA (round 6, fp16 build), 1 = both planes on fp16 MFMAs (round 4)   // 0: exact per-tile row max, 1: lazy (alarm on the row sums; what ships: -4 % attention time)
+int g_attn_variant = ATTN_DEFAULT;   // 0: exact per-tile row max, 1: lazy (alarm on the row sums; what ships: -4 % attention time)
+int g_attn_qsplit_form = 2;   // two-plane q: 2 = the second plane on a scaled e5m2 MFMA (round 6, fp16 build), 1 = both planes on fp16 MFMAs (round 4)
 
+// form: the form of the two-plane q (read only when q_lo is set): g_attn_qsplit_form for the product's launches, the caller's own for
+// wvn_debug_attention_planes
 void launch_pre(bool xcd, dim3 grid, hipStream_t st, const op16_t* q, const op16_t* k, const op16_t* vt, op16_t* out,
-                int heads, int nbh, int nqb, int ntok, int ntok_s, int npad, op16_t* out_lo, const op16_t* q_lo, int out_frag) {
-  if (q_lo && WVN_OPERAND_F16 && g_attn_qsplit_form == 2) {   // two-plane q, the second plane on ONE scaled e5m2 MFMA per sub-tile (round 6); 148 registers: three
+                int heads, int nbh, int nqb, int ntok, int ntok_s, int npad, op16_t* out_lo, const op16_t* q_lo, int out_frag, int form) {
+  if (q_lo && WVN_OPERAND_F16 && form == 2) {   // two-plane q, the second plane on ONE scaled e5m2 MFMA per sub-tile (round 6); 148 registers: three
     // workgroups per CU (forced to four -- 128 registers, 68 bytes of scratch -- it runs 14 % slower: 31.0 against 27.2 ms of attention per step)
     if (xcd)
       hipLaunchKernelGGL((attention_bf16_kernel<2, true, 3, false, true, 0, true, 2>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
@@ -676,7 +678,8 @@ void WVN_OPSYM(wvn_attention_bf16_set_variant)(int v) {
 // scale > 0: q holds the raw projections.  scale == 0: q is pre-multiplied by softmax_scale * log2(e) (EPI_QKV with
 // q_scale set), the kernel with the running max folded into the S^T MFMA chain runs.
 int WVN_OPSYM(wvn_attention_bf16_launch)(const op16_t* q, const op16_t* k, const op16_t* vt, op16_t* out, int B, int heads,
-                              int ntok, int ntok_s, int npad, float scale, hipStream_t st, op16_t* out_lo, const op16_t* q_lo, int out_frag) {
+                              int ntok, int ntok_s, int npad, float scale, hipStream_t st, op16_t* out_lo, const op16_t* q_lo, int out_frag,
+                              int qsplit_form) {
   // out_lo (WVN_PREC_MIX): the normalised output leaves as two bf16 planes, hi = bf16(o) -> out, lo = bf16(o - hi) -> out_lo (the
   // operand representation of the exact-mode projection GEMM), straight from the fp32 accumulators -- whatever this build's own
   // operand format is
@@ -687,7 +690,8 @@ int WVN_OPSYM(wvn_attention_bf16_launch)(const op16_t* q, const op16_t* k, const
   dim3 grid(nqb * nbh);
   const bool xcd = (nbh % 8) == 0;  // the XCD decode needs whole groups of 8 (frame, head) pairs
   if (scale == 0.f && !g_attn_dbg) {
-    launch_pre(xcd, grid, st, q, k, vt, out, heads, nbh, nqb, ntok, ntok_s, npad, out_lo, q_lo, out_frag);
+    launch_pre(xcd, grid, st, q, k, vt, out, heads, nbh, nqb, ntok, ntok_s, npad, out_lo, q_lo, out_frag,
+               qsplit_form < 0 ? g_attn_qsplit_form : qsplit_form);
     WVN_LAUNCH_CHECK();
     return WVN_OK;
   }
