@@ -562,6 +562,35 @@ int wvn_pixel_mlp_infer_exact(const wvn_mlp_desc* d, const float* params, const 
                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Fused per-segment traversability inference: the node's per-frame path with prediction_per_pixel = False
+ * (wvn_feature_extractor_node.py:320-366, quick_start.py:184-210):
+ *   input_feat = feat[seg.reshape(-1)];  out = SimpleMLP(input_feat)
+ *   trav = out[:,0] (after its sigmoid);  loss_reco = mse(out[:,1:], input_feat);  conf = confidence(loss_reco)
+ * with the MLP evaluated once per SEGMENT row and the results painted onto the segment maps (csrc/segment_predict.hip):
+ * no [H*W, D] gather, two launches, no host synchronisation.  fp32 FMA throughout, one fixed summation order per row: a
+ * pixel's outputs depend on its segment's features and the parameters only (not on B, S or the row's position).
+ *
+ * feat     : [B][S][D] fp32, element (b, s, k) at feat[b * ld_frame + s * ld_row + k]; ld_row >= D, ld_frame >= 0 (0: every
+ *            frame shares one table).  NaN rows are allowed (extract_batch writes them for ids a frame does not contain): they
+ *            give NaN at the pixels that reference them and nowhere else.
+ * seg      : [B][H][W] segment ids, int32 (seg_bytes = 4, extract_batch) or int64 (seg_bytes = 8, extract).  Id rule of torch
+ *            indexing: ids in [0, S) select row id, ids in [-S, 0) select row S + id (the -1 ids of segmentation_type
+ *            "random"), any other id gives NaN in every output.
+ * trav / conf / loss_reco : [B][H][W] fp32, each may be NULL.  mean/std/std_factor: ConfidenceGenerator state; conf_state
+ *            (may be NULL): the same three floats in DEVICE memory, read instead of the scalars (HIP-graph capture).
+ * workspace: wvn_segment_predict_workspace_bytes() bytes, 16-byte aligned, no initialisation needed (receives the per-segment
+ *            table {trav, conf, loss_reco, 0}, [B*S][4] fp32).  params: the flat parameter buffer, 16-byte aligned.
+ * Limits: H1 = 256, H2 = 32, 1 <= D <= 1024; B <= 65535, B*S <= 2^26, H*W < 2^31.  WVN_ERR_ARG otherwise (and for NULL
+ * params / feat / seg / workspace or seg_bytes other than 4 or 8), checked on the host before any GPU call; the workspace
+ * query returns 0 for an unsupported geometry.
+ * ------------------------------------------------------------------------------------------- */
+size_t wvn_segment_predict_workspace_bytes(const wvn_mlp_desc* d, int B, int S);
+int wvn_segment_predict(const wvn_mlp_desc* d, const float* params, const float* feat, int ld_row, long long ld_frame,
+                        int B, int S, const void* seg, int seg_bytes, int H, int W, float mean, float std, float std_factor,
+                        const float* conf_state, float* trav, float* conf, float* loss_reco, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A -> B wire format: the per-frame wild_visual_navigation_msgs/ImageFeatures message built at
  * wvn_feature_extractor_node.py:373-393 (seg.cpu().numpy().astype(np.int32) + feat.cpu().numpy().flatten().tolist()) and
  * decoded at wvn_learning_node.py:651-656.  wvn_wire_pack lays the frame out on the device as the message carries it:

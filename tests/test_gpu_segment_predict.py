@@ -1,0 +1,229 @@
+"""Fused per-segment traversability inference (csrc/segment_predict.hip, SimpleMLP.forward_per_segment,
+FeatureExtractor.predict_per_segment) against the reference sequence of the per-segment mode
+(quick_start.py:184-210 with --no-prediction_per_pixel, wvn_feature_extractor_node.py:320-366):
+   input_feat = feat[seg.reshape(-1)]; prediction = model.forward(Data(x=input_feat));
+   trav = prediction[:, 0]; conf = confidence_generator.inference_without_update(mse(prediction[:, 1:], input_feat)).
+
+Every output is a function of one segment row, so the kernel is held to an fp64 oracle evaluated once per segment (fp32 FMA
+error bars below) and to bit-exact invariances: batching, row order, alignment."""
+import pytest
+import torch
+
+from oracle import mlp as OM, vit as OV
+from wild_visual_navigation_amd import _lib
+from wild_visual_navigation_amd.cfg import ExperimentParams
+from wild_visual_navigation_amd.feature_extractor import FeatureExtractor
+from wild_visual_navigation_amd.model import get_model
+from wild_visual_navigation_amd.utils import ConfidenceGenerator, Data
+
+pytestmark = pytest.mark.gpu
+
+MEAN, STD, FAC = 0.9, 0.25, 0.5
+
+
+def g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _model(dev, D, seed=7):
+    params = ExperimentParams()
+    params.model.simple_mlp_cfg.input_size = D
+    model = get_model(params.model).to(dev)
+    model.eval()
+    sd = OM.make_mlp_state_dict(D, seed=seed)
+    model.load_state_dict(sd, strict=False)
+    return model, sd
+
+
+def _oracle_rows(sd, feat):
+    """feat [B, S, D] fp32 -> per-segment (trav, loss, conf) [B, S] in float64 (conf: confidence_generator.py:182-193)."""
+    sd64 = {k: v.double() for k, v in sd.items()}
+    B, S, D = feat.shape
+    x = feat.reshape(B * S, D).double()
+    out = OM.mlp_forward(sd64, x)
+    loss = ((out[:, 1:] - x) ** 2).mean(1)
+    conf = OM.confidence_from_stats(loss, MEAN, STD, FAC).double()
+    return out[:, 0].reshape(B, S), loss.reshape(B, S), conf.reshape(B, S)
+
+
+def _paint(rows, seg):
+    """rows [B, S], seg [B, H, W] with ids in [0, S) -> [B, H, W]."""
+    return torch.stack([rows[b][seg[b].long()] for b in range(seg.shape[0])])
+
+
+def _features(B, S, D, seed):
+    return torch.randn(B, S, D, generator=g(seed))      # |x| ~ 1: reconstruction losses around the confidence window [0.775, 1.275]
+
+
+@pytest.mark.parametrize("HW", [(37, 53), (224, 224), (448, 448)])
+@pytest.mark.parametrize("S", [1, 20, 196])
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("D", [90, 384, 768])
+def test_kernel_matches_fp64_oracle(dev, D, B, S, HW):
+    H, W = HW
+    model, sd = _model(dev, D)
+    feat = _features(B, S, D, seed=D + 10 * B + S)
+    seg = torch.randint(0, S, (B, H, W), generator=g(S + H), dtype=torch.int32)
+    trav, conf, loss = model.forward_per_segment(feat.to(dev), seg.to(dev), MEAN, STD, FAC, want_loss=True)
+    assert trav.shape == (B, H, W) and conf.shape == (B, H, W) and loss.shape == (B, H, W)
+    t0, l0, c0 = (_paint(r, seg) for r in _oracle_rows(sd, feat))
+    assert (trav.cpu().double() - t0).abs().max().item() <= 1e-5
+    assert ((loss.cpu().double() - l0).abs() / l0).max().item() <= 1e-5
+    assert (conf.cpu().double() - c0).abs().max().item() <= 1e-4
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("D", [90, 384, 768, 1024])
+def test_one_segment_per_pixel(dev, D, B):
+    """S = H*W at 64 x 64 (4096 rows per frame: the table is read through L2, not staged in LDS); D = 1024 is the largest
+    geometry (the table kernel's LDS tile beyond 64 KB)."""
+    H = W = 64
+    S = H * W
+    model, sd = _model(dev, D)
+    feat = _features(B, S, D, seed=D + B)
+    seg = torch.stack([torch.randperm(S, generator=g(b)).reshape(H, W) for b in range(B)])     # int64 ids
+    trav, conf, loss = model.forward_per_segment(feat.to(dev), seg.to(dev), MEAN, STD, FAC, want_loss=True)
+    t0, l0, c0 = (_paint(r, seg) for r in _oracle_rows(sd, feat))
+    assert (trav.cpu().double() - t0).abs().max().item() <= 1e-5
+    assert ((loss.cpu().double() - l0).abs() / l0).max().item() <= 1e-5
+    assert (conf.cpu().double() - c0).abs().max().item() <= 1e-4
+
+
+@pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
+def test_id_rule(dev, dtype):
+    """torch indexing: ids in [-S, 0) select row S + id; ids >= S or < -S give NaN in all three outputs; NaN rows nobody references
+    leave every other pixel finite."""
+    S, D, H, W = 20, 384, 37, 53
+    model, _ = _model(dev, D)
+    feat = _features(1, S, D, seed=5)
+    feat[0, 3] = float("nan")                                   # rows of ids a frame does not contain (extract_batch)
+    feat[0, 17] = float("nan")
+    ok = torch.tensor([i for i in range(S) if i not in (3, 17)])
+    seg = ok[torch.randint(0, len(ok), (H, W), generator=g(1))]
+    wrapped = torch.arange(-S, 0)
+    wrapped = wrapped[~torch.isin(wrapped + S, torch.tensor([3, 17]))]
+    seg[0, : len(wrapped)] = wrapped                            # every legal negative id once
+    bad = torch.tensor([S, S + 1, 1000, -S - 1, -1000, 2 ** 31 - 1, -(2 ** 31)])
+    seg[1, : len(bad)] = bad
+    seg = seg.to(dtype)
+    trav, conf, loss = model.forward_per_segment(feat.to(dev), seg.to(dev), MEAN, STD, FAC, want_loss=True)
+    trav, conf, loss = trav.cpu(), conf.cpu(), loss.cpu()
+    badmask = torch.zeros(H, W, dtype=torch.bool)
+    badmask[1, : len(bad)] = True
+    for out in (trav, conf, loss):
+        assert torch.isnan(out[badmask]).all()
+        assert torch.isfinite(out[~badmask]).all()
+    # a wrapped id paints exactly what its non-negative twin paints
+    ref_t, ref_c, ref_l = model.forward_per_segment(feat.to(dev), torch.arange(S, dtype=dtype, device=dev)[None], MEAN, STD, FAC,
+                                                    want_loss=True)
+    for out, ref in ((trav, ref_t), (conf, ref_c), (loss, ref_l)):
+        assert torch.equal(out[0, : len(wrapped)], ref.cpu()[0, (wrapped + S)])
+        assert torch.equal(out[~badmask], ref.cpu()[0, seg[~badmask].long() % S])
+
+
+def test_invariances_bit_exact(dev):
+    """A frame computed inside a batch equals the frame computed alone; permuting the table rows with a matching relabel of seg
+    changes no bit; unaligned segment maps / outputs (the one-pixel path) paint the same bits as aligned ones."""
+    B, S, D, H, W = 3, 196, 384, 37, 53
+    model, _ = _model(dev, D)
+    feat = _features(B, S, D, seed=11).to(dev)
+    seg = torch.randint(0, S, (B, H, W), generator=g(12), dtype=torch.int32).to(dev)
+    batch = model.forward_per_segment(feat, seg, MEAN, STD, FAC, want_loss=True)
+    for b in range(B):
+        alone = model.forward_per_segment(feat[b], seg[b], MEAN, STD, FAC, want_loss=True)
+        for x, y in zip(batch, alone):
+            assert torch.equal(x[b], y)
+    perm = torch.randperm(S, generator=g(13)).to(dev)           # new row i = old row perm[i]
+    inv = torch.argsort(perm).to(torch.int32)
+    permuted = model.forward_per_segment(feat[:, perm], inv[seg.long()], MEAN, STD, FAC, want_loss=True)
+    for x, y in zip(batch, permuted):
+        assert torch.equal(x, y)
+    # 4-byte offset segment map: no 16-byte accesses
+    buf = torch.empty(B * H * W + 1, dtype=torch.int32, device=dev)
+    buf[1:] = seg.reshape(-1)
+    off = model.forward_per_segment(feat, buf[1:].view(B, H, W), MEAN, STD, FAC, want_loss=True)
+    for x, y in zip(batch, off):
+        assert torch.equal(x, y)
+    # any output may be left out
+    t_only = model.forward_per_segment(feat, seg, MEAN, STD, FAC)
+    assert t_only[2] is None and torch.equal(t_only[0], batch[0]) and torch.equal(t_only[1], batch[1])
+
+
+def _reference_sequence(model, cg, feat, seg):
+    """quick_start.py:184-210: gather, forward, column 0, confidence (fp32, through the drop-in's own forward)."""
+    x = feat[seg.reshape(-1).long()]
+    pred = model.forward(Data(x=x))
+    mse = ((pred[:, 1:] - x) ** 2).mean(1)
+    return pred[:, 0].reshape(seg.shape), cg.inference_without_update(mse).reshape(seg.shape)
+
+
+@pytest.mark.parametrize("seg_type,feat_type", [("grid", "dino"), ("slic", "dino"), ("stego", "stego")])
+def test_predict_per_segment_equals_reference_sequence(dev, golden, seg_type, feat_type):
+    """Drop-in level on the reference's demo frames, in the three (segmentation, features) combinations the constructor accepts."""
+    frames = golden("demo_frames_224.pt")["frames_u8"][:2].to(dev)
+    sd = OV.make_vit_state_dict("vit_small", 8, pretrain_grid=28, seed=21, depth=2)
+    fe = FeatureExtractor(device=dev, segmentation_type=seg_type, feature_type=feat_type, patch_size=8, backbone_type="vit_small",
+                          input_size=224, pretrained_weights=sd, run_clustering=True)
+    model, _ = _model(dev, fe.feature_dim, seed=42)
+    cg = ConfidenceGenerator(method="latest_measurement", std_factor=FAC).to(dev)
+    cg.mean[0], cg.std[0] = MEAN, STD
+    trav, conf, loss, feat, seg, nseg = fe.predict_per_segment(frames, model, cg, want_loss=True)
+    assert trav.shape == (2, 224, 224) and conf.shape == (2, 224, 224) and loss.shape == (2, 224, 224)
+    feat_b, seg_b, nseg_b = fe.extract_batch(frames)
+    assert torch.equal(feat.isnan(), feat_b.isnan()) and torch.equal(torch.nan_to_num(feat), torch.nan_to_num(feat_b))
+    assert torch.equal(seg, seg_b) and torch.equal(nseg, nseg_b)
+    for b in range(2):
+        n = int(nseg[b])
+        t_ref, c_ref = _reference_sequence(model, cg, feat[b, :n], seg[b])
+        assert (trav[b] - t_ref).abs().max().item() <= 1e-5, (seg_type, b)
+        assert (conf[b] - c_ref).abs().max().item() <= 1e-4, (seg_type, b)
+
+
+def test_random_segmentation_wraps_minus_one(dev, golden):
+    """segmentation_type='random' leaves -1 on every unsampled pixel; the reference's feat[seg] wraps it onto the last row."""
+    frames = golden("demo_frames_224.pt")["frames_u8"][:1]
+    sd = OV.make_vit_state_dict("vit_small", 8, pretrain_grid=28, seed=21, depth=2)
+    fe = FeatureExtractor(device=dev, segmentation_type="random", feature_type="dino", patch_size=8, backbone_type="vit_small",
+                          input_size=224, pretrained_weights=sd)
+    model, _ = _model(dev, fe.feature_dim, seed=42)
+    cg = ConfidenceGenerator(method="latest_measurement", std_factor=FAC).to(dev)
+    cg.mean[0], cg.std[0] = MEAN, STD
+    _, feat, seg, _, _ = fe.extract(img=(frames.float() / 255).to(dev), n_random_pixels=100)
+    assert feat.shape[0] == 100 and seg.dtype == torch.int64 and (seg == -1).any()
+    trav, conf, _ = model.forward_per_segment(feat, seg, MEAN, STD, FAC)
+    t_ref, c_ref = _reference_sequence(model, cg, feat, seg)
+    assert torch.isfinite(trav).all()
+    assert (trav - t_ref).abs().max().item() <= 1e-5
+    assert (conf - c_ref).abs().max().item() <= 1e-4
+    assert (trav[seg == -1] == trav[seg == 99]).all()                          # the one pixel of segment 99
+
+
+def test_confidence_state_from_device_memory(dev):
+    """conf_state (device {mean, std, std_factor}) overrides the scalar arguments: the form a captured HIP graph needs."""
+    model, _ = _model(dev, 384)
+    feat = _features(2, 20, 384, seed=3).to(dev)
+    seg = torch.randint(0, 20, (2, 64, 80), generator=g(4), dtype=torch.int32).to(dev)
+    a = model.forward_per_segment(feat, seg, MEAN, STD, FAC, want_loss=True)
+    state = torch.tensor([MEAN, STD, FAC], dtype=torch.float32, device=dev)
+    b = model.forward_per_segment(feat, seg, 123.0, 456.0, 7.0, want_loss=True, conf_state=state)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
+    c = model.forward_per_segment(feat, seg, MEAN, 2 * STD, FAC)
+    assert not torch.equal(a[1], c[1])
+
+
+def test_refusals(dev):
+    model, _ = _model(dev, 384)
+    feat = _features(1, 20, 384, seed=1)
+    seg = torch.randint(0, 20, (1, 16, 16), generator=g(2), dtype=torch.int32)
+    with pytest.raises(_lib.WvnError):
+        model.forward_per_segment(feat, seg.to(dev))                       # CPU features
+    with pytest.raises(_lib.WvnError):
+        model.forward_per_segment(feat.to(dev), seg)                       # CPU segment map
+    with pytest.raises(_lib.WvnError):
+        model.forward_per_segment(feat.to(dev), seg.float().to(dev))       # float ids
+    with pytest.raises(_lib.WvnError):
+        model.forward_per_segment(feat[..., :383].to(dev), seg.to(dev))    # fewer than D columns
+    with pytest.raises(_lib.WvnError):
+        model.forward_per_segment(feat.double().to(dev), seg.to(dev))      # fp64 features
+    with pytest.raises(_lib.WvnError):
+        model.forward_per_segment(feat.expand(2, 20, 384).to(dev), seg.to(dev))   # 2 tables for 1 map

@@ -174,6 +174,8 @@ _SIGNATURES = {
     "wvn_pixel_mlp_exact_pack": ([_p, _p, _p, _p], _i),
     "wvn_pixel_mlp_infer_exact": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
     "wvn_pixel_mlp_infer": ([_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p], _i),
+    "wvn_segment_predict_workspace_bytes": ([_p, _i, _i], _sz),
+    "wvn_segment_predict": ([_p, _p, _p, _i, _ll, _i, _i, _p, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
     "wvn_debug_gemm_bf16_timed": ([_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p], _i),
     "wvn_debug_f16_saturate": ([_p, _p, _i, _p], _i),
     "wvn_debug_attention_timing": ([_p], _i),

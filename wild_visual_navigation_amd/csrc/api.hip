@@ -1156,6 +1156,30 @@ int wvn_pixel_mlp_infer_exact(const wvn_mlp_desc* d, const float* params, const 
                                           workspace_bytes, (hipStream_t)stream);
 }
 
+// fused per-segment inference (segment_predict.hip)
+size_t wvn_segment_predict_workspace_bytes(const wvn_mlp_desc* d, int B, int S) {
+  if (!d || !wvn_segment_predict_supported(d->D, d->H1, d->H2) || B <= 0 || S <= 0) return 0;
+  if ((long long)B * S > (1ll << 26)) return 0;
+  return wvn_segment_predict_workspace_bytes_impl(B, S);
+}
+int wvn_segment_predict(const wvn_mlp_desc* d, const float* params, const float* feat, int ld_row, long long ld_frame,
+                        int B, int S, const void* seg, int seg_bytes, int H, int W, float mean, float std, float std_factor,
+                        const float* conf_state, float* trav, float* conf, float* loss_reco, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  // every check is host arithmetic: a refused call touches no GPU state
+  if (!d || !params || !feat || !seg || !workspace) return WVN_ERR_ARG;
+  if (!wvn_segment_predict_supported(d->D, d->H1, d->H2)) return WVN_ERR_ARG;
+  if (B <= 0 || S <= 0 || H <= 0 || W <= 0 || B > 65535) return WVN_ERR_ARG;
+  if ((long long)B * S > (1ll << 26) || (long long)H * W > 0x7fffffffll) return WVN_ERR_ARG;
+  if (seg_bytes != 4 && seg_bytes != 8) return WVN_ERR_ARG;
+  if (ld_row < d->D || ld_frame < 0) return WVN_ERR_ARG;
+  if (((uintptr_t)params | (uintptr_t)workspace) & 15) return WVN_ERR_ARG;
+  if (((uintptr_t)seg & (seg_bytes - 1)) || ((uintptr_t)feat & 3)) return WVN_ERR_ARG;
+  if (workspace_bytes < wvn_segment_predict_workspace_bytes_impl(B, S)) return WVN_ERR_WORKSPACE;
+  return wvn_segment_predict_launch(d->D, params, feat, ld_row, ld_frame, B, S, seg, seg_bytes, H, W, mean, std, std_factor,
+                                    conf_state, trav, conf, loss_reco, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int wvn_mlp_confidence(const float* out, int ldo, const float* x, int ldx, float mean, float std, float std_factor,
                        float* trav, float* conf, int R, int D, void* stream) {
   if (!out || !x) return WVN_ERR_ARG;

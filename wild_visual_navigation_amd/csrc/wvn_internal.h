@@ -273,6 +273,14 @@ int wvn_pixel_mlp_infer_exact_launch(int D, int h1, int h2, const float* params,
                                      const float* conf_state, float* trav, float* conf, float* loss, void* workspace,
                                      size_t workspace_bytes, hipStream_t st);
 
+// ---- fused per-segment traversability inference (segment_predict.hip) --------------------------------------------------
+bool wvn_segment_predict_supported(int D, int h1, int h2);
+size_t wvn_segment_predict_workspace_bytes_impl(int B, int S);
+int wvn_segment_predict_launch(int D, const float* params, const float* feat, int ld_row, long long ld_frame, int B, int S,
+                               const void* seg, int seg_bytes, int H, int W, float mean, float std, float std_factor,
+                               const float* conf_state, float* trav, float* conf, float* loss, void* workspace,
+                               size_t workspace_bytes, hipStream_t st);
+
 // ---- supervision path (supervision.hip) and SLIC (slic.hip) -------------------------------------------------------------
 int wvn_project_render_fmin_launch(const void* nodes, int n, const float* points, int points_batched, int npts, int C, int H,
                                    int W, const float* value_dev, float value, hipStream_t st);

@@ -209,6 +209,28 @@ class FeatureExtractor:
                 self._extractor._model.forward_tokens(img, lowp_out=zx[:, model.X_COL:])
         return model.forward_per_pixel(zx, B, G, (H, H), mean, std, f, want_loss=want_loss, conf_state=conf_state)
 
+    @torch.no_grad()
+    def predict_per_segment(self, img: torch.Tensor, model, confidence_generator=None, want_loss: bool = False,
+                            backbone_out: Optional[torch.Tensor] = None, **kwargs):
+        """The live node's per-frame prediction WITHOUT ``prediction_per_pixel`` (wvn_feature_extractor_node.py:320-366;
+        quick_start.py:184-210) for a batch: img [B,3,H,W] -> (trav [B,H,W], conf [B,H,W], loss_reco | None, feat [B,S,D],
+        seg [B,H,W] int32, nseg [B]).  ``extract_batch(img, backbone_out, **kwargs)`` (grid, slic or stego segmentation), then
+        ``model.forward_per_segment(feat, seg)``: equivalent to ``feat[seg.reshape(-1)]`` -> ``model.forward`` -> column 0 /
+        ``confidence_generator.inference_without_update(mse(pred[:, 1:], x))`` per frame, with the MLP run once per segment
+        (csrc/segment_predict.hip).  ``feat`` / ``seg`` / ``nseg`` are extract_batch's, for the training messages of the same pass.
+        A confidence generator on the GPU is read from device memory: no host synchronisation beyond extract_batch's own."""
+        feat, seg, nseg = self.extract_batch(img, backbone_out=backbone_out, **kwargs)
+        mean, std, f, conf_state = 0.0, 1.0, 0.5, None
+        if confidence_generator is not None:
+            cg = confidence_generator
+            if cg.mean.device == feat.device:
+                conf_state = torch.cat([cg.mean.detach().reshape(1).float(), cg.std.detach().reshape(1).float(),
+                                        torch.full((1,), float(cg.std_factor), dtype=torch.float32, device=feat.device)])
+            else:
+                mean, std, f = float(cg.mean), float(cg.std), float(cg.std_factor)
+        trav, conf, loss = model.forward_per_segment(feat, seg, mean, std, f, want_loss=want_loss, conf_state=conf_state)
+        return trav, conf, loss, feat, seg, nseg
+
     def _grid(self) -> int:
         return self._extractor.grid
 

@@ -37,6 +37,7 @@ class SimpleMLP(torch.nn.Module):
         self._pix_packed: Optional[torch.Tensor] = None
         self._pix_packed_x3: Optional[torch.Tensor] = None
         self._pix_ws: Optional[torch.Tensor] = None
+        self._seg_ws: Optional[torch.Tensor] = None
 
     # ---- flat parameter storage --------------------------------------------------------------------
     def _params_in_order(self):
@@ -167,4 +168,54 @@ class SimpleMLP(torch.nn.Module):
                                          loss.data_ptr() if want_loss else 0, self._pix_ws.data_ptr(), self._pix_ws.numel(),
                                          _lib.stream())
         _lib.check(rc, "wvn_pixel_mlp_infer_exact")
+        return trav, conf, loss
+
+    # ---- fused per-segment inference ------------------------------------------------------------------
+    @torch.no_grad()
+    def forward_per_segment(self, feat: torch.Tensor, seg: torch.Tensor, mean: float = 0.0, std: float = 1.0,
+                            std_factor: float = 0.5, want_loss: bool = False, conf_state: Optional[torch.Tensor] = None):
+        """What wvn_feature_extractor_node.py:320-366 / quick_start.py:184-210 compute without prediction_per_pixel --
+        ``feat[seg.reshape(-1)]`` -> ``forward`` -> column 0 / reconstruction confidence -- with the MLP run once per segment
+        and the results painted onto the map (csrc/segment_predict.hip): ``feat`` [S, D] or [B, S, D] fp32 (NaN rows allowed),
+        ``seg`` [H, W] or [B, H, W] int32 / int64 ids (ids in [-S, 0) wrap to row S + id as in torch indexing, any other
+        out-of-range id gives NaN) -> (trav, conf, loss_reco | None), fp32 with the shape of ``seg``.  ``conf_state``: optional
+        fp32 device tensor {mean, std, std_factor} read by the kernel instead of the three floats (for HIP-graph capture)."""
+        _lib.require_cuda(feat, "feat")
+        _lib.require_cuda(seg, "seg")
+        D = self.input_size
+        if feat.dtype != torch.float32 or feat.dim() not in (2, 3) or feat.shape[-1] < D:
+            raise _lib.WvnError(f"feat must be fp32 [S, >= {D}] or [B, S, >= {D}], got {tuple(feat.shape)} {feat.dtype}")
+        if seg.dtype not in (torch.int32, torch.int64) or seg.dim() not in (2, 3):
+            raise _lib.WvnError(f"seg must be int32 / int64 [H, W] or [B, H, W], got {tuple(seg.shape)} {seg.dtype}")
+        f3 = feat if feat.dim() == 3 else feat[None]
+        s3 = seg if seg.dim() == 3 else seg[None]
+        if f3.shape[0] != s3.shape[0]:
+            raise _lib.WvnError(f"feat and seg hold different numbers of frames: {tuple(feat.shape)} vs {tuple(seg.shape)}")
+        if f3.stride(2) != 1 or f3.stride(1) < D:
+            f3 = f3.contiguous()
+        s3 = s3.contiguous()
+        if conf_state is not None:
+            _lib.require_cuda(conf_state, "conf_state")
+            if conf_state.dtype != torch.float32 or conf_state.numel() < 3 or not conf_state.is_contiguous():
+                raise _lib.WvnError("conf_state must be a contiguous fp32 device tensor {mean, std, std_factor}")
+        B, S = f3.shape[0], f3.shape[1]
+        H, W = s3.shape[1], s3.shape[2]
+        h = _lib.lib()
+        flat = self.flat_params()
+        _lib.require_cuda(flat, "parameters")
+        need = h.wvn_segment_predict_workspace_bytes(C.byref(self.desc), B, S)
+        if need == 0:
+            raise _lib.WvnError(f"fused per-segment inference needs SimpleMLP(D <= 1024, [256, 32, 1], reconstruction=True) and "
+                                f"B * S <= 2^26, got D = {D}, B = {B}, S = {S}")
+        if self._seg_ws is None or self._seg_ws.numel() < need or self._seg_ws.device != feat.device:
+            self._seg_ws = torch.empty(need, dtype=torch.uint8, device=feat.device)
+        trav = torch.empty(seg.shape, dtype=torch.float32, device=seg.device)
+        conf = torch.empty_like(trav)
+        loss = torch.empty_like(trav) if want_loss else None
+        rc = h.wvn_segment_predict(C.byref(self.desc), flat.data_ptr(), f3.data_ptr(), f3.stride(1), f3.stride(0), B, S,
+                                   s3.data_ptr(), s3.element_size(), H, W, float(mean), float(std), float(std_factor),
+                                   conf_state.data_ptr() if conf_state is not None else 0, trav.data_ptr(), conf.data_ptr(),
+                                   loss.data_ptr() if want_loss else 0, self._seg_ws.data_ptr(), self._seg_ws.numel(),
+                                   _lib.stream())
+        _lib.check(rc, "wvn_segment_predict")
         return trav, conf, loss
