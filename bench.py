@@ -27,10 +27,11 @@ the 64-frame batch over the ranks):
   --precision bf16 : the same kernels with bf16 operands (8 significand bits; same speed, 8x the operand rounding)
 Inputs (a pool of distinct batches) are resident in HBM before the timed region; weights are seeded synthetic (no network).
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = fused attention, HIP-event timed on the launch stream inside
-the timed region), `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, rank 0, N = 1 only) and `parity`
-(the GPU path against that oracle on the same frames: what BASELINE.md 4.5 asks to be reported with every speed number).
-The default run (N = 1, --mode full) times four more legs after the headline leg, each >= 20 steps, and reports them inside the same
-line, each with its own roofline and parity:
+the timed region).  A plain run does nothing else: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+--full adds `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, rank 0, N = 1 only) and `parity`
+(the GPU path against that oracle on the same frames: what BASELINE.md 4.5 asks to be reported with every speed number);
+with --full the default run (N = 1, --mode full) also times more legs after the headline leg, each >= 20 steps, and reports them inside
+the same line, each with its own roofline and parity:
   `fp16_speed`     : the SAME workload with --precision fp16 (the speed path; outside the 1e-3 clause, hence a leg and not `value`)
   `stego_fast`     : the opt-in fast form of the STEGO stage (one backbone pass, k-means over the patch codes, fused pooling), fp16 --
                      less work per frame by definition, reported as an option
@@ -38,7 +39,7 @@ line, each with its own roofline and parity:
   `dinov2_fp8`     : BASELINE configs[4], one GPU's share (DINOv2 ViT-B/14 518^2 + STEGO head, batch 16, fp8 block linears)
   `grid_mixed`     : SURVEY 8(d) C3-(i): the same 64 frames with `grid` segmentation (32-pixel cells, 196 segments per frame, ONE backbone pass,
                      12 544 MLP rows per step: the general learner path) in --precision mixed -- NOT the metric (north_star names the STEGO segmentation)
-(--no-extra-legs skips them; A/B runs and N > 1 runs never run them).
+(--full --no-extra-legs skips them; A/B runs and N > 1 runs never run them).
 """
 import argparse
 import json
@@ -86,7 +87,7 @@ def linear_flops_per_frame(S=448, P=8, D=384, depth=12):
 LINEAR_ISSUE = {"fp16": 1.0, "bf16": 1.0, "exact": 3.0, "mixed": 2.0, "mixed_x3": 3.0, "fp8": 0.5, "fp32": None}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50, help="timed steps of the headline leg (>= 1)")
@@ -102,9 +103,12 @@ def parse():
                     help="'upstream' (default = the defaults of StegoInterface): the code averaged with the mirrored frame's (flip TTA, "
                          "two backbone passes per frame) and k-means over the H x H up-sampled code pixels, as the absent STEGO package "
                          "does it as published (parity unpinned); 'patch' = the opt-in fast form: single pass, k-means over the patch "
-                         "codes (the default run times it as the extra leg stego_fast)")
+                         "codes (--full times it as the extra leg stego_fast)")
     ap.add_argument("--pool", type=int, default=4, help="distinct input batches cycled through the steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg: the CPU-oracle sample and parity blocks and, on the plain default workload, the extra legs "
+                         "(a plain run measures the headline figure only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle sample and the parity blocks")
     ap.add_argument("--attn-variant", type=int, default=None, help="A/B: 0 exact per-tile row max, 1 lazy (alarm on the row sums)")
     ap.add_argument("--no-fuse-proj", action="store_true", help="A/B: the attention projection as its own kernel instead of the fused MLP kernel's prologue")
     ap.add_argument("--no-fuse-qkv", action="store_true", help="A/B: LayerNorm kernel + QKV GEMM instead of the fused kernel")
@@ -113,8 +117,9 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=32)
     ap.add_argument("--precision", default=None, choices=["fp16", "bf16", "mixed", "exact", "fp32", "fp8"],
                     help="default: mixed for --mode full (the <= 1e-3 headline), fp16 for --mode backbone / fast, fp8 for --mode dinov2")
-    ap.add_argument("--no-extra-legs", action="store_true", help="headline leg only (no fp16_speed / stego_fast / backbone_b32 / dinov2_fp8 legs)")
-    ap.add_argument("--extra-steps", type=int, default=20, help="timed steps of each extra leg (after 5 warm-up steps)")
+    ap.add_argument("--no-extra-legs", action="store_true",
+                    help="--full without the extra legs (no fp16_speed / stego_fast / grid_mixed / backbone_b32 / dinov2_fp8 legs)")
+    ap.add_argument("--extra-steps", type=int, default=20, help="--full: timed steps of each extra leg (after 5 warm-up steps)")
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
                     help="process-group backend for N > 1 (default nccl = RCCL; gloo: the multi-process path on a box with one GPU, "
                          "all ranks on cuda:0 -- tests/test_gpu_distributed.py)")
@@ -129,7 +134,7 @@ def parse():
                     help="after the timed steps, write what the headline leg's last timed step returned to its caller as DIR/<name>.npy "
                          "(float32; at most 64 MB in all: a fixed, seeded sample of each array when larger; the result line's 'dumped_outputs' "
                          "records every array's shape and whether it was sampled)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.batch is None:
@@ -649,6 +654,15 @@ def dump_outputs(path, outputs, budget=DUMP_BUDGET_BYTES):
     return manifest
 
 
+def full_extras(args, world):
+    """What runs after the headline leg: (the extra legs, the CPU-oracle sample + parity blocks).  A plain run: neither.  The
+    extra legs: --full on the plain default workload only (N = 1, configs[2], no A/B switch); the oracle: --full, N = 1."""
+    legs = (args.full and world == 1 and args.mode == "full" and args.segmentation == "stego" and args.stego_reading == "upstream"
+            and not args.no_extra_legs and args.attn_variant is None
+            and not (args.no_fuse_proj or args.no_fuse_qkv or args.no_fuse_mlp or args.no_overlap))
+    return legs, args.full and world == 1 and not args.no_cpu_baseline
+
+
 def main():
     args = parse()
     maybe_spawn(args)
@@ -688,10 +702,8 @@ def main():
     dumped = None
     if rank == 0 and args.dump_outputs is not None:
         dumped = dump_outputs(args.dump_outputs, head.pop("outputs"))
-    # the two extra legs: the plain default run only (N = 1, configs[2], no A/B switch), the batches unchanged
-    plain = (world == 1 and args.mode == "full" and args.segmentation == "stego" and args.stego_reading == "upstream"
-             and not args.no_extra_legs and args.attn_variant is None
-             and not (args.no_fuse_proj or args.no_fuse_qkv or args.no_fuse_mlp or args.no_overlap))
+    # the extra legs (the batches unchanged) and the CPU oracle: --full only
+    plain, oracle_sample = full_extras(args, world)
     legs = {}
     SPEED = "fp16"   # the opt-in speed path's operand format
     if plain and args.precision in ("exact", "mixed"):
@@ -782,7 +794,7 @@ def main():
                                              "on the tail stream at high priority, next to the persistent backbone kernels)")
             out["replicas_identical_after_timed_steps"] = head["replicas_identical"]
         orc = None
-        if world == 1 and not args.no_cpu_baseline:
+        if oracle_sample:
             out["cpu_baseline"], orc = cpu_oracle_sample(args, head["fe"])
             out["parity"] = gpu_parity(args, head["fe"], dev, orc, args.precision)
         for name, leg in legs.items():
