@@ -514,6 +514,53 @@ int wvn_mlp_train_phase_b_rows(const wvn_mlp_desc* d, const float* params, const
                                const unsigned char* y_valid, int R, const int* rows_dev, const double* stats, float std_factor,
                                float w_trav, float w_reco, float* grads, float* confidence_out, void* workspace,
                                size_t workspace_bytes, int fused, void* stream);
+/* The step with any ConfidenceGenerator method (utils/confidence_generator.py) and either loss form (utils/loss.py:138-143,
+ * anomaly_balanced).  The _rows entry points above are these with method = WVN_CONF_LATEST_MEASUREMENT, balanced = 1 and no
+ * state, and give the same bits as these with that configuration.
+ *   method   : WVN_CONF_* below.  Every method's update runs before the loss, on this step's positives (the global stats).
+ *   balanced : 1 = anomaly_balanced (unlabelled rows weighted by 1 - confidence), 0 = the plain mean of the raw trav loss.
+ *   state    : [WVN_CONF_STATE_DOUBLES] device doubles, persistent across steps and owned by the caller.  Layout (WVN_CONF_S_*):
+ *              the ConfidenceGenerator parameters mean / var / std (fp32 values), the running_mean sums running_n / sum /
+ *              sum_of_squares, and the moving_average window: a ring of WVN_CONF_WINDOW per-step {n, sum, sum^2} with its head
+ *              and fill count.  Phases A and B only read it; phase C commits the post-update statistic.  Initial value for a
+ *              fresh ConfidenceGenerator: all zeros except var = std = 1.
+ *   minmax   : [2] device floats; phase A writes {max, -min} of the reconstruction loss over the real rows of the shard (-inf for
+ *              an empty one).  Data-parallel ranks all-reduce it with MAX between phases A and B.  Required for
+ *              WVN_CONF_MOVING_AVERAGE (its confidence is min-max scaled over all rows of the step), ignored otherwise.
+ * Same launches as the _rows entry points for every method; no host synchronisation.  WVN_ERR_ARG (before any GPU call) for an
+ * unknown method, a NULL desc or state, or a NULL minmax with WVN_CONF_MOVING_AVERAGE. */
+#define WVN_CONF_LATEST_MEASUREMENT 0
+#define WVN_CONF_RUNNING_MEAN 1
+#define WVN_CONF_KALMAN_FILTER 2
+#define WVN_CONF_MOVING_AVERAGE 3
+#define WVN_CONF_WINDOW 5
+#define WVN_CONF_STATE_DOUBLES 32
+#define WVN_CONF_S_MEAN 0
+#define WVN_CONF_S_VAR 1
+#define WVN_CONF_S_STD 2
+#define WVN_CONF_S_RUN_N 3
+#define WVN_CONF_S_RUN_SUM 4
+#define WVN_CONF_S_RUN_SUMSQ 5
+#define WVN_CONF_S_HEAD 6
+#define WVN_CONF_S_FILL 7
+#define WVN_CONF_S_RING 8 /* [WVN_CONF_WINDOW][3]; slots 23..31 reserved */
+typedef struct wvn_conf_desc {
+  int method;
+  int balanced;
+  double* state;
+  float* minmax;
+} wvn_conf_desc;
+int wvn_mlp_train_phase_a_conf(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const unsigned char* y_valid,
+                               int R, const int* rows_dev, double* stats, void* workspace, size_t workspace_bytes,
+                               unsigned int* sync_word, const wvn_conf_desc* conf, void* stream);
+int wvn_mlp_train_phase_b_conf(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const float* y,
+                               const unsigned char* y_valid, int R, const int* rows_dev, const double* stats, float std_factor,
+                               float w_trav, float w_reco, float* grads, float* confidence_out, void* workspace,
+                               size_t workspace_bytes, int fused, const wvn_conf_desc* conf, void* stream);
+/* phase C of such a step: Adam + losses[5] (conf mean / std = the method's post-update statistic) + the state commit */
+int wvn_mlp_train_phase_c_conf(const wvn_mlp_desc* d, float* params, const float* grads, float* adam_m, float* adam_v, int step,
+                               float lr, const double* stats, float w_trav, float w_reco, float* losses, const wvn_conf_desc* conf,
+                               void* stream);
 /* quick_start.py:194-210 / loss.py:162-164: trav[r] = out[r][0], conf[r] = confidence(mse(out[r][1:], x[r])) */
 int wvn_mlp_confidence(const float* out, int ldo, const float* x, int ldx, float mean, float std, float std_factor,
                        float* trav, float* conf, int R, int D, void* stream);

@@ -46,6 +46,17 @@ class WvnError(RuntimeError):
     pass
 
 
+# ConfidenceGenerator methods of the training step (include/wvn_hip.h: WVN_CONF_*, wvn_conf_desc)
+CONF_METHODS = {"latest_measurement": 0, "running_mean": 1, "kalman_filter": 2, "moving_average": 3}
+CONF_WINDOW = 5
+CONF_STATE_DOUBLES = 32
+CONF_S_MEAN, CONF_S_VAR, CONF_S_STD, CONF_S_RUN_N, CONF_S_RUN_SUM, CONF_S_RUN_SUMSQ, CONF_S_HEAD, CONF_S_FILL, CONF_S_RING = range(9)
+
+
+class ConfDesc(C.Structure):
+    _fields_ = [("method", C.c_int), ("balanced", C.c_int), ("state", C.c_void_p), ("minmax", C.c_void_p)]
+
+
 class VitLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "qkv_w", "proj_w", "fc1_w", "fc2_w", "qkv_b", "proj_b", "fc1_b", "fc2_b", "ln1_g", "ln1_b", "ln2_g", "ln2_b", "ls1", "ls2", "qkv_s", "proj_s", "fc1_s", "fc2_s", "fc2_w_fused", "fc1_w_fused", "qkv_w_fused", "proj_w_frag",
@@ -165,6 +176,9 @@ _SIGNATURES = {
     "wvn_mlp_train_phase_a_rows": ([_p, _p, _p, _i, _p, _i, _p, _p, _p, _sz, _p, _p], _i),
     "wvn_mlp_train_phase_b_rows": ([_p, _p, _p, _i, _p, _p, _i, _p, _p, _f, _f, _f, _p, _p, _p, _sz, _i, _p], _i),
     "wvn_mlp_train_phase_c": ([_p, _p, _p, _p, _p, _i, _f, _p, _f, _f, _p, _p], _i),
+    "wvn_mlp_train_phase_a_conf": ([_p, _p, _p, _i, _p, _i, _p, _p, _p, _sz, _p, _p, _p], _i),
+    "wvn_mlp_train_phase_b_conf": ([_p, _p, _p, _i, _p, _p, _i, _p, _p, _f, _f, _f, _p, _p, _p, _sz, _i, _p, _p], _i),
+    "wvn_mlp_train_phase_c_conf": ([_p, _p, _p, _p, _p, _i, _f, _p, _f, _f, _p, _p, _p], _i),
     "wvn_mlp_confidence": ([_p, _i, _p, _i, _f, _f, _f, _p, _p, _i, _i, _p], _i),
     "wvn_pixel_mlp_pack_bytes": ([_p], _sz),
     "wvn_pixel_mlp_zx_cols": ([_p], _i),

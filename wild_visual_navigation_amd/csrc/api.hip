@@ -1031,9 +1031,10 @@ int wvn_compact_segment_rows(const float* feat, int D, const float* side, int Ds
   return wvn_compact_segment_rows_launch(feat, D, side, Dside, nseg, B, S, x_out, side_out, rows_dev, (hipStream_t)stream);
 }
 
-int wvn_mlp_train_phase_a_rows(const wvn_mlp_desc* d, const float* params, const float* x, int ldx,
-                               const unsigned char* y_valid, int R, const int* rows_dev, double* stats, void* workspace,
-                               size_t workspace_bytes, unsigned int* sync_word, void* stream) {
+namespace {
+int mlp_phase_a(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const unsigned char* y_valid, int R,
+                const int* rows_dev, double* stats, void* workspace, size_t workspace_bytes, unsigned int* sync_word, void* stream,
+                const ConfArgs& conf) {
   if (!d || !params || !x || !y_valid || !stats || !workspace || R <= 0) return WVN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   MlpWs w = mlp_carve(d, R, workspace);
@@ -1042,10 +1043,35 @@ int wvn_mlp_train_phase_a_rows(const wvn_mlp_desc* d, const float* params, const
     const MlpOff o = mlp_off(d);
     const size_t off[6] = {o.W1, o.b1, o.W2, o.b2, o.W3, o.b3};
     return wvn_mlp_train_fwd_launch(params, off, o.total, x, ldx, y_valid, R, d->D, rows_dev, w.h1, w.h2, w.out, w.lr, stats, w.fused,
-                                    sync_word, st);
+                                    sync_word, st, conf);
   }
   RET_IF(mlp_fwd(d, params, x, ldx, R, w.out, w.h1, w.h2, st));
-  return wvn_mlp_rowloss_stats_launch(w.out, 1 + d->D, x, ldx, y_valid, w.lr, stats, R, d->D, st, rows_dev);
+  return wvn_mlp_rowloss_stats_launch(w.out, 1 + d->D, x, ldx, y_valid, w.lr, stats, R, d->D, st, rows_dev, conf);
+}
+
+// wvn_conf_desc -> ConfArgs, checked on the host before any GPU call
+int conf_args(const wvn_conf_desc* c, ConfArgs* a) {
+  if (!c || !c->state || c->method < WVN_CONF_LATEST_MEASUREMENT || c->method > WVN_CONF_MOVING_AVERAGE) return WVN_ERR_ARG;
+  if (c->method == WVN_CONF_MOVING_AVERAGE && !c->minmax) return WVN_ERR_ARG;
+  a->method = c->method;
+  a->balanced = c->balanced != 0;
+  a->state = c->state;
+  a->minmax = c->method == WVN_CONF_MOVING_AVERAGE ? c->minmax : nullptr;
+  return WVN_OK;
+}
+}  // namespace
+
+int wvn_mlp_train_phase_a_rows(const wvn_mlp_desc* d, const float* params, const float* x, int ldx,
+                               const unsigned char* y_valid, int R, const int* rows_dev, double* stats, void* workspace,
+                               size_t workspace_bytes, unsigned int* sync_word, void* stream) {
+  return mlp_phase_a(d, params, x, ldx, y_valid, R, rows_dev, stats, workspace, workspace_bytes, sync_word, stream, ConfArgs());
+}
+int wvn_mlp_train_phase_a_conf(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const unsigned char* y_valid,
+                               int R, const int* rows_dev, double* stats, void* workspace, size_t workspace_bytes,
+                               unsigned int* sync_word, const wvn_conf_desc* conf, void* stream) {
+  ConfArgs a;
+  RET_IF(conf_args(conf, &a));
+  return mlp_phase_a(d, params, x, ldx, y_valid, R, rows_dev, stats, workspace, workspace_bytes, sync_word, stream, a);
 }
 int wvn_mlp_train_phase_a(const wvn_mlp_desc* d, const float* params, const float* x, int ldx,
                           const unsigned char* y_valid, int R, double* stats, void* workspace, size_t workspace_bytes,
@@ -1061,10 +1087,10 @@ int wvn_mlp_train_phase_b(const wvn_mlp_desc* d, const float* params, const floa
                                     confidence_out, workspace, workspace_bytes, 0, stream);
 }
 
-int wvn_mlp_train_phase_b_rows(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const float* y,
-                               const unsigned char* y_valid, int R, const int* rows_dev, const double* stats, float std_factor,
-                               float w_trav, float w_reco, float* grads, float* confidence_out, void* workspace,
-                               size_t workspace_bytes, int fused, void* stream) {
+namespace {
+int mlp_phase_b(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const float* y, const unsigned char* y_valid,
+                int R, const int* rows_dev, const double* stats, float std_factor, float w_trav, float w_reco, float* grads,
+                float* confidence_out, void* workspace, size_t workspace_bytes, int fused, void* stream, const ConfArgs& conf) {
   if (!d || !params || !x || !y || !y_valid || !stats || !grads || !workspace || R <= 0) return WVN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   MlpWs w = mlp_carve(d, R, workspace);
@@ -1074,10 +1100,10 @@ int wvn_mlp_train_phase_b_rows(const wvn_mlp_desc* d, const float* params, const
   if (fused && wvn_mlp_train_fused_ok(d->D, d->H1, d->H2, R)) {   // (phase A of this step ran the fused forward on this workspace)
     const size_t off[6] = {o.W1, o.b1, o.W2, o.b2, o.W3, o.b3};
     return wvn_mlp_train_bwd_launch(params, off, o.total, x, ldx, y, y_valid, R, d->D, rows_dev, w.h1, w.h2, w.out, w.lr, w.g_out, w.g_h2,
-                                    w.g_h1, stats, std_factor, w_trav, w_reco, confidence_out, grads, w.fused, st);
+                                    w.g_h1, stats, std_factor, w_trav, w_reco, confidence_out, grads, w.fused, st, conf);
   }
   RET_IF(wvn_mlp_gradout_launch(w.out, O, x, ldx, y, y_valid, w.lr, stats, std_factor, w_trav, w_reco, w.g_out, O,
-                                w.trav_w, w.trav_raw, confidence_out, grads + o.total, R, d->D, st, rows_dev));
+                                w.trav_w, w.trav_raw, confidence_out, grads + o.total, R, d->D, st, rows_dev, conf));
   // layer 3
   RET_IF(mlp_wgrad(w.g_out, O, w.h2, d->H2, O, d->H2, R, w.part, grads + o.W3, st));
   RET_IF(wvn_colsum_launch(w.g_out, O, R, O, grads + o.b3, st));
@@ -1101,6 +1127,24 @@ int wvn_mlp_train_phase_b_rows(const wvn_mlp_desc* d, const float* params, const
   RET_IF(wvn_colsum_launch(w.g_h1, d->H1, R, d->H1, grads + o.b1, st));
   return WVN_OK;
 }
+}  // namespace
+
+int wvn_mlp_train_phase_b_rows(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const float* y,
+                               const unsigned char* y_valid, int R, const int* rows_dev, const double* stats, float std_factor,
+                               float w_trav, float w_reco, float* grads, float* confidence_out, void* workspace,
+                               size_t workspace_bytes, int fused, void* stream) {
+  return mlp_phase_b(d, params, x, ldx, y, y_valid, R, rows_dev, stats, std_factor, w_trav, w_reco, grads, confidence_out, workspace,
+                     workspace_bytes, fused, stream, ConfArgs());
+}
+int wvn_mlp_train_phase_b_conf(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const float* y,
+                               const unsigned char* y_valid, int R, const int* rows_dev, const double* stats, float std_factor,
+                               float w_trav, float w_reco, float* grads, float* confidence_out, void* workspace,
+                               size_t workspace_bytes, int fused, const wvn_conf_desc* conf, void* stream) {
+  ConfArgs a;
+  RET_IF(conf_args(conf, &a));
+  return mlp_phase_b(d, params, x, ldx, y, y_valid, R, rows_dev, stats, std_factor, w_trav, w_reco, grads, confidence_out, workspace,
+                     workspace_bytes, fused, stream, a);
+}
 
 int wvn_mlp_train_phase_c(const wvn_mlp_desc* d, float* params, const float* grads, float* adam_m, float* adam_v,
                           int step, float lr, const double* stats, float w_trav, float w_reco, float* losses,
@@ -1111,6 +1155,16 @@ int wvn_mlp_train_phase_c(const wvn_mlp_desc* d, float* params, const float* gra
   // Adam and the step's losses in ONE launch
   return wvn_adam_launch(params, grads, adam_m, adam_v, (int)o.total, step, lr, 0.9f, 0.999f, 1e-8f, st, stats, grads + o.total, w_trav,
                          w_reco, losses);
+}
+int wvn_mlp_train_phase_c_conf(const wvn_mlp_desc* d, float* params, const float* grads, float* adam_m, float* adam_v, int step,
+                               float lr, const double* stats, float w_trav, float w_reco, float* losses, const wvn_conf_desc* conf,
+                               void* stream) {
+  ConfArgs a;
+  RET_IF(conf_args(conf, &a));
+  if (!d || !params || !grads || !adam_m || !adam_v || !stats || !losses || step <= 0) return WVN_ERR_ARG;   // (losses: the commit rides on it)
+  const MlpOff o = mlp_off(d);
+  return wvn_adam_launch(params, grads, adam_m, adam_v, (int)o.total, step, lr, 0.9f, 0.999f, 1e-8f, (hipStream_t)stream, stats,
+                         grads + o.total, w_trav, w_reco, losses, a);
 }
 
 // fused per-pixel inference (pixel_mlp.hip)

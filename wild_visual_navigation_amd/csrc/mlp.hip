@@ -35,8 +35,10 @@ __global__ __launch_bounds__(256) void mlp_rowloss_kernel(const float* __restric
 // stats = { n_valid, sum(lr[valid]), sum(lr[valid]^2), R }  in fp64, single workgroup, fixed order
 __global__ __launch_bounds__(1024) void mlp_stats_kernel(const float* __restrict__ lr,
                                                          const unsigned char* __restrict__ valid, int R,
-                                                         double* __restrict__ stats, const int* __restrict__ rows_dev) {
+                                                         double* __restrict__ stats, const int* __restrict__ rows_dev,
+                                                         float* __restrict__ minmax) {
   __shared__ double sh[3][16];
+  __shared__ float shm[2][16];
   if (rows_dev) R = min(R, *rows_dev);
   double n = 0, s1 = 0, s2 = 0;
   for (int r = threadIdx.x; r < R; r += 1024)
@@ -44,11 +46,23 @@ __global__ __launch_bounds__(1024) void mlp_stats_kernel(const float* __restrict
   n = wave_sum_d(n); s1 = wave_sum_d(s1); s2 = wave_sum_d(s2);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { sh[0][w] = n; sh[1][w] = s1; sh[2][w] = s2; }
+  if (minmax) {   // {max, -min} of lr over all real rows (moving_average; order-free)
+    float mn = INFINITY, mx = -INFINITY;
+    for (int r = threadIdx.x; r < R; r += 1024) { mn = fminf(mn, lr[r]); mx = fmaxf(mx, lr[r]); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
+    if ((threadIdx.x & 63) == 0) { shm[0][w] = mn; shm[1][w] = mx; }
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     double a = 0, b = 0, c = 0;
     for (int i = 0; i < 16; ++i) { a += sh[0][i]; b += sh[1][i]; c += sh[2][i]; }
     stats[0] = a; stats[1] = b; stats[2] = c; stats[3] = (double)R;
+    if (minmax) {
+      float mn = INFINITY, mx = -INFINITY;
+      for (int i = 0; i < 16; ++i) { mn = fminf(mn, shm[0][i]); mx = fmaxf(mx, shm[1][i]); }
+      minmax[0] = mx; minmax[1] = -mn;
+    }
   }
 }
 
@@ -62,7 +76,8 @@ __global__ __launch_bounds__(256) void mlp_gradout_kernel(const float* __restric
                                                           float w_trav, float w_reco, float* __restrict__ g, int ldg,
                                                           float* __restrict__ trav_w, float* __restrict__ trav_raw,
                                                           float* __restrict__ conf_out, int R, int D,
-                                                          const int* __restrict__ rows_dev) {
+                                                          const int* __restrict__ rows_dev, int method, int balanced,
+                                                          const double* __restrict__ cstate, const float* __restrict__ minmax) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= R) return;
@@ -74,11 +89,18 @@ __global__ __launch_bounds__(256) void mlp_gradout_kernel(const float* __restric
   const ConfStats cs = conf_stats(stats);
   const float Rtot = (float)stats[3], nv = (float)stats[0];
   const bool v = valid[row] != 0;
-  const float conf = confidence_of(lr[row], cs.mean, cs.std, std_factor);
+  float conf;
+  if (cstate) {   // another method: the post-update statistic from the state and this step's (global) stats
+    const ConfPost cp = conf_post(method, stats, cstate);
+    const float xmax = minmax ? minmax[0] : 0.f, xmin = minmax ? -minmax[1] : 0.f;
+    conf = conf_method(method, lr[row], cp, std_factor, xmin, xmax);
+  } else {
+    conf = confidence_of(lr[row], cs.mean, cs.std, std_factor);
+  }
   const float s = out[(size_t)row * ldo];
   const float diff = s - y[row];
   const float raw = diff * diff;
-  const float wrow = v ? 1.f : (1.f - conf);
+  const float wrow = (v || !balanced) ? 1.f : (1.f - conf);   // anomaly_balanced = False: the plain mean of the raw trav loss
   if (lane == 0) {
     trav_raw[row] = raw;
     trav_w[row] = raw * wrow;
@@ -136,8 +158,12 @@ __global__ __launch_bounds__(1024) void colsum_kernel(const float* __restrict__ 
 
 // torch.optim.Adam single-tensor update (no amsgrad / weight decay / maximize)
 __device__ inline void write_losses(const double* __restrict__ stats, const float* __restrict__ extra, float w_trav, float w_reco,
-                                    float* __restrict__ losses) {
-  const ConfStats cs = conf_stats(stats);
+                                    float* __restrict__ losses, int method = 0, double* __restrict__ cstate = nullptr) {
+  ConfStats cs = conf_stats(stats);
+  if (cstate) {   // another method: commit its post-update statistic to the persistent state
+    const ConfPost cp = conf_commit(method, stats, cstate);
+    cs.mean = cp.mean; cs.std = cp.std;
+  }
   const float Rtot = (float)stats[3];
   const float reco = (float)(stats[1] / stats[0]);
   const float trav_conf = extra[0] / Rtot;
@@ -151,9 +177,9 @@ __device__ inline void write_losses(const double* __restrict__ stats, const floa
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, int n, float lr, float b1, float b2, float eps, float bc1,
                             float bc2_sqrt, const double* __restrict__ stats, const float* __restrict__ extra, float w_trav,
-                            float w_reco, float* __restrict__ losses) {
+                            float w_reco, float* __restrict__ losses, int method, double* __restrict__ cstate) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (losses && i == 0) write_losses(stats, extra, w_trav, w_reco, losses);   // (the step's losses ride along: one launch fewer)
+  if (losses && i == 0) write_losses(stats, extra, w_trav, w_reco, losses, method, cstate);   // (the step's losses ride along: one launch fewer)
   if (i >= n) return;
   const float gi = g[i];
   const float mi = m[i] * b1 + (1.f - b1) * gi;
@@ -229,10 +255,10 @@ int wvn_compact_segment_rows_launch(const float* feat, int D, const float* side,
 }
 
 int wvn_mlp_rowloss_stats_launch(const float* out, int ldo, const float* x, int ldx, const unsigned char* valid,
-                                 float* lr, double* stats, int R, int D, hipStream_t st, const int* rows_dev) {
+                                 float* lr, double* stats, int R, int D, hipStream_t st, const int* rows_dev, const ConfArgs& conf) {
   hipLaunchKernelGGL(mlp_rowloss_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, st, out, ldo, x, ldx, lr, R, D, rows_dev);
   WVN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mlp_stats_kernel, dim3(1), dim3(1024), 0, st, lr, valid, R, stats, rows_dev);
+  hipLaunchKernelGGL(mlp_stats_kernel, dim3(1), dim3(1024), 0, st, lr, valid, R, stats, rows_dev, conf.minmax);
   WVN_LAUNCH_CHECK();
   return WVN_OK;
 }
@@ -240,9 +266,10 @@ int wvn_mlp_rowloss_stats_launch(const float* out, int ldo, const float* x, int 
 int wvn_mlp_gradout_launch(const float* out, int ldo, const float* x, int ldx, const float* y,
                            const unsigned char* valid, const float* lr, const double* stats, float std_factor,
                            float w_trav, float w_reco, float* g, int ldg, float* trav_w, float* trav_raw,
-                           float* conf_out, float* extra, int R, int D, hipStream_t st, const int* rows_dev) {
+                           float* conf_out, float* extra, int R, int D, hipStream_t st, const int* rows_dev, const ConfArgs& conf) {
   hipLaunchKernelGGL(mlp_gradout_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, st, out, ldo, x, ldx, y, valid, lr, stats,
-                     std_factor, w_trav, w_reco, g, ldg, trav_w, trav_raw, conf_out, R, D, rows_dev);
+                     std_factor, w_trav, w_reco, g, ldg, trav_w, trav_raw, conf_out, R, D, rows_dev, conf.method, conf.balanced,
+                     (const double*)conf.state, (const float*)conf.minmax);
   WVN_LAUNCH_CHECK();
   hipLaunchKernelGGL(mlp_losssum_kernel, dim3(1), dim3(1024), 0, st, trav_w, trav_raw, R, extra);
   WVN_LAUNCH_CHECK();
@@ -256,11 +283,12 @@ int wvn_colsum_launch(const float* A, int lda, int R, int N, float* outv, hipStr
 }
 
 int wvn_adam_launch(float* p, const float* g, float* m, float* v, int n, int step, float lr, float b1, float b2,
-                    float eps, hipStream_t st, const double* stats, const float* extra, float w_trav, float w_reco, float* losses) {
+                    float eps, hipStream_t st, const double* stats, const float* extra, float w_trav, float w_reco, float* losses,
+                    const ConfArgs& conf) {
   const float bc1 = (float)(1.0 - pow((double)b1, (double)step));
   const float bc2s = (float)sqrt(1.0 - pow((double)b2, (double)step));
   hipLaunchKernelGGL(adam_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, bc1, bc2s, stats, extra,
-                     w_trav, w_reco, losses);
+                     w_trav, w_reco, losses, conf.method, conf.state);
   WVN_LAUNCH_CHECK();
   return WVN_OK;
 }

@@ -1,8 +1,9 @@
 // Device helpers shared by the traversability-MLP training kernels (mlp.hip: one kernel per stage; mlp_train.hip: the
-// four-launch step): the confidence statistic and the confidence of a reconstruction loss.
-// Reference: wild_visual_navigation/utils/confidence_generator.py:78-82, 182-193.
+// four-launch step): the confidence statistic and the confidence of a reconstruction loss, for the four ConfidenceGenerator
+// methods.  Reference: wild_visual_navigation/utils/confidence_generator.py, kalman_filter.py.
 #pragma once
 #include "common.h"
+#include "../../include/wvn_hip.h"
 
 struct ConfStats { float mean, std; };
 __device__ inline ConfStats conf_stats(const double* st) {
@@ -25,3 +26,83 @@ __device__ inline float confidence_of(float x, float mean, float std, float f) {
   return 1.f - (xc - lo) / (hi - lo);
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The other ConfidenceGenerator methods (confidence_generator.py:87-151).  Their statistic has a memory: the persistent device
+// state cs[WVN_CONF_STATE_DOUBLES] (layout in include/wvn_hip.h) plus this step's global stats {n_lab, sum, sum^2, R}.  Phase B
+// evaluates the post-update statistic from (cs, stats) in every workgroup; phase C evaluates it once more and commits it.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct ConfPost { float mean, var, std; };
+
+// the ring head / fill count read from the state, clamped to [0, hi] (NaN -> 0): a corrupted state cannot address past the ring
+__device__ inline int state_int(double v, int hi) { return v >= 1.0 ? (v < hi ? (int)v : hi) : 0; }
+
+__device__ inline ConfPost conf_post(int method, const double* st, const double* cs) {
+  ConfPost c;
+  c.var = (float)cs[WVN_CONF_S_VAR];
+  if (method == WVN_CONF_RUNNING_MEAN) {          // update_running_mean: fp64 running sums, fp32 mean, population variance
+    const double n = cs[WVN_CONF_S_RUN_N] + st[0], s = cs[WVN_CONF_S_RUN_SUM] + st[1], s2 = cs[WVN_CONF_S_RUN_SUMSQ] + st[2];
+    c.mean = (float)(s / n);
+    const float m2 = c.mean * c.mean;              // self.mean ** 2 in fp32, promoted against the fp64 sum
+    c.var = (float)(s2 / n - (double)m2);
+    c.std = sqrtf(c.var);
+  } else if (method == WVN_CONF_KALMAN_FILTER) {  // update_kalman_filter: scalar KF, process noise 0.2, measurement noise 1
+    float m = (float)cs[WVN_CONF_S_MEAN], v = c.var;
+    if (st[0] > 0.0) {                             // a step without positives leaves the filter where it is
+      const float z = (float)(st[1] / st[0]);
+      const float vp = v + 0.2f;
+      const float k = vp * (1.f / (vp + 1.f));
+      m = m + k * (z - m);
+      v = (1.f - k) * vp;
+    }
+    c.mean = m; c.var = v; c.std = sqrtf(v);
+  } else if (method == WVN_CONF_MOVING_AVERAGE) {  // update_moving_average: the positives of the last 5 steps (this one included)
+    const int head = state_int(cs[WVN_CONF_S_HEAD], WVN_CONF_WINDOW - 1), fill = state_int(cs[WVN_CONF_S_FILL], WVN_CONF_WINDOW);
+    const int keep = fill < WVN_CONF_WINDOW - 1 ? fill : WVN_CONF_WINDOW - 1;
+    double n = 0, s = 0, s2 = 0;
+    for (int i = keep; i >= 1; --i) {              // oldest first, then this step
+      const double* e = cs + WVN_CONF_S_RING + 3 * ((head - i + WVN_CONF_WINDOW) % WVN_CONF_WINDOW);
+      n += e[0]; s += e[1]; s2 += e[2];
+    }
+    n += st[0]; s += st[1]; s2 += st[2];
+    const double sn[3] = {n, s, s2};
+    const ConfStats cw = conf_stats(sn);
+    c.mean = cw.mean; c.std = cw.std;
+  } else {                                         // latest_measurement: this step's positives (var untouched)
+    const ConfStats cl = conf_stats(st);
+    c.mean = cl.mean; c.std = cl.std;
+  }
+  return c;
+}
+
+// phase C: commit the post-update statistic (one thread)
+__device__ inline ConfPost conf_commit(int method, const double* st, double* cs) {
+  const ConfPost c = conf_post(method, st, cs);
+  if (method == WVN_CONF_RUNNING_MEAN) {
+    cs[WVN_CONF_S_RUN_N] += st[0]; cs[WVN_CONF_S_RUN_SUM] += st[1]; cs[WVN_CONF_S_RUN_SUMSQ] += st[2];
+  } else if (method == WVN_CONF_MOVING_AVERAGE) {
+    const int head = state_int(cs[WVN_CONF_S_HEAD], WVN_CONF_WINDOW - 1), fill = state_int(cs[WVN_CONF_S_FILL], WVN_CONF_WINDOW);
+    double* e = cs + WVN_CONF_S_RING + 3 * head;
+    e[0] = st[0]; e[1] = st[1]; e[2] = st[2];
+    cs[WVN_CONF_S_HEAD] = (double)((head + 1) % WVN_CONF_WINDOW);
+    cs[WVN_CONF_S_FILL] = (double)(fill < WVN_CONF_WINDOW ? fill + 1 : WVN_CONF_WINDOW);
+  }
+  cs[WVN_CONF_S_MEAN] = c.mean; cs[WVN_CONF_S_VAR] = c.var; cs[WVN_CONF_S_STD] = c.std;
+  return c;
+}
+
+// the training-row confidence returned by update(); xmin / xmax: min / max of loss_reco over all rows of the step (moving_average)
+__device__ inline float conf_method(int method, float x, const ConfPost& c, float f, float xmin, float xmax) {
+  if (method == WVN_CONF_KALMAN_FILTER) {
+    if (x < c.mean) return 1.f;
+    const float d = (x - c.mean) / (c.std * f);
+    return expf(-(d * d) * 0.5f);
+  }
+  if (method == WVN_CONF_MOVING_AVERAGE) {   // clip to mean +- 2 std, then min-max scale over the step (clip is monotone)
+    const float lo = c.mean - 2.f * c.std, hi = c.mean + 2.f * c.std;
+    if (isnan(lo) || isnan(hi)) return NAN;  // torch.clip with a NaN bound
+    const float xc = fminf(fmaxf(x, lo), hi), a = fminf(fmaxf(xmin, lo), hi), b = fminf(fmaxf(xmax, lo), hi);
+    return (xc - a) / (b - a);
+  }
+  return confidence_of(x, c.mean, c.std, f);
+}

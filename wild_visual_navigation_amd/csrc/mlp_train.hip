@@ -39,6 +39,11 @@ struct TrainParams {
   float std_factor, w_trav, w_reco;
   float* conf_out;                // optional [R]
   float* grads;                   // [ntotal + 2]
+  // ConfidenceGenerator method (mlp_device.h); cstate == nullptr: latest_measurement, no state (the original step)
+  int method, balanced;
+  const double* cstate;           // [WVN_CONF_STATE_DOUBLES] read by bwd
+  float* minmax;                  // [2] {max, -min} of lr over the real rows: written by fwd, read by bwd (nullptr: not formed)
+  float* part_mm;                 // [ntiles][2] per-tile {min, max} of lr (fwd)
 };
 
 __device__ inline int real_rows(const TrainParams& p) { return p.rows_dev ? min(p.R, *p.rows_dev) : p.R; }
@@ -164,9 +169,16 @@ __global__ __launch_bounds__(256) void mlp_train_fwd_kernel(TrainParams p) {
     const bool v = row0 + tid < Rr && p.valid[row0 + tid] != 0;
     const double l = v ? (double)h2s[tid] : 0.0;
     const double n = sum32_d(v ? 1.0 : 0.0), s1 = sum32_d(l), s2 = sum32_d(l * l);
+    float mn = INFINITY, mx = -INFINITY;
+    if (p.minmax) {   // min / max of lr over the tile's real rows (moving_average; min and max are order-free)
+      if (row0 + tid < Rr) mn = mx = h2s[tid];
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
+    }
     if (tid == 0) {
       double* d = p.part + (size_t)blockIdx.x * 4;
       d[0] = n; d[1] = s1; d[2] = s2;
+      if (p.minmax) { p.part_mm[(size_t)blockIdx.x * 2] = mn; p.part_mm[(size_t)blockIdx.x * 2 + 1] = mx; }
       // publish: the partial must be visible device-wide before the ticket (MI355X_MICROARCH.md, producer form)
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -186,6 +198,14 @@ __global__ __launch_bounds__(256) void mlp_train_fwd_kernel(TrainParams p) {
         c += __hip_atomic_load(d + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       p.stats[0] = a; p.stats[1] = b; p.stats[2] = c; p.stats[3] = (double)Rr;
+      if (p.minmax) {
+        float mn = INFINITY, mx = -INFINITY;
+        for (unsigned i = 0; i < gridDim.x; ++i) {
+          mn = fminf(mn, __hip_atomic_load(p.part_mm + (size_t)i * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+          mx = fmaxf(mx, __hip_atomic_load(p.part_mm + (size_t)i * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        }
+        p.minmax[0] = mx; p.minmax[1] = -mn;
+      }
       __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next step
     }
   }
@@ -204,6 +224,12 @@ __global__ __launch_bounds__(256) void mlp_train_bwd_kernel(TrainParams p) {
   const int Rr = real_rows(p);
   const ConfStats cs = conf_stats(p.stats);
   const float Rtot = (float)p.stats[3], nv = (float)p.stats[0];
+  ConfPost cp{};
+  float xmin = 0.f, xmax = 0.f;
+  if (p.cstate) {   // another method: the post-update statistic from the state and this step's (global) stats
+    cp = conf_post(p.method, p.stats, p.cstate);
+    if (p.minmax) { xmax = p.minmax[0]; xmin = -p.minmax[1]; }
+  }
   // ---- gradient seed (loss.py:125-147): 8 threads per row ----
   {
     const int r = tid >> 3, q = tid & 7, row = row0 + r;
@@ -211,10 +237,11 @@ __global__ __launch_bounds__(256) void mlp_train_bwd_kernel(TrainParams p) {
     const bool v = real && p.valid[row] != 0;
     float diff = 0.f, s = 0.f, wrow = 0.f, conf = 0.f;
     if (real) {
-      conf = confidence_of(p.lr[row], cs.mean, cs.std, p.std_factor);
+      conf = p.cstate ? conf_method(p.method, p.lr[row], cp, p.std_factor, xmin, xmax)
+                      : confidence_of(p.lr[row], cs.mean, cs.std, p.std_factor);
       s = p.out[(size_t)row * O];
       diff = s - p.y[row];
-      wrow = v ? 1.f : (1.f - conf);
+      wrow = (v || !p.balanced) ? 1.f : (1.f - conf);   // anomaly_balanced = False: the plain mean of the raw trav loss
     }
     if (q == 0) {
       const float raw = diff * diff;
@@ -340,7 +367,7 @@ bool wvn_mlp_train_fused_ok(int D, int H1_, int H2_, int R) {
   // gradients lose from about 3000 rows on (792 vs 504 us at 6400), where the general path's split-K GEMMs take over
   return H1_ == H1 && H2_ == H2 && D > 0 && fwd_lds(D) <= FUSED_LDS_MAX && R > 0 && R <= 2048;   // D <= 460
 }
-size_t wvn_mlp_train_fused_scratch_bytes(int R) { return (size_t)ceil_div(R, TR) * 4 * sizeof(double); }
+size_t wvn_mlp_train_fused_scratch_bytes(int R) { return (size_t)ceil_div(R, TR) * (4 * sizeof(double) + 2 * sizeof(float)); }
 
 static TrainParams make_params(const float* P, const size_t* off, size_t ntotal, const float* x, int ldx, int R, int D, const int* rows_dev,
                                float* h1, float* h2, float* out, float* lr, void* scratch, unsigned* sync_word) {
@@ -349,15 +376,17 @@ static TrainParams make_params(const float* P, const size_t* off, size_t ntotal,
   p.x = x; p.ldx = ldx; p.R = R; p.D = D; p.rows_dev = rows_dev;
   p.h1 = h1; p.h2 = h2; p.out = out; p.lr = lr;
   p.part = (double*)scratch;
+  p.part_mm = (float*)(p.part + (size_t)ceil_div(R, TR) * 4);
   p.ticket = sync_word;
+  p.balanced = 1;
   return p;
 }
 
 int wvn_mlp_train_fwd_launch(const float* P, const size_t* off, size_t ntotal, const float* x, int ldx, const unsigned char* valid, int R,
                              int D, const int* rows_dev, float* h1, float* h2, float* out, float* lr, double* stats, void* scratch,
-                             unsigned* sync_word, hipStream_t st) {
+                             unsigned* sync_word, hipStream_t st, const ConfArgs& conf) {
   TrainParams p = make_params(P, off, ntotal, x, ldx, R, D, rows_dev, h1, h2, out, lr, scratch, sync_word);
-  p.valid = valid; p.stats = stats;
+  p.valid = valid; p.stats = stats; p.minmax = conf.minmax;
   if (fwd_lds(D) > FUSED_LDS_MAX) return WVN_ERR_ARG;
   static LdsOptIn lds_opt_in;   // (the kernels also hold a few bytes of static LDS: the dynamic limit must stay below 160 KB)
   if (const int rc = lds_opt_in((int)FUSED_LDS_MAX, (const void*)mlp_train_fwd_kernel, (const void*)mlp_train_bwd_kernel)) return rc;
@@ -372,8 +401,9 @@ int wvn_mlp_train_fwd_launch(const float* P, const size_t* off, size_t ntotal, c
 int wvn_mlp_train_bwd_launch(const float* P, const size_t* off, size_t ntotal, const float* x, int ldx, const float* y,
                              const unsigned char* valid, int R, int D, const int* rows_dev, float* h1, float* h2, float* out, float* lr,
                              float* g_out, float* g_h2, float* g_h1, const double* stats, float std_factor, float w_trav, float w_reco,
-                             float* conf_out, float* grads, void* scratch, hipStream_t st) {
+                             float* conf_out, float* grads, void* scratch, hipStream_t st, const ConfArgs& conf) {
   TrainParams p = make_params(P, off, ntotal, x, ldx, R, D, rows_dev, h1, h2, out, lr, scratch, nullptr);
+  p.method = conf.method; p.balanced = conf.balanced; p.cstate = conf.state; p.minmax = conf.minmax;
   p.y = y; p.valid = valid; p.stats = (double*)stats; p.g_out = g_out; p.g_h2 = g_h2; p.g_h1 = g_h1;
   p.std_factor = std_factor; p.w_trav = w_trav; p.w_reco = w_reco; p.conf_out = conf_out; p.grads = grads;
   static LdsOptIn lds_opt_in;

@@ -76,6 +76,13 @@ def allreduce_sum_(t: torch.Tensor, group=None) -> torch.Tensor:
     return t
 
 
+def allreduce_max_(t: torch.Tensor, group=None) -> torch.Tensor:
+    """In-place MAX over ranks (no-op for a single process); exact, so every rank receives the same bits."""
+    if is_parallel():
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    return t
+
+
 def all_ranks_ready(ready: bool, device=None) -> bool:
     """MIN over ranks of a local flag (True for a single process): the collective decision whether a step that contains
     collectives runs at all."""

@@ -10,6 +10,11 @@ exchanges that make it data-parallel:
 Local contributions are sums (not means) scaled by the global normalisers inside phase B, so the
 N-GPU trajectory equals the 1-GPU trajectory on the concatenated batch up to fp32 summation order.
 Reference arithmetic: traversability_estimator.py:464-477, loss.py:93-160, torch.optim.Adam.
+
+ConfidenceGenerator methods other than latest_measurement, and anomaly_balanced=False, run through the *_conf entry points of
+the same phases: the statistic's memory is a small persistent device state (``conf_state``, include/wvn_hip.h) that phase B
+reads and phase C commits on every rank alike.  moving_average adds one collective between phases A and B: a MAX over the
+ranks of {max, -min} of the reconstruction loss (two floats).
 """
 import ctypes as C
 from typing import Dict, Optional
@@ -17,7 +22,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import _lib
-from ..distributed import allreduce_sum_
+from ..distributed import allreduce_max_, allreduce_sum_
 from ..model.simple_mlp import SimpleMLP
 
 
@@ -25,8 +30,14 @@ from ..model.simple_mlp import SimpleMLP
 
 class MlpTrainer:
     def __init__(self, model: SimpleMLP, lr: float = 1e-3, std_factor: float = 0.5, w_trav: float = 0.03,
-                 w_reco: float = 0.5, process_group=None, fused: bool = True):
+                 w_reco: float = 0.5, process_group=None, fused: bool = True, method: str = "latest_measurement",
+                 anomaly_balanced: bool = True):
+        if method not in _lib.CONF_METHODS:
+            raise ValueError(f"Unknown ConfidenceGenerator method {method!r} (one of {', '.join(_lib.CONF_METHODS)})")
         self.model = model
+        self.method, self.anomaly_balanced = method, bool(anomaly_balanced)
+        # the *_conf entry points (device state) for anything but the original configuration, which keeps its entry points
+        self._conf = method != "latest_measurement" or not self.anomaly_balanced
         self.lr, self.std_factor, self.w_trav, self.w_reco = lr, std_factor, w_trav, w_reco
         self.group = process_group
         self.step = 0
@@ -46,10 +57,56 @@ class MlpTrainer:
             else:
                 self.m = torch.zeros(n, dtype=torch.float32, device=dev)
                 self.v = torch.zeros(n, dtype=torch.float32, device=dev)
+            if self._state_dev is not None:   # (the confidence statistic's memory moves too)
+                self.conf_state = self.conf_state.to(dev)
+            else:
+                self.conf_state = self._initial_conf_state(dev)
+            self.minmax = torch.zeros(2, dtype=torch.float32, device=dev)
             self.stats = torch.zeros(4, dtype=torch.float64, device=dev)
             self.losses = torch.zeros(5, dtype=torch.float32, device=dev)
             self.sync_word = torch.zeros(1, dtype=torch.int32, device=dev)   # arrival counter of the fused forward (zero between steps)
             self._state_dev = dev
+
+    @staticmethod
+    def _initial_conf_state(dev) -> torch.Tensor:
+        st = torch.zeros(_lib.CONF_STATE_DOUBLES, dtype=torch.float64, device=dev)
+        st[_lib.CONF_S_VAR] = 1.0
+        st[_lib.CONF_S_STD] = 1.0
+        return st
+
+    @torch.no_grad()
+    def load_confidence_state(self, cg) -> None:
+        """Make the device state equal to a ConfidenceGenerator's (after construction, a load, a reset or a host-side update):
+        mean / var / std, the running_mean sums, the moving_average window as per-step sums.  Device copies only."""
+        self._state(self.model.flat_params().device)
+        st = self.conf_state
+        st.zero_()
+        st[_lib.CONF_S_MEAN:_lib.CONF_S_MEAN + 1].copy_(cg.mean.detach().reshape(-1))
+        st[_lib.CONF_S_VAR:_lib.CONF_S_VAR + 1].copy_(cg.var.detach().reshape(-1))
+        st[_lib.CONF_S_STD:_lib.CONF_S_STD + 1].copy_(cg.std.detach().reshape(-1))
+        if cg.method == "running_mean":
+            for i, name in enumerate(("running_n", "running_sum", "running_sum_of_squares")):
+                st[_lib.CONF_S_RUN_N + i:_lib.CONF_S_RUN_N + i + 1].copy_(getattr(cg, name).detach().reshape(-1))
+        win = cg.window_sums()[-_lib.CONF_WINDOW:]
+        for i, (n, s1, s2) in enumerate(win):
+            e = _lib.CONF_S_RING + 3 * i
+            st[e] = float(n)
+            st[e + 1].copy_(s1)
+            st[e + 2].copy_(s2)
+        st[_lib.CONF_S_HEAD] = float(len(win) % _lib.CONF_WINDOW)
+        st[_lib.CONF_S_FILL] = float(len(win))
+
+    @torch.no_grad()
+    def store_confidence_state(self, cg) -> None:
+        """The device state into a ConfidenceGenerator's parameters (device copies, no host synchronisation)."""
+        st = self.conf_state
+        cg.mean.copy_(st[_lib.CONF_S_MEAN:_lib.CONF_S_MEAN + 1])
+        cg.var.view(-1).copy_(st[_lib.CONF_S_VAR:_lib.CONF_S_VAR + 1])
+        cg.std.copy_(st[_lib.CONF_S_STD:_lib.CONF_S_STD + 1])
+        if cg.method == "running_mean":
+            cg.running_n.copy_(st[_lib.CONF_S_RUN_N:_lib.CONF_S_RUN_N + 1])
+            cg.running_sum.copy_(st[_lib.CONF_S_RUN_SUM:_lib.CONF_S_RUN_SUM + 1])
+            cg.running_sum_of_squares.copy_(st[_lib.CONF_S_RUN_SUMSQ:_lib.CONF_S_RUN_SUMSQ + 1])
 
     # Adam moments in torch.optim.Adam.state_dict() shape, for save/load_checkpoint compatibility
     def optimizer_state_dict(self) -> Dict:
@@ -120,6 +177,8 @@ class MlpTrainer:
         # A rank whose shard is empty this step (ragged frame sharding) still takes part in both collectives, contributing
         # zeros: every rank makes the same sequence of RCCL calls whatever its row count.
         rd = _lib.ptr(rows_dev)
+        if self._conf:
+            return self._train_step_conf(x, y, yv, R, rd, conf)
         if R > 0:
             _lib.check(lib.wvn_mlp_train_phase_a_rows(C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), yv.data_ptr(), R, rd,
                                                       self.stats.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -139,5 +198,37 @@ class MlpTrainer:
         _lib.check(lib.wvn_mlp_train_phase_c(C.byref(d), flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
                                              self.v.data_ptr(), self.step, self.lr, self.stats.data_ptr(), self.w_trav,
                                              self.w_reco, self.losses.data_ptr(), st), "phase_c")
+        self.last_confidence = conf
+        return self.losses
+
+    def _train_step_conf(self, x, y, yv, R, rd, conf):
+        lib, d, flat, st = _lib.lib(), self.model.desc, self.model.flat_params(), _lib.stream()
+        ws = self.model._workspace(max(R, 1))
+        moving = self.method == "moving_average"
+        cd = _lib.ConfDesc(_lib.CONF_METHODS[self.method], int(self.anomaly_balanced), self.conf_state.data_ptr(),
+                           self.minmax.data_ptr())
+        if R > 0:
+            _lib.check(lib.wvn_mlp_train_phase_a_conf(C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), yv.data_ptr(), R, rd,
+                                                      self.stats.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      self.sync_word.data_ptr() if self.fused else 0, C.byref(cd), st), "phase_a")
+        else:
+            self.stats.zero_()
+            if moving:
+                self.minmax.fill_(-float("inf"))
+        self._timed_allreduce(self.stats)
+        if moving:   # min / max of the reconstruction loss over ALL ranks' rows (the same collective on every rank)
+            allreduce_max_(self.minmax, self.group)
+        if R > 0:
+            _lib.check(lib.wvn_mlp_train_phase_b_conf(C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), y.data_ptr(),
+                                                      yv.data_ptr(), R, rd, self.stats.data_ptr(), self.std_factor, self.w_trav,
+                                                      self.w_reco, self.grads.data_ptr(), _lib.ptr(conf), ws.data_ptr(),
+                                                      ws.numel(), int(self.fused), C.byref(cd), st), "phase_b")
+        else:
+            self.grads.zero_()
+        self._timed_allreduce(self.grads)
+        self.step += 1
+        _lib.check(lib.wvn_mlp_train_phase_c_conf(C.byref(d), flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
+                                                  self.v.data_ptr(), self.step, self.lr, self.stats.data_ptr(), self.w_trav,
+                                                  self.w_reco, self.losses.data_ptr(), C.byref(cd), st), "phase_c")
         self.last_confidence = conf
         return self.losses

@@ -66,7 +66,9 @@ class TraversabilityEstimator:
             log_folder=_get(gen, "model_path") or "/tmp").to(self._device)
         self._optimizer = MlpTrainer(self._model, lr=_get(_get(params, "optimizer"), "lr"),
                                      std_factor=_get(loss_cfg, "confidence_std_factor"),
-                                     w_trav=_get(loss_cfg, "w_trav"), w_reco=_get(loss_cfg, "w_reco"))
+                                     w_trav=_get(loss_cfg, "w_trav"), w_reco=_get(loss_cfg, "w_reco"),
+                                     method=_get(loss_cfg, "method"), anomaly_balanced=_get(loss_cfg, "anomaly_balanced"))
+        self._cg_version = None   # the ConfidenceGenerator state version the trainer's device state was last loaded from
         self._loss = torch.tensor([torch.inf])
         self._step = 0
 
@@ -236,11 +238,18 @@ class TraversabilityEstimator:
     def train_on_batch(self, x: torch.Tensor, y: torch.Tensor, y_valid: torch.Tensor) -> torch.Tensor:
         """Fused forward + loss + backward + Adam on this rank's rows; updates the confidence statistic.
         Returns the device tensor {total, trav, reco, conf_mean, conf_std} without synchronising."""
-        losses = self._optimizer.train_step(x.to(self._device), y.to(self._device), y_valid.to(self._device))
         cg = self._traversability_loss._confidence_generator
+        tr = self._optimizer
+        if tr._conf and self._cg_version != cg._version:   # constructed, loaded, reset or updated on the host since the last step
+            tr.load_confidence_state(cg)
+            self._cg_version = cg._version
+        losses = tr.train_step(x.to(self._device), y.to(self._device), y_valid.to(self._device))
         with torch.no_grad():
-            cg.mean.copy_(losses[3:4])
-            cg.std.copy_(losses[4:5])
+            if tr._conf:   # mean / var / std (and the running sums) of the step's method
+                tr.store_confidence_state(cg)
+            else:
+                cg.mean.copy_(losses[3:4])
+                cg.std.copy_(losses[4:5])
         self._loss = losses[0:1]
         return losses
 

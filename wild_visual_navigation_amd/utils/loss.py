@@ -19,8 +19,11 @@ class TraversabilityLoss(torch.nn.Module):
                  method: str, confidence_std_factor: float, log_enabled: bool = False, log_folder: str = "/tmp",
                  trav_cross_entropy=False):
         super().__init__()
-        if trav_cross_entropy or not anomaly_balanced:
-            raise ValueError("the MI355X path implements the default loss (MSE, anomaly_balanced=True)")
+        if trav_cross_entropy:
+            # the reference's cross-entropy branch indexes res[:, :-D].squeeze()[:, 0]: with SimpleMLP's single traversability
+            # column that is a 1-D tensor and the indexing raises (loss.py:133-138), so the configuration never ran upstream
+            raise ValueError("trav_cross_entropy=True is not supported: the reference's cross-entropy loss indexes "
+                             "res[:, :-D].squeeze()[:, 0], which fails for SimpleMLP's single traversability output")
         self._w_trav, self._w_reco, self._w_temp = w_trav, w_reco, w_temp
         self._anomaly_balanced = anomaly_balanced
         self.__dict__["_model"] = model  # not registered as a sub-module (mirrors usage, avoids state-dict dup)
@@ -28,7 +31,8 @@ class TraversabilityLoss(torch.nn.Module):
                                                          log_enabled=log_enabled, log_folder=log_folder)
 
     def reset(self):
-        self._confidence_generator.reset()
+        if self._anomaly_balanced:   # (loss.py:88-90: a no-op for anomaly_balanced=False)
+            self._confidence_generator.reset()
 
     # The reference registers the model as a sub-module of the loss (loss.py:75), so its ``traversability_loss_state_dict``
     # carries ``_model.layers.*`` next to ``_confidence_generator.*``.  Here the model is not a sub-module (one owner for the
@@ -56,8 +60,11 @@ class TraversabilityLoss(torch.nn.Module):
             else:
                 confidence = self._confidence_generator.inference_without_update(x=loss_reco)
         loss_trav_raw = F.mse_loss(res[:, :-D].squeeze(), graph.y[:], reduction="none")
-        weighted = torch.where(graph.y_valid, loss_trav_raw, loss_trav_raw * (1 - confidence))
-        loss_trav_confidence = weighted.sum() / graph.y.shape[0]
+        if self._anomaly_balanced:
+            weighted = torch.where(graph.y_valid, loss_trav_raw, loss_trav_raw * (1 - confidence))
+            loss_trav_confidence = weighted.sum() / graph.y.shape[0]
+        else:
+            loss_trav_confidence = loss_trav_raw.mean()
         loss_temp = torch.zeros_like(loss_trav_confidence)
         loss_reco_mean = loss_reco[graph.y_valid].mean()
         loss = self._w_trav * loss_trav_confidence + self._w_reco * loss_reco_mean + self._w_temp * loss_temp
