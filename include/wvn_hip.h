@@ -750,6 +750,30 @@ int wvn_debug_gemm_n384(const void* A, int lda, const void* W, int ldw, const fl
                         void* stream);
 
 
+/* ---- exact dense CRF (csrc/dense_crf.hip; DESIGN.md "Dense CRF") ----
+ * Mean-field inference of the fully connected CRF of the public STEGO crf.py / pydensecrf DenseCRF2D recipe with every pixel pair
+ * evaluated: unary -log(clip(softmax(logits), 1e-5, 1)), smoothness kernel exp(-|dp|^2 / (2 pos_xy_std^2)) (weight pos_w; radius
+ * ceil(8 pos_xy_std), pos_xy_std <= 4), appearance kernel exp(-|dp|^2 / (2 bi_xy_std^2) - |dI|^2 / (2 bi_rgb_std^2)) (weight bi_w),
+ * symmetric normalisation, Potts compatibility, `iterations` (1..1000) updates.  Two CRFs on the same image may share the pass:
+ * logits1 (K1 >= 1 columns) and logits2 (K2 >= 0; NULL iff K2 == 0), K1 + K2 <= 64, each addressed as p[b * sb + k * sc + pixel * sp]
+ * (fp32; pixel = y * W + x).  image: u8 [B][H][W][3].  Outputs (any may be NULL, not all): labels int32 [B][1 or 2][H][W] (first
+ * maximum of the final Q, ids within each group; nseg_last non-NULL (needs labels): the last group's ids are compacted to ascending
+ * contiguous ids as the k-means relabel does and nseg_last [B] receives their count), probs fp32 [B][K1 + K2][H][W] (final Q), debug fp32 [B][2 KP + 2][H][W] with
+ * KP = 32 (K1 + K2 <= 32) or 64: rows 0..KP-1 the last iteration's bilateral message n_b(i) sum_j k_b n_b(j) Q_j, rows KP..2KP-1 the
+ * smoothness message, row 2 KP n_b, row 2 KP + 1 n_g (tests).  workspace: wvn_dense_crf_workspace_bytes(B, H, W, K1 + K2) bytes,
+ * 256-byte aligned, no initialisation.  B <= 65535, H, W <= 2048.  WVN_ERR_ARG (before any GPU call) for any other shape, a NULL
+ * input, non-positive standard deviations or non-finite weights; WVN_ERR_WORKSPACE when the workspace is too small. */
+size_t wvn_dense_crf_workspace_bytes(int B, int H, int W, int K);
+int wvn_dense_crf(const float* logits1, int K1, long long s1b, long long s1c, long long s1p, const float* logits2, int K2, long long s2b,
+                  long long s2c, long long s2p, const unsigned char* image, int B, int H, int W, int iterations, float pos_w, float pos_xy_std,
+                  float bi_w, float bi_xy_std, float bi_rgb_std, int* labels, int* nseg_last, float* probs, float* debug, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* the image STEGO's dense_crf rebuilds from the normalised frame: out u8 [B][out_h][out_w][3] =
+ * u8(trunc(255 * ((((x - mean) / std) * std) + mean))) with x the fp32 [0,1] frame (frame_u8: u8 / 255) [B][3][src_h][src_w] sampled
+ * through the ingest tables rows [out_h] / cols [out_w] (both NULL: identity, out == src size). */
+int wvn_crf_image(const void* frame, int frame_u8, int B, int src_h, int src_w, const int* rows, const int* cols, int out_h, int out_w,
+                  unsigned char* out, void* stream);
+
 /* ---- step scheduling (no reference counterpart: the reference runs one frame at a time on one CUDA stream,
  * wild_visual_navigation_ros/scripts/wvn_feature_extractor_node.py:319-363) ----
  * A HIP stream whose kernels may only occupy the compute units named by `mask` (bit i of the `words` 32-bit words = CU i in the

@@ -7,9 +7,10 @@ STEGO head (1x1-conv linear branch + 1x1-conv/ReLU/1x1-conv branch, summed) on t
 deterministic per-image cosine k-means for ``run_clustering=True``.  ``model_path`` is honoured: a Lightning checkpoint in
 either the upstream STEGO (``net.model.* / net.cluster1.* / cluster_probe.clusters / linear_probe.*``) or the
 self_supervised_segmentation (``backbone.* / segmentation_head.*``) key layout is loaded (``load_stego_checkpoint``); without
-one, seeded synthetic weights are used and a warning says so.  ``run_crf=True`` -- the reference constructor's own default -- needs
-pydensecrf (CPU, external): it raises unless the caller opts in to running WITHOUT the CRF refinement (``skip_crf=True`` or the
-environment variable ``WVN_SKIP_CRF=1``), in which case a warning says that the CRF step was dropped.
+one, seeded synthetic weights are used and a warning says so.  ``run_crf=True`` -- the reference constructor's own default -- runs
+the exact dense CRF on HIP with ``crf="exact"`` (``ops.dense_crf``); without it, it raises unless the caller opts in to running WITHOUT
+the CRF refinement (``skip_crf=True`` or the environment variable ``WVN_SKIP_CRF=1``), in which case a warning says that the CRF
+step was dropped.
 
 Two knobs make the definition explicit instead of implicit.  Their DEFAULTS are the upstream behaviour as published (Stego.get_code
 averages the code with the flipped-back code of the mirrored frame; postprocess clusters the code up-sampled to the image size);
@@ -123,6 +124,7 @@ class StegoInterface:
         fuse_proj: bool = True,
         skip_crf: Optional[bool] = None,  # run_crf=True without pydensecrf: None -> WVN_SKIP_CRF env, True -> warn and drop the CRF step
         pos_embed_rule: str = "dino",   # position-table resampling of the backbone (backbone.resample_pos_embed)
+        crf: Optional[str] = None,       # with run_crf=True: "exact" = the mean-field dense CRF with every pixel pair (ops.dense_crf, csrc/dense_crf.hip)
         code_align_corners: bool = True,   # how postprocess() up-samples the code BEFORE clustering / probing (the absent package's choice, stego_interface.py:94-100):
         #                                    True = the align_corners=True taps of WVN's own later up-sample (:107); False = the half-pixel taps of the public STEGO
         #                                    evaluation code.  `features` (stego_interface.py:107) and the pooling are WVN's own code: always align_corners=True
@@ -132,14 +134,26 @@ class StegoInterface:
                              run_clustering=run_clustering, n_image_clusters=n_image_clusters)
         else:
             self._cfg = _Cfg(cfg)
-        if self._cfg.run_crf:
+        if crf not in (None, "exact"):
+            raise _lib.WvnError(f"crf must be None or 'exact', not {crf!r}")
+        self._crf = bool(self._cfg.run_crf) and crf == "exact"
+        if self._crf:
+            # the exact dense CRF on the input_size x input_size frame, before the nearest resample to the camera height (DESIGN.md "Dense CRF")
+            if skip_crf:
+                raise _lib.WvnError("crf='exact' runs the CRF refinement; it cannot be combined with skip_crf=True")
+            if cluster_resolution != "pixel":
+                raise _lib.WvnError("crf='exact' refines pixel-resolution maps: it needs cluster_resolution='pixel'")
+            if not code_align_corners:
+                raise _lib.WvnError("crf='exact' builds its pixel logits with the align_corners=True up-sample; code_align_corners=False has no "
+                                    "dense half-pixel up-sample to feed it")
+        elif self._cfg.run_crf:
             import os
 
             if skip_crf is None:
                 skip_crf = os.environ.get("WVN_SKIP_CRF", "0") not in ("", "0")
             if not skip_crf:
-                raise _lib.WvnError("run_crf=True needs pydensecrf (CPU, external); FeatureExtractor uses run_crf=False.  Pass "
-                                    "skip_crf=True (or set WVN_SKIP_CRF=1) to run the segmentation without the CRF refinement")
+                raise _lib.WvnError("run_crf=True needs pydensecrf (CPU, external) unless crf='exact' selects the HIP dense CRF; FeatureExtractor "
+                                    "uses run_crf=False.  Pass skip_crf=True (or set WVN_SKIP_CRF=1) to run the segmentation without the CRF refinement")
             warnings.warn("StegoInterface: run_crf=True but the dense CRF (pydensecrf, CPU) is not part of the MI355X path -- the "
                           "cluster / linear predictions are returned WITHOUT CRF refinement (skip_crf)", stacklevel=2)
         if cluster_resolution not in ("patch", "pixel"):
@@ -311,6 +325,8 @@ class StegoInterface:
         self._code = None  # dense code is produced lazily (features property): 72 MB/frame at 448^2
         self._H = H
         self._labels_patch = None
+        if self._crf:
+            return self._inference_crf(img, code)
         if self._cluster_resolution == "pixel":      # cluster the S x S up-sampled code pixels
             K = self._cfg.n_image_clusters
             if self._cfg.run_clustering:
@@ -371,6 +387,52 @@ class StegoInterface:
             else:
                 lin = self._probe_labels(rows, self._w_probe, self._b_probe, cosine=False)
                 self._linear_pred = ops.upsample_nearest_labels(lin.reshape(B, G, G), H)[None]
+        else:
+            self._linear_pred = None
+        return self._linear_pred, self._cluster_pred
+
+    def _inference_crf(self, img: torch.Tensor, code: torch.Tensor):
+        """``inference`` with ``crf='exact'`` (stego_interface.py:94-100): both maps refined by the dense CRF on the input_size x input_size
+        frame, then nearest-resampled to the camera height.  CRF logits per branch (readings, DESIGN.md "Dense CRF"): the linear probe's
+        patch logits bilinearly up-sampled (align_corners=True); the cluster probe / the per-image k-means: 2 * cos(code pixel, centroid)
+        (STEGO's cluster_probe(code, 2, log_probs=True)) with the code pixels the up-sampled code and, for k-means, the final per-image
+        centroids.  Two CRFs that fit one pass (<= 64 columns together) share it."""
+        G, H, S = self._bb.grid, img.shape[2], self._cfg.input_size
+        B = code.shape[0]
+        image = ops.crf_image(img.to(self._device), S)                        # [B, S, S, 3] u8
+        rows = code.reshape(B * G * G, self._C)
+        lin = None
+        if self._w_probe is not None:
+            logits = ops.gemm_f32(rows if rows.is_contiguous() else rows.contiguous(), self._w_probe, self._b_probe)
+            lin = ops.upsample_bilinear(logits.reshape(B, G * G, -1), G, S)   # [B, n, S, S]
+        pixn = ops.normalize_rows(ops.upsample_bilinear(code, G, S).permute(0, 2, 3, 1).reshape(B * S * S, self._C))
+        if self._cfg.run_clustering:
+            K = self._cfg.n_image_clusters
+            _, _, cent = ops.kmeans_cosine_pixels(code, G, S, K, KMEANS_ITERS, relabel=False, return_centroids=True,
+                                                  form=self._kmeans_form if ops.kmeans_pixels_linear_supported(G, S, self._C, K) else "direct")
+            cent2 = ops.normalize_rows(cent.reshape(B * K, self._C)) * 2.0          # (x 2: exact in fp32)
+            sim = torch.empty(B, S * S, K, dtype=torch.float32, device=self._device)
+            for b in range(B):
+                ops.gemm_f32(pixn[b * S * S:(b + 1) * S * S], cent2[b * K:(b + 1) * K], None, out=sim[b])
+        else:
+            K = self._clusters.shape[0]
+            sim = ops.gemm_f32(pixn, self._clusters * 2.0, None).reshape(B, S * S, K)
+        clu = sim.reshape(B, S, S, K).permute(0, 3, 1, 2)                     # [B, K, S, S] view (pixel stride K)
+        relabel = bool(self._cfg.run_clustering)
+        if lin is not None and lin.shape[1] + K <= 64:
+            out = ops.dense_crf((lin, clu), image, relabel_last=relabel)
+            labels, nseg = out if relabel else (out, None)
+            lab_lin, lab_clu = labels[:, 0], labels[:, 1]
+        else:
+            lab_lin = ops.dense_crf(lin, image) if lin is not None else None
+            out = ops.dense_crf(clu, image, relabel_last=relabel)
+            lab_clu, nseg = (out[0], out[1]) if relabel else (out, None)
+        self._n_segments = nseg
+        lab_clu = lab_clu.contiguous()
+        self._cluster_pred = (lab_clu if H == S else ops.upsample_nearest_labels(lab_clu, H))[None]
+        if lab_lin is not None:
+            lab_lin = lab_lin.contiguous()
+            self._linear_pred = (lab_lin if H == S else ops.upsample_nearest_labels(lab_lin, H))[None]
         else:
             self._linear_pred = None
         return self._linear_pred, self._cluster_pred

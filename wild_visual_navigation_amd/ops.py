@@ -435,6 +435,86 @@ def resize_nearest_crop(img: torch.Tensor, tables) -> torch.Tensor:
     return out
 
 
+def crf_image(frame: torch.Tensor, size: Optional[int] = None) -> torch.Tensor:
+    """frame [B,3,H,W] (fp32 in [0,1] or raw uint8) -> the u8 image [B, S, S, 3] STEGO's dense_crf rebuilds from the normalised frame:
+    u8(trunc(255 * ((((x - mean) / std) * std) + mean))), one fp32 operation at a time, with x the NEAREST-resized, centre-cropped frame
+    (the ingest tables of ``transforms.ingest_tables``; ``size`` None keeps the frame's own size)."""
+    require_cuda(frame, "frame")
+    B, Cc, Hs, Ws = frame.shape
+    if Cc != 3:
+        raise _lib.WvnError(f"crf_image: expected [B,3,H,W], got {tuple(frame.shape)}")
+    u8 = frame.dtype == torch.uint8
+    frame = (frame if u8 else frame.float()).contiguous()
+    rows = cols = None
+    Ho = Wo = size
+    if size is None or (Hs, Ws) == (size, size):
+        Ho, Wo = Hs, Ws
+    else:
+        from .feature_extractor.transforms import ingest_tables
+        tab = ingest_tables(Hs, Ws, size, frame.device)
+        rows, cols = tab.rows, tab.cols
+    out = torch.empty(B, Ho, Wo, 3, dtype=torch.uint8, device=frame.device)
+    check(lib().wvn_crf_image(ptr(frame), int(u8), B, Hs, Ws, ptr(rows), ptr(cols), Ho, Wo, ptr(out), stream()), "wvn_crf_image")
+    return out
+
+
+def dense_crf(logits, image_u8: torch.Tensor, iterations: int = 10, pos_w: float = 3.0, pos_xy_std: float = 1.0, bi_w: float = 4.0,
+              bi_xy_std: float = 67.0, bi_rgb_std: float = 3.0, return_probs: bool = False, relabel_last: bool = False,
+              _debug: bool = False):
+    """Exact mean-field dense CRF (csrc/dense_crf.hip; DESIGN.md "Dense CRF"): logits [B,K,H,W] fp32 (K <= 64; any strides with the
+    pixel dimensions dense, e.g. a permuted [B,H,W,K] view), image_u8 [B,H,W,3] -> labels int32 [B,H,W] (first maximum of Q^T), plus
+    Q fp32 [B,K,H,W] when ``return_probs``.  ``logits`` may also be a tuple of two such tensors (K1 + K2 <= 64): two CRFs on the same
+    image in one pass (shared exponentials), labels [B,2,H,W] and Q [B,K1+K2,H,W].  ``relabel_last``: the last group's labels are
+    compacted to ascending contiguous ids (the k-means relabel rule) and their count per frame int32 [B] is returned after the labels.  ``_debug`` (tests): also returns the last
+    iteration's messages and normalisers [B, 2 KP + 2, H, W] (include/wvn_hip.h)."""
+    pair = isinstance(logits, (tuple, list))
+    ls = list(logits) if pair else [logits]
+    if len(ls) not in (1, 2):
+        raise _lib.WvnError("dense_crf: one logits tensor or a pair")
+    require_cuda(image_u8, "image_u8")
+    if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or image_u8.shape[-1] != 3:
+        raise _lib.WvnError(f"dense_crf: image must be uint8 [B,H,W,3], got {tuple(image_u8.shape)} {image_u8.dtype}")
+    B, H, W, _ = image_u8.shape
+    desc = []
+    for t in ls:
+        require_cuda(t, "logits")
+        if t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] != B or tuple(t.shape[2:]) != (H, W):
+            raise _lib.WvnError(f"dense_crf: logits must be fp32 [B,K,{H},{W}] matching the image, got {tuple(t.shape)} {t.dtype}")
+        if t.stride(2) != W * t.stride(3):
+            t = t.contiguous()
+        desc.append((t, t.shape[1], t.stride(0), t.stride(1), t.stride(3)))
+    K1 = desc[0][1]
+    K2 = desc[1][1] if pair else 0
+    KT = K1 + K2
+    if K1 < 1 or K2 < 0 or KT > 64 or (pair and K2 < 1):
+        raise _lib.WvnError(f"dense_crf: 1..64 label columns in all (got {K1} + {K2})")
+    image_u8 = image_u8.contiguous()
+    dev = image_u8.device
+    ng = 2 if pair else 1
+    labels = torch.empty(B, ng, H, W, dtype=torch.int32, device=dev)
+    probs = torch.empty(B, KT, H, W, dtype=torch.float32, device=dev) if return_probs else None
+    KP = 32 if KT <= 32 else 64
+    dbg = torch.zeros(B, 2 * KP + 2, H, W, dtype=torch.float32, device=dev) if _debug else None
+    nseg = torch.empty(B, dtype=torch.int32, device=dev) if relabel_last else None
+    nbytes = lib().wvn_dense_crf_workspace_bytes(B, H, W, KT)
+    if nbytes == 0:
+        raise _lib.WvnError(f"dense_crf: unsupported shape B={B}, H={H}, W={W}, K={KT}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    t1, _, b1, c1, p1 = desc[0]
+    t2, _, b2, c2, p2 = desc[1] if pair else (None, 0, 0, 0, 0)
+    check(lib().wvn_dense_crf(ptr(t1), K1, b1, c1, p1, ptr(t2), K2, b2, c2, p2, ptr(image_u8), B, H, W, int(iterations), float(pos_w),
+                              float(pos_xy_std), float(bi_w), float(bi_xy_std), float(bi_rgb_std), ptr(labels), ptr(nseg), ptr(probs), ptr(dbg),
+                              ptr(ws), nbytes, stream()), "wvn_dense_crf")
+    out = (labels if pair else labels[:, 0],)
+    if relabel_last:
+        out += (nseg,)
+    if return_probs:
+        out += (probs,)
+    if _debug:
+        out += (dbg,)
+    return out[0] if len(out) == 1 else out
+
+
 def gemm_f32(a, b, bias=None, epi=_lib.F32_NONE, trans_a=False, trans_b=True, out=None, mask=None):
     """fp32 GEMM; trans_b=True means b is stored [N,K] (Linear layout)."""
     M = a.shape[1] if trans_a else a.shape[0]
