@@ -774,6 +774,27 @@ int wvn_dense_crf(const float* logits1, int K1, long long s1b, long long s1c, lo
 int wvn_crf_image(const void* frame, int frame_u8, int B, int src_h, int src_w, const int* rows, const int* cols, int out_h, int out_w,
                   unsigned char* out, void* stream);
 
+/* ---- permutohedral-lattice dense CRF (csrc/dense_crf_permutohedral.hip; DESIGN.md "Permutohedral dense CRF") ----
+ * The CRF of wvn_dense_crf (same unary, Potts update, symmetric normalisation, softmax, tie rule, arguments and outputs) with both
+ * kernel sums computed by the permutohedral-lattice filter pydensecrf's DenseCRF2D runs (Adams et al. 2010): Gaussian features
+ * (x / pos_xy_std, y / pos_xy_std), bilateral features (x / bi_xy_std, y / bi_xy_std, r / bi_rgb_std, g / bi_rgb_std, b / bi_rgb_std),
+ * splat, blur along the d + 1 axes, slice scaled by 1 / (1 + 2^-d).  debug rows as wvn_dense_crf (the lattice messages and
+ * normalisers).  Bitwise reproducible and independent of the batch.  No pos_xy_std limit, but WVN_ERR_ARG when the lattice
+ * coordinates the shape and standard deviations allow do not fit 16-bit keys (pydensecrf's) or, packed, 64 bits.  workspace:
+ * wvn_dense_crf_permutohedral_workspace_bytes(B, H, W, K1 + K2) bytes (sized by the bound of N (d + 1) lattice points per frame and
+ * lattice), 256-byte aligned, no initialisation; the call is stream-ordered with no host synchronisation. */
+size_t wvn_dense_crf_permutohedral_workspace_bytes(int B, int H, int W, int K);
+int wvn_dense_crf_permutohedral(const float* logits1, int K1, long long s1b, long long s1c, long long s1p, const float* logits2, int K2,
+                                long long s2b, long long s2c, long long s2p, const unsigned char* image, int B, int H, int W, int iterations,
+                                float pos_w, float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, int* labels, int* nseg_last,
+                                float* probs, float* debug, void* workspace, size_t workspace_bytes, void* stream);
+/* tests: the lattice of one kernel (bilateral = 0: Gaussian, d = 2, features of xy_std; 1: bilateral, d = 5) for every frame.  With
+ * E = H W (d + 1): M int [B]; keys int [B][E][d] (rows 0..M-1: the lattice points' keys, ascending lexicographically); bary fp32 and
+ * vert int [B][E] (vertex pixel (d + 1) + r: its weight and its table row 1..M); nbr int [B][d + 1][E][2] (rows 0..M-1: the rows of
+ * the blur neighbours n1, n2 along each axis, 0 = absent).  workspace: wvn_dense_crf_permutohedral_workspace_bytes(B, H, W, 1). */
+int wvn_debug_permutohedral_lattice(const unsigned char* image, int B, int H, int W, int bilateral, float xy_std, float rgb_std, int* M,
+                                    int* keys, float* bary, int* vert, int* nbr, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- step scheduling (no reference counterpart: the reference runs one frame at a time on one CUDA stream,
  * wild_visual_navigation_ros/scripts/wvn_feature_extractor_node.py:319-363) ----
  * A HIP stream whose kernels may only occupy the compute units named by `mask` (bit i of the `words` 32-bit words = CU i in the

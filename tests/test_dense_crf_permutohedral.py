@@ -1,0 +1,520 @@
+"""Permutohedral-lattice dense CRF (csrc/dense_crf_permutohedral.hip, ops.dense_crf(method="permutohedral"),
+StegoInterface(run_crf=True, crf="permutohedral")) against the statements of DESIGN.md "Permutohedral dense CRF".
+
+Two statements live here and nowhere else: the lattice construction in float32, one numpy operation per statement of the reading
+(``lattice32``), and the filter and CRF on that lattice in float64 (``filter64``, ``crf_lattice64``).  The CPU tests pin both to a
+literal per-pixel loop transcription of the reading; the GPU tests hold the kernels to them (the lattice bit for bit)."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from wild_visual_navigation_amd import _lib
+from tests.test_dense_crf import _features, blocky_image, crf_image_ref, g, kernel_apply, unary64
+
+F32 = np.float32
+
+
+# ---------------------------------------------------------------- the float32 lattice statement --------------------------------------
+def lattice_scale(d):
+    """inv_std_dev = sqrt(2/3) (d + 1) and scale[i] = 1 / sqrt((i + 2)(i + 1)) * inv_std_dev: double expressions stored as float."""
+    inv = F32(math.sqrt(2.0 / 3.0) * (d + 1))
+    return np.array([1.0 / math.sqrt(float((i + 2) * (i + 1))) * float(inv) for i in range(d)], dtype=F32)
+
+
+def features32(H, W, image, xy_std, rgb_std=None):
+    """DenseCRF2D's features [N, d] fp32: (x / xy_std, y / xy_std[, r / rgb_std, g / rgb_std, b / rgb_std]), x the column."""
+    ys, xs = np.mgrid[0:H, 0:W]
+    cols = [xs.reshape(-1).astype(F32) / F32(xy_std), ys.reshape(-1).astype(F32) / F32(xy_std)]
+    if rgb_std is not None:
+        im = np.asarray(image).reshape(-1, 3).astype(F32)
+        cols += [im[:, c] / F32(rgb_std) for c in range(3)]
+    return np.stack(cols, 1)
+
+
+def lattice32(f):
+    """Permutohedral::init on features f [N, d] (fp32, vectorised over pixels).  Returns M, keys [M, d] (ascending lexicographically),
+    bary fp32 [N, d + 1], vert [N, d + 1] (rows 1..M of each vertex), nbr [d + 1, M, 2] (blur neighbour rows, 0 = absent)."""
+    N, d = f.shape
+    scale = lattice_scale(d)
+    e = np.zeros((N, d + 1), F32)
+    sm = np.zeros(N, F32)
+    for j in range(d, 0, -1):
+        cf = f[:, j - 1] * scale[j - 1]
+        e[:, j] = sm - F32(j) * cf
+        sm = sm + cf
+    e[:, 0] = sm
+    down_factor, up_factor = F32(1.0) / F32(d + 1), F32(d + 1)
+    v = down_factor * e
+    up, down = np.ceil(v) * up_factor, np.floor(v) * up_factor
+    rd = np.where(up - e < e - down, up, down).astype(np.int32)
+    rem0 = rd.astype(F32)
+    s = np.zeros(N, np.int32)
+    for i in range(d + 1):
+        s = (s.astype(F32) + rd[:, i].astype(F32) * down_factor).astype(np.int32)   # int sum; sum += rd2 * down_factor
+    rank = np.zeros((N, d + 1), np.int64)
+    for i in range(d):
+        di = e[:, i] - rem0[:, i]
+        for j in range(i + 1, d + 1):
+            lt = di < e[:, j] - rem0[:, j]
+            rank[:, i] += lt
+            rank[:, j] += ~lt
+    rank += s[:, None]
+    neg, pos = rank < 0, rank > d
+    rank[neg] += d + 1
+    rem0[neg] += F32(d + 1)
+    rank[pos] -= d + 1
+    rem0[pos] -= F32(d + 1)
+    bar = np.zeros((N, d + 2), F32)
+    ar = np.arange(N)
+    for i in range(d + 1):
+        vv = (e[:, i] - rem0[:, i]) * down_factor
+        bar[ar, d - rank[:, i]] += vv
+        bar[ar, d - rank[:, i] + 1] -= vv
+    bar[:, 0] = (bar[:, 0].astype(np.float64) + (1.0 + bar[:, d + 1].astype(np.float64))).astype(F32)
+    keys = np.empty((N, d + 1, d), np.int64)
+    for r in range(d + 1):
+        keys[:, r, :] = rem0[:, :d].astype(np.int64) + np.where(rank[:, :d] <= d - r, r, r - (d + 1))
+    flat = keys.reshape(-1, d)
+    order = np.lexsort(flat.T[::-1])
+    sk = flat[order]
+    head = np.ones(len(sk), bool)
+    head[1:] = (sk[1:] != sk[:-1]).any(1)
+    ukeys = sk[head]
+    vert = np.empty(len(flat), np.int64)
+    vert[order] = np.cumsum(head)
+    return dict(M=len(ukeys), keys=ukeys, bary=bar[:, :d + 1], vert=vert.reshape(N, d + 1), nbr=_neighbours(ukeys))
+
+
+def _neighbours(ukeys):
+    M, d = ukeys.shape
+    base = ukeys.min(0) - d - 2
+    span = ukeys.max(0) - base + d + 3
+    mult = np.ones(d, np.int64)
+    for i in range(d - 2, -1, -1):
+        mult[i] = mult[i + 1] * span[i + 1]
+    codes = ((ukeys - base) * mult).sum(1)   # coordinate 0 most significant: ascending with the keys
+    nbr = np.zeros((d + 1, M, 2), np.int64)
+    for j in range(d + 1):
+        n1, n2 = ukeys - 1, ukeys + 1
+        if j < d:
+            n1[:, j] = ukeys[:, j] + d
+            n2[:, j] = ukeys[:, j] - d
+        for s, n in enumerate((n1, n2)):
+            c = ((n - base) * mult).sum(1)
+            at = np.minimum(np.searchsorted(codes, c), M - 1)
+            nbr[j, :, s] = np.where(codes[at] == c, at + 1, 0)
+    return nbr
+
+
+def filter64(lat, V):
+    """splat / blur / slice of V [N, C] float64 (torch, any device) on the lattice ``lat`` (tensors on V's device)."""
+    N, d1 = lat["vert"].shape
+    d = d1 - 1
+    vert, bary = lat["vert"].reshape(-1).long(), lat["bary"].double()
+    tab = torch.zeros(lat["M"] + 1, V.shape[1], dtype=torch.float64, device=V.device)
+    tab.index_add_(0, vert, (bary[..., None] * V[:, None, :]).reshape(-1, V.shape[1]))
+    for j in range(d + 1):
+        n = lat["nbr"][j].long()
+        new = tab.clone()
+        new[1:] = tab[1:] + 0.5 * (tab[n[:, 0]] + tab[n[:, 1]])
+        tab = new
+    alpha = 1.0 / (1.0 + 2.0 ** -d)
+    return (bary[..., None] * tab[lat["vert"].long()]).sum(1) * alpha
+
+
+def lattices(image, H, W, pos_xy_std=1.0, bi_xy_std=67.0, bi_rgb_std=3.0, dev="cpu"):
+    out = []
+    for f in (features32(H, W, image, pos_xy_std), features32(H, W, image, bi_xy_std, bi_rgb_std)):
+        lat = lattice32(f)
+        out.append(dict(M=lat["M"], vert=torch.from_numpy(lat["vert"]).to(dev), bary=torch.from_numpy(lat["bary"]).to(dev),
+                        nbr=torch.from_numpy(lat["nbr"]).to(dev)))
+    return out
+
+
+def crf_lattice64(logits, image, iterations=10, pos_w=3.0, pos_xy_std=1.0, bi_w=4.0, bi_xy_std=67.0, bi_rgb_std=3.0, parts=False):
+    """logits [K, H, W], image u8 [H, W, 3] -> Q^T [K, H, W] float64 with both messages filtered on the fp32 lattices."""
+    K, H, W = logits.shape
+    dev = logits.device
+    lg, lb = lattices(image.cpu().numpy(), H, W, pos_xy_std, bi_xy_std, bi_rgb_std, dev)
+    ones = torch.ones(H * W, 1, dtype=torch.float64, device=dev)
+    n_g = (filter64(lg, ones)[:, 0] + 1e-20).rsqrt()
+    n_b = (filter64(lb, ones)[:, 0] + 1e-20).rsqrt()
+    negU = unary64(logits.reshape(K, H * W))
+    Q = torch.softmax(negU, 1)
+    first = None
+    for _ in range(iterations):
+        mg = n_g[:, None] * filter64(lg, n_g[:, None] * Q)
+        mb = n_b[:, None] * filter64(lb, n_b[:, None] * Q)
+        if first is None:
+            first = dict(n_g=n_g, n_b=n_b, msg_g=mg, msg_b=mb, lg=lg, lb=lb)
+        Q = torch.softmax(negU + pos_w * mg + bi_w * mb, 1)
+    Q = Q.T.reshape(K, H, W)
+    return (Q, first) if parts else Q
+
+
+# ---------------------------------------------------------------- the literal loop transcription -------------------------------------
+def lattice_literal(f):
+    """Permutohedral::init pixel by pixel with a hash table, as the reading writes it (np.float32 scalars, Python ints)."""
+    N, d = f.shape
+    scale = lattice_scale(d)
+    table, keys_of, bary, rows = {}, [], np.zeros((N, d + 1), F32), np.zeros((N, d + 1), np.int64)
+    canonical = [[r if j <= d - r else r - (d + 1) for j in range(d + 1)] for r in range(d + 1)]
+    for k in range(N):
+        e = [F32(0)] * (d + 1)
+        sm = F32(0)
+        for j in range(d, 0, -1):
+            cf = F32(f[k, j - 1]) * scale[j - 1]
+            e[j] = F32(sm - F32(j) * cf)
+            sm = F32(sm + cf)
+        e[0] = sm
+        down_factor, up_factor = F32(1.0) / F32(d + 1), F32(d + 1)
+        rem0, total = [F32(0)] * (d + 1), 0
+        for i in range(d + 1):
+            v = F32(down_factor * e[i])
+            up, down = F32(math.ceil(v)) * up_factor, F32(math.floor(v)) * up_factor
+            rd = int(up) if up - e[i] < e[i] - down else int(down)
+            rem0[i] = F32(rd)
+            total = int(F32(F32(total) + F32(F32(rd) * down_factor)))
+        rank = [0] * (d + 1)
+        for i in range(d):
+            di = F32(e[i] - rem0[i])
+            for j in range(i + 1, d + 1):
+                if di < F32(e[j] - rem0[j]):
+                    rank[i] += 1
+                else:
+                    rank[j] += 1
+        for i in range(d + 1):
+            rank[i] += total
+            if rank[i] < 0:
+                rank[i] += d + 1
+                rem0[i] = F32(rem0[i] + F32(d + 1))
+            elif rank[i] > d:
+                rank[i] -= d + 1
+                rem0[i] = F32(rem0[i] - F32(d + 1))
+        b = [F32(0)] * (d + 2)
+        for i in range(d + 1):
+            v = F32(F32(e[i] - rem0[i]) * down_factor)
+            b[d - rank[i]] = F32(b[d - rank[i]] + v)
+            b[d - rank[i] + 1] = F32(b[d - rank[i] + 1] - v)
+        b[0] = F32(float(b[0]) + (1.0 + float(b[d + 1])))
+        for r in range(d + 1):
+            key = tuple(int(rem0[i]) + canonical[r][rank[i]] for i in range(d))
+            if key not in table:
+                table[key] = len(keys_of)
+                keys_of.append(key)
+            rows[k, r] = table[key]
+            bary[k, r] = b[r]
+    # renumber in ascending key order (the sort's numbering; the hash table's insertion order is not part of the reading)
+    order = sorted(range(len(keys_of)), key=lambda i: keys_of[i])
+    new = {old: n + 1 for n, old in enumerate(order)}
+    ukeys = [keys_of[i] for i in order]
+    index = {key: n + 1 for n, key in enumerate(ukeys)}
+    nbr = np.zeros((d + 1, len(ukeys), 2), np.int64)
+    for j in range(d + 1):
+        for m, key in enumerate(ukeys):
+            n1 = [c - 1 for c in key]
+            n2 = [c + 1 for c in key]
+            if j < d:
+                n1[j], n2[j] = key[j] + d, key[j] - d
+            nbr[j, m] = (index.get(tuple(n1), 0), index.get(tuple(n2), 0))
+    vert = np.vectorize(lambda r: new[r])(rows)
+    return dict(M=len(ukeys), keys=np.array(ukeys, np.int64).reshape(-1, d), bary=bary, vert=vert, nbr=nbr)
+
+
+def filter_literal(lat, V):
+    """seqCompute in Python floats: splat in pixel order, blur axis by axis, slice with alpha."""
+    N, d1 = lat["vert"].shape
+    d, C_ = d1 - 1, V.shape[1]
+    vals = [[0.0] * C_ for _ in range(lat["M"] + 1)]
+    for i in range(N):
+        for r in range(d1):
+            o, w = int(lat["vert"][i, r]), float(lat["bary"][i, r])
+            for c in range(C_):
+                vals[o][c] += w * float(V[i, c])
+    for j in range(d1):
+        new = [row[:] for row in vals]
+        for m in range(lat["M"]):
+            n1, n2 = (int(x) for x in lat["nbr"][j, m])
+            for c in range(C_):
+                new[m + 1][c] = vals[m + 1][c] + 0.5 * (vals[n1][c] + vals[n2][c])
+        vals = new
+    alpha = 1.0 / (1.0 + 2.0 ** -d)
+    out = np.zeros((N, C_))
+    for i in range(N):
+        for r in range(d1):
+            for c in range(C_):
+                out[i, c] += float(lat["bary"][i, r]) * vals[int(lat["vert"][i, r])][c] * alpha
+    return out
+
+
+# ---------------------------------------------------------------- CPU ----------------------------------------------------------------
+@pytest.mark.parametrize("bilateral", [False, True])
+def test_lattice_statement_matches_the_literal_loop(bilateral):
+    H, W = 7, 9
+    image = blocky_image(H, W, 11, noise=20).numpy()
+    f = features32(H, W, image, 1.5, 10.0) if bilateral else features32(H, W, image, 1.5)
+    want, got = lattice_literal(f), lattice32(f)
+    assert got["M"] == want["M"] and got["M"] > H * W // 2
+    assert np.array_equal(got["keys"], want["keys"]) and np.array_equal(got["vert"], want["vert"])
+    assert np.array_equal(got["bary"].view(np.int32), want["bary"].view(np.int32))
+    assert np.array_equal(got["nbr"], want["nbr"]) and (got["nbr"] > 0).any()
+    assert np.allclose(got["bary"].sum(1), 1.0, atol=1e-5) and (got["bary"] >= -1e-6).all()
+    V = np.random.default_rng(0).standard_normal((H * W, 3))
+    lat_t = dict(M=got["M"], vert=torch.from_numpy(got["vert"]), bary=torch.from_numpy(got["bary"]), nbr=torch.from_numpy(got["nbr"]))
+    assert np.abs(filter64(lat_t, torch.from_numpy(V)).numpy() - filter_literal(got, V)).max() < 1e-12
+
+
+# measured on the image below (DESIGN.md "Permutohedral dense CRF"): max relative distance of the lattice normaliser from the exact
+# one 0.138 (Gaussian kernel, pos_xy_std = 1) and 0.564 (bilateral, the STEGO constants).  The lattice filter does not keep the
+# kernel's mass (filter(1) is 0.77-0.93 of the exact sum for the Gaussian, 0.41-0.70 for the bilateral kernel here); the symmetric
+# normalisation divides most of that out of the messages.
+NORM_DISTANCE = {"gaussian": 0.18, "bilateral": 0.65}
+
+
+def test_lattice_normaliser_is_near_the_exact_one():
+    H, W = 24, 32
+    image = blocky_image(H, W, 5)
+    lg, lb = lattices(image.numpy(), H, W)
+    pos, col = _features(H, W, image, "cpu")
+    ones = torch.ones(H * W, 1, dtype=torch.float64)
+    for name, lat, exact in (("gaussian", lg, kernel_apply(pos, col, ones, 1.0)), ("bilateral", lb, kernel_apply(pos, col, ones, 67.0, 3.0))):
+        n_lat = (filter64(lat, ones)[:, 0] + 1e-20).rsqrt()
+        n_ex = (exact[:, 0] + 1e-20).rsqrt()
+        dist = ((n_lat - n_ex).abs() / n_ex).max().item()
+        assert dist <= NORM_DISTANCE[name], (name, dist)
+
+
+def test_permutohedral_symbols_are_exported_and_bound():
+    for name in ("wvn_dense_crf_permutohedral", "wvn_dense_crf_permutohedral_workspace_bytes", "wvn_debug_permutohedral_lattice"):
+        assert name in _lib.EXPORTED_SYMBOLS
+    h = _lib.lib()
+    assert h.wvn_dense_crf_permutohedral_workspace_bytes(2, 40, 56, 27) > 0
+    assert h.wvn_dense_crf_permutohedral_workspace_bytes(1, 40, 56, 0) == 0
+    assert h.wvn_dense_crf_permutohedral_workspace_bytes(1, 40, 56, 65) == 0
+
+
+def test_permutohedral_rejects_bad_arguments_without_the_gpu():
+    h = _lib.lib()
+    buf = C.create_string_buffer(1 << 16)
+    p = C.addressof(buf)
+    ws = h.wvn_dense_crf_permutohedral_workspace_bytes(1, 8, 8, 4)
+
+    def call(l1=p, K1=4, l2=0, K2=0, img=p, B=1, H=8, W=8, T=10, pos_std=1.0, bi_std=67.0, rgb_std=3.0, labels=p, nseg=0, probs=0,
+             work=p, nbytes=ws, pos_w=3.0):
+        return h.wvn_dense_crf_permutohedral(l1, K1, 64 * K1, 64, 1, l2, K2, 64 * max(K2, 1), 64, 1, img, B, H, W, T, pos_w, pos_std, 4.0,
+                                             bi_std, rgb_std, labels, nseg, probs, 0, work, nbytes, None)
+
+    ARG = 1001
+    assert call(K1=0) == ARG and call(K1=65) == ARG and call(K1=40, l2=p, K2=30) == ARG
+    assert call(K2=3) == ARG and call(l2=p) == ARG
+    assert call(l1=0) == ARG and call(img=0) == ARG and call(work=0) == ARG
+    assert call(labels=0) == ARG and call(labels=0, nseg=p, probs=p) == ARG
+    assert call(B=0) == ARG and call(H=0) == ARG and call(W=-3) == ARG and call(H=4096) == ARG
+    assert call(T=0) == ARG
+    assert call(pos_std=0.0) == ARG and call(rgb_std=-1.0) == ARG and call(bi_std=float("inf")) == ARG and call(pos_w=float("nan")) == ARG
+    # key range: coordinates beyond pydensecrf's 16-bit keys, or more than 64 bits packed
+    assert call(rgb_std=0.01) == ARG                           # colour coordinates up to ~3.6e4
+    assert call(H=2048, W=2048, pos_std=0.05, nbytes=1 << 62) == ARG   # positions up to ~7e4
+    assert call(rgb_std=0.2) == ARG                            # 16-bit coordinates, but five of them need more than 64 bits
+    assert call(nbytes=ws - 1) == 1002                         # WVN_ERR_WORKSPACE
+    lws = h.wvn_dense_crf_permutohedral_workspace_bytes(1, 8, 8, 1)
+    assert h.wvn_debug_permutohedral_lattice(p, 1, 8, 8, 1, 67.0, 0.01, p, p, p, p, p, p, lws, None) == ARG
+
+
+def test_stego_interface_permutohedral_refusals():
+    from wild_visual_navigation_amd.feature_extractor.stego_interface import StegoInterface
+
+    with pytest.raises(_lib.WvnError, match="skip_crf"):
+        StegoInterface("cpu", input_size=64, run_crf=True, crf="permutohedral", skip_crf=True, allow_synthetic=True)
+    with pytest.raises(_lib.WvnError, match="cluster_resolution"):
+        StegoInterface("cpu", input_size=64, run_crf=True, crf="permutohedral", cluster_resolution="patch", allow_synthetic=True)
+    with pytest.raises(_lib.WvnError, match="code_align_corners"):
+        StegoInterface("cpu", input_size=64, run_crf=True, crf="permutohedral", code_align_corners=False, allow_synthetic=True)
+
+
+# ---------------------------------------------------------------- GPU ----------------------------------------------------------------
+def _gpu_lattice_equals_statement(dev, image):
+    from wild_visual_navigation_amd import ops
+
+    H, W, _ = image.shape
+    for bilateral, (xy, rgb) in ((False, (1.0, None)), (True, (67.0, 3.0))):
+        got = ops._permutohedral_lattice(image[None].to(dev), bilateral, xy, rgb if rgb else 1.0)[0]
+        want = lattice32(features32(H, W, image.numpy(), xy, rgb))
+        assert got["M"] == want["M"], (bilateral, got["M"], want["M"])
+        assert np.array_equal(got["keys"].numpy(), want["keys"])
+        assert np.array_equal(got["vert"].numpy(), want["vert"])
+        assert np.array_equal(got["bary"].numpy().view(np.int32), want["bary"].view(np.int32))
+        assert np.array_equal(got["nbr"].numpy(), want["nbr"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", [(64, 64), (40, 56), (97, 131)])
+def test_lattice_is_bit_identical_to_the_fp32_statement(dev, H, W):
+    _gpu_lattice_equals_statement(dev, blocky_image(H, W, H * W))
+
+
+@pytest.mark.gpu
+def test_lattice_of_a_demo_frame_is_bit_identical(dev, golden):
+    frames = golden("demo_frames_224.pt")["frames_u8"]
+    _gpu_lattice_equals_statement(dev, crf_image_ref(frames[:1])[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", [(64, 64), (40, 56), (97, 131)])
+def test_permutohedral_normalisers_and_one_iteration_messages(dev, H, W):
+    from wild_visual_navigation_amd import ops
+
+    K, KP = 5, 32
+    image = blocky_image(H, W, H + W)
+    logits = torch.randn(1, K, H, W, generator=g(H)) * 2
+    _, _, dbg = ops.dense_crf(logits.to(dev), image[None].to(dev), iterations=1, return_probs=True, _debug=True, method="permutohedral")
+    dbg = dbg[0].reshape(dbg.shape[1], H * W).double()
+    _, first = crf_lattice64(logits[0].double().to(dev), image.to(dev), 1, parts=True)
+    for row, n in ((2 * KP, first["n_b"]), (2 * KP + 1, first["n_g"])):
+        err = ((dbg[row] - n).abs() / n).max().item()
+        assert err <= 1e-5, err
+    for rows, lat, n, msg in ((slice(0, K), first["lb"], first["n_b"], first["msg_b"]), (slice(KP, KP + K), first["lg"], first["n_g"], first["msg_g"])):
+        scale = n * filter64(lat, n[:, None])[:, 0]          # the message of unit values
+        err = ((dbg[rows].T - msg).abs() / scale[:, None]).max().item()
+        assert err <= 1e-5, err
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [2, 27, 40, 64])
+def test_permutohedral_ten_iterations_against_fp64(dev, K):
+    from wild_visual_navigation_amd import ops
+
+    H, W = 40, 52
+    image = blocky_image(H, W, K)
+    logits = torch.randn(1, K, H, W, generator=g(K)) * 1.5
+    lab, Q = ops.dense_crf(logits.to(dev), image[None].to(dev), return_probs=True, method="permutohedral")
+    Q64 = crf_lattice64(logits[0].double().to(dev), image.to(dev))
+    err = (Q[0].double() - Q64).abs().max().item()
+    assert err <= 1e-4, err
+    top2 = Q64.topk(2, 0).values
+    bad = (lab[0].long() != Q64.argmax(0)) & (top2[0] - top2[1] >= 1e-4)
+    assert not bad.any(), int(bad.sum())
+
+
+@pytest.mark.gpu
+def test_permutohedral_is_deterministic_and_batch_independent(dev):
+    from wild_visual_navigation_amd import ops
+
+    B, H, W = 3, 37, 45
+    images = torch.stack([blocky_image(H, W, 30 + b) for b in range(B)]).to(dev)
+    la = (torch.randn(B, 7, H, W, generator=g(1)) * 2).to(dev)
+    lb = (torch.randn(B, 20, H, W, generator=g(2)) * 2).to(dev)
+    lab, Q = ops.dense_crf(la, images, return_probs=True, method="permutohedral")
+    lab_again, Q_again = ops.dense_crf(la, images, return_probs=True, method="permutohedral")
+    assert torch.equal(lab, lab_again) and torch.equal(Q, Q_again)
+    for b in range(B):
+        lb1, Qb = ops.dense_crf(la[b:b + 1], images[b:b + 1], return_probs=True, method="permutohedral")
+        assert torch.equal(lab[b:b + 1], lb1) and torch.equal(Q[b:b + 1], Qb)
+    lab2, Q2 = ops.dense_crf((la, lb), images, return_probs=True, method="permutohedral")
+    assert torch.equal(lab2[:, 0], lab) and torch.equal(Q2[:, :7], Q)
+    # wider than 32 columns in all (the 64-column layout): the first group is still bit-identical to its CRF alone
+    lc = (torch.randn(B, 30, H, W, generator=g(3)) * 2).to(dev)
+    lab3, Q3 = ops.dense_crf((la, lc), images, return_probs=True, method="permutohedral")
+    assert torch.equal(lab3[:, 0], lab) and torch.equal(Q3[:, :7], Q)
+    pm = la.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    assert torch.equal(ops.dense_crf(pm, images, method="permutohedral"), lab)
+
+
+@pytest.mark.gpu
+def test_permutohedral_crf_follows_the_colour_regions(dev):
+    from wild_visual_navigation_amd import ops
+
+    H, W = 48, 64
+    truth = torch.zeros(H, W, dtype=torch.long)
+    truth[:, W // 2:] = 1
+    truth[H // 3: 2 * H // 3, W // 4: W // 2] = 1
+    image = torch.where(truth[..., None] == 1, torch.tensor([200, 40, 60]), torch.tensor([30, 120, 220]))
+    image = (image + torch.randint(-3, 4, (H, W, 3), generator=g(3))).clamp(0, 255).to(torch.uint8)
+    logits = torch.stack([(truth == 0).float(), (truth == 1).float()]) * 0.6 + torch.randn(2, H, W, generator=g(4)) * 0.8
+    raw_acc = (logits.argmax(0) == truth).float().mean().item()
+    lab = ops.dense_crf(logits[None].to(dev), image[None].to(dev), method="permutohedral")[0].cpu().long()
+    acc = (lab == truth).float().mean().item()
+    assert raw_acc < 0.8 and acc > 0.99, (raw_acc, acc)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("branch", ["probe", "probe_wide", "kmeans"])
+def test_stego_interface_permutohedral_branches(dev, branch, monkeypatch):
+    from oracle import interfaces as OI, vit as OV
+    from wild_visual_navigation_amd import ops
+    from wild_visual_navigation_amd.feature_extractor.stego_interface import StegoInterface
+
+    S, seed = 64, 0
+    run_clustering = branch == "kmeans"
+    K_probe = 40 if branch == "probe_wide" else 12
+    sd = OV.make_vit_state_dict("vit_small", 8, pretrain_grid=28, seed=seed, depth=1)
+    head = OI.make_stego_head_state_dict(384, 90, seed=seed + 1)
+    gen = g(seed + 2)
+    probes = {"clusters": torch.randn(K_probe, 90, generator=gen), "linear.weight": torch.randn(27, 90, generator=gen) * 0.3,
+              "linear.bias": torch.randn(27, generator=gen) * 0.1}
+    si = StegoInterface(dev, input_size=S, n_image_clusters=5, run_clustering=run_clustering, run_crf=True, crf="permutohedral",
+                        backbone_weights=sd, head_weights=head, probe_weights=probes, precision="exact", flip_tta=False,
+                        cluster_resolution="pixel", allow_synthetic=True)
+    calls = []
+    real = ops.dense_crf
+
+    def record(logits, image, **kw):
+        assert kw.get("method") == "permutohedral"
+        keep = tuple(t.clone() for t in logits) if isinstance(logits, tuple) else logits.clone()
+        out = real(logits, image, **kw)
+        calls.append((keep, image.clone(), kw, out))
+        return out
+
+    monkeypatch.setattr(ops, "dense_crf", record)
+    img = torch.rand(2, 3, S, S, generator=g(21))
+    lin, clu = si.inference(img.to(dev))
+    monkeypatch.setattr(ops, "dense_crf", real)
+    assert len(calls) == (2 if branch == "probe_wide" else 1)
+    labs = []
+    for logits, image, kw, out in calls:
+        again = real(logits, image, **kw)
+        for x, y in zip(again if isinstance(again, tuple) else (again,), out if isinstance(out, tuple) else (out,)):
+            assert torch.equal(x, y)
+        lab = again[0] if kw.get("relabel_last") else again
+        labs += [lab[:, 0], lab[:, 1]] if lab.dim() == 4 else [lab]
+    lab_lin, lab_clu = labs[0], labs[-1]
+    assert torch.equal(lin[0], lab_lin) and torch.equal(clu[0], lab_clu)
+    if run_clustering:
+        for b in range(2):
+            ids = torch.unique(clu[0, b])
+            assert int(si._n_segments[b]) == ids.numel() and torch.equal(ids.cpu(), torch.arange(ids.numel(), dtype=ids.dtype))
+
+
+@pytest.mark.gpu
+def test_feature_extractor_stego_with_permutohedral_crf(dev):
+    from oracle import interfaces as OI, vit as OV
+    from wild_visual_navigation_amd.feature_extractor import FeatureExtractor
+
+    S = 64
+    sd = OV.make_vit_state_dict("vit_small", 8, pretrain_grid=28, seed=3, depth=1)
+    head = OI.make_stego_head_state_dict(384, 90, seed=4)
+    fe = FeatureExtractor(dev, segmentation_type="stego", feature_type="stego", input_size=S, run_crf=True, crf="permutohedral",
+                          pretrained_weights=sd, head_weights=head, n_image_clusters=6, precision="exact", flip_tta=False, allow_synthetic=True)
+    img = torch.rand(1, 3, S, S, generator=g(8)).to(dev)
+    edges, feat, seg, center, _ = fe.extract(img)
+    ids = torch.unique(seg)
+    assert torch.equal(ids.cpu(), torch.arange(ids.numel(), dtype=ids.dtype))
+    assert feat.shape == (ids.numel(), 90) and torch.isfinite(feat).all()
+
+
+@pytest.mark.gpu
+def test_permutohedral_agrees_with_the_exact_crf_on_most_pixels(dev):
+    """The lattice approximates the exact kernels: on a blocky frame the two CRFs' labels agree on most pixels (measured in DESIGN)."""
+    from wild_visual_navigation_amd import ops
+
+    H, W, K = 64, 80, 6
+    image = blocky_image(H, W, 77)[None].to(dev)
+    logits = (torch.randn(1, K, H, W, generator=g(77)) * 1.5).to(dev)
+    a = ops.dense_crf(logits, image)
+    b = ops.dense_crf(logits, image, method="permutohedral")
+    agree = (a == b).float().mean().item()
+    print(f"label agreement exact vs permutohedral: {agree:.4f}")
+    assert agree >= 0.9, agree

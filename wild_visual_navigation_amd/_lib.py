@@ -197,6 +197,9 @@ _SIGNATURES = {
     "wvn_dense_crf_workspace_bytes": ([_i, _i, _i, _i], _sz),
     "wvn_dense_crf": ([_p, _i, _ll, _ll, _ll, _p, _i, _ll, _ll, _ll, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
     "wvn_crf_image": ([_p, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p], _i),
+    "wvn_dense_crf_permutohedral_workspace_bytes": ([_i, _i, _i, _i], _sz),
+    "wvn_dense_crf_permutohedral": ([_p, _i, _ll, _ll, _ll, _p, _i, _ll, _ll, _ll, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
+    "wvn_debug_permutohedral_lattice": ([_p, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p, _sz, _p], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

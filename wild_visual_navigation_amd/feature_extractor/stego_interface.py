@@ -8,7 +8,8 @@ deterministic per-image cosine k-means for ``run_clustering=True``.  ``model_pat
 either the upstream STEGO (``net.model.* / net.cluster1.* / cluster_probe.clusters / linear_probe.*``) or the
 self_supervised_segmentation (``backbone.* / segmentation_head.*``) key layout is loaded (``load_stego_checkpoint``); without
 one, seeded synthetic weights are used and a warning says so.  ``run_crf=True`` -- the reference constructor's own default -- runs
-the exact dense CRF on HIP with ``crf="exact"`` (``ops.dense_crf``); without it, it raises unless the caller opts in to running WITHOUT
+the exact dense CRF on HIP with ``crf="exact"`` (``ops.dense_crf``), or pydensecrf's own permutohedral-lattice algorithm with
+``crf="permutohedral"``; without it, it raises unless the caller opts in to running WITHOUT
 the CRF refinement (``skip_crf=True`` or the environment variable ``WVN_SKIP_CRF=1``), in which case a warning says that the CRF
 step was dropped.
 
@@ -124,7 +125,8 @@ class StegoInterface:
         fuse_proj: bool = True,
         skip_crf: Optional[bool] = None,  # run_crf=True without pydensecrf: None -> WVN_SKIP_CRF env, True -> warn and drop the CRF step
         pos_embed_rule: str = "dino",   # position-table resampling of the backbone (backbone.resample_pos_embed)
-        crf: Optional[str] = None,       # with run_crf=True: "exact" = the mean-field dense CRF with every pixel pair (ops.dense_crf, csrc/dense_crf.hip)
+        crf: Optional[str] = None,       # with run_crf=True: "exact" = the mean-field dense CRF with every pixel pair (ops.dense_crf, csrc/dense_crf.hip);
+        #                                  "permutohedral" = the same CRF on pydensecrf's lattice filter (csrc/dense_crf_permutohedral.hip)
         code_align_corners: bool = True,   # how postprocess() up-samples the code BEFORE clustering / probing (the absent package's choice, stego_interface.py:94-100):
         #                                    True = the align_corners=True taps of WVN's own later up-sample (:107); False = the half-pixel taps of the public STEGO
         #                                    evaluation code.  `features` (stego_interface.py:107) and the pooling are WVN's own code: always align_corners=True
@@ -134,17 +136,18 @@ class StegoInterface:
                              run_clustering=run_clustering, n_image_clusters=n_image_clusters)
         else:
             self._cfg = _Cfg(cfg)
-        if crf not in (None, "exact"):
-            raise _lib.WvnError(f"crf must be None or 'exact', not {crf!r}")
-        self._crf = bool(self._cfg.run_crf) and crf == "exact"
+        if crf not in (None, "exact", "permutohedral"):
+            raise _lib.WvnError(f"crf must be None, 'exact' or 'permutohedral', not {crf!r}")
+        self._crf = bool(self._cfg.run_crf) and crf is not None
+        self._crf_method = crf
         if self._crf:
-            # the exact dense CRF on the input_size x input_size frame, before the nearest resample to the camera height (DESIGN.md "Dense CRF")
+            # the dense CRF on the input_size x input_size frame, before the nearest resample to the camera height (DESIGN.md "Dense CRF")
             if skip_crf:
-                raise _lib.WvnError("crf='exact' runs the CRF refinement; it cannot be combined with skip_crf=True")
+                raise _lib.WvnError(f"crf={crf!r} runs the CRF refinement; it cannot be combined with skip_crf=True")
             if cluster_resolution != "pixel":
-                raise _lib.WvnError("crf='exact' refines pixel-resolution maps: it needs cluster_resolution='pixel'")
+                raise _lib.WvnError(f"crf={crf!r} refines pixel-resolution maps: it needs cluster_resolution='pixel'")
             if not code_align_corners:
-                raise _lib.WvnError("crf='exact' builds its pixel logits with the align_corners=True up-sample; code_align_corners=False has no "
+                raise _lib.WvnError(f"crf={crf!r} builds its pixel logits with the align_corners=True up-sample; code_align_corners=False has no "
                                     "dense half-pixel up-sample to feed it")
         elif self._cfg.run_crf:
             import os
@@ -152,7 +155,7 @@ class StegoInterface:
             if skip_crf is None:
                 skip_crf = os.environ.get("WVN_SKIP_CRF", "0") not in ("", "0")
             if not skip_crf:
-                raise _lib.WvnError("run_crf=True needs pydensecrf (CPU, external) unless crf='exact' selects the HIP dense CRF; FeatureExtractor "
+                raise _lib.WvnError("run_crf=True needs pydensecrf (CPU, external) unless crf='exact' or 'permutohedral' selects the HIP dense CRF; FeatureExtractor "
                                     "uses run_crf=False.  Pass skip_crf=True (or set WVN_SKIP_CRF=1) to run the segmentation without the CRF refinement")
             warnings.warn("StegoInterface: run_crf=True but the dense CRF (pydensecrf, CPU) is not part of the MI355X path -- the "
                           "cluster / linear predictions are returned WITHOUT CRF refinement (skip_crf)", stacklevel=2)
@@ -392,7 +395,7 @@ class StegoInterface:
         return self._linear_pred, self._cluster_pred
 
     def _inference_crf(self, img: torch.Tensor, code: torch.Tensor):
-        """``inference`` with ``crf='exact'`` (stego_interface.py:94-100): both maps refined by the dense CRF on the input_size x input_size
+        """``inference`` with ``crf='exact'`` or ``'permutohedral'`` (stego_interface.py:94-100): both maps refined by the dense CRF on the input_size x input_size
         frame, then nearest-resampled to the camera height.  CRF logits per branch (readings, DESIGN.md "Dense CRF"): the linear probe's
         patch logits bilinearly up-sampled (align_corners=True); the cluster probe / the per-image k-means: 2 * cos(code pixel, centroid)
         (STEGO's cluster_probe(code, 2, log_probs=True)) with the code pixels the up-sampled code and, for k-means, the final per-image
@@ -419,13 +422,14 @@ class StegoInterface:
             sim = ops.gemm_f32(pixn, self._clusters * 2.0, None).reshape(B, S * S, K)
         clu = sim.reshape(B, S, S, K).permute(0, 3, 1, 2)                     # [B, K, S, S] view (pixel stride K)
         relabel = bool(self._cfg.run_clustering)
+        method = self._crf_method
         if lin is not None and lin.shape[1] + K <= 64:
-            out = ops.dense_crf((lin, clu), image, relabel_last=relabel)
+            out = ops.dense_crf((lin, clu), image, relabel_last=relabel, method=method)
             labels, nseg = out if relabel else (out, None)
             lab_lin, lab_clu = labels[:, 0], labels[:, 1]
         else:
-            lab_lin = ops.dense_crf(lin, image) if lin is not None else None
-            out = ops.dense_crf(clu, image, relabel_last=relabel)
+            lab_lin = ops.dense_crf(lin, image, method=method) if lin is not None else None
+            out = ops.dense_crf(clu, image, relabel_last=relabel, method=method)
             lab_clu, nseg = (out[0], out[1]) if relabel else (out, None)
         self._n_segments = nseg
         lab_clu = lab_clu.contiguous()

@@ -460,13 +460,18 @@ def crf_image(frame: torch.Tensor, size: Optional[int] = None) -> torch.Tensor:
 
 def dense_crf(logits, image_u8: torch.Tensor, iterations: int = 10, pos_w: float = 3.0, pos_xy_std: float = 1.0, bi_w: float = 4.0,
               bi_xy_std: float = 67.0, bi_rgb_std: float = 3.0, return_probs: bool = False, relabel_last: bool = False,
-              _debug: bool = False):
-    """Exact mean-field dense CRF (csrc/dense_crf.hip; DESIGN.md "Dense CRF"): logits [B,K,H,W] fp32 (K <= 64; any strides with the
+              _debug: bool = False, method: str = "exact"):
+    """Mean-field dense CRF.  ``method="exact"`` (default): every pixel pair (csrc/dense_crf.hip; DESIGN.md "Dense CRF");
+    ``"permutohedral"``: both kernel sums by the permutohedral-lattice filter pydensecrf runs (csrc/dense_crf_permutohedral.hip;
+    DESIGN.md "Permutohedral dense CRF"), same arguments and returns.  logits [B,K,H,W] fp32 (K <= 64; any strides with the
     pixel dimensions dense, e.g. a permuted [B,H,W,K] view), image_u8 [B,H,W,3] -> labels int32 [B,H,W] (first maximum of Q^T), plus
     Q fp32 [B,K,H,W] when ``return_probs``.  ``logits`` may also be a tuple of two such tensors (K1 + K2 <= 64): two CRFs on the same
     image in one pass (shared exponentials), labels [B,2,H,W] and Q [B,K1+K2,H,W].  ``relabel_last``: the last group's labels are
     compacted to ascending contiguous ids (the k-means relabel rule) and their count per frame int32 [B] is returned after the labels.  ``_debug`` (tests): also returns the last
     iteration's messages and normalisers [B, 2 KP + 2, H, W] (include/wvn_hip.h)."""
+    if method not in ("exact", "permutohedral"):
+        raise _lib.WvnError(f"dense_crf: method must be 'exact' or 'permutohedral', not {method!r}")
+    perm = method == "permutohedral"
     pair = isinstance(logits, (tuple, list))
     ls = list(logits) if pair else [logits]
     if len(ls) not in (1, 2):
@@ -496,15 +501,16 @@ def dense_crf(logits, image_u8: torch.Tensor, iterations: int = 10, pos_w: float
     KP = 32 if KT <= 32 else 64
     dbg = torch.zeros(B, 2 * KP + 2, H, W, dtype=torch.float32, device=dev) if _debug else None
     nseg = torch.empty(B, dtype=torch.int32, device=dev) if relabel_last else None
-    nbytes = lib().wvn_dense_crf_workspace_bytes(B, H, W, KT)
+    name = "wvn_dense_crf_permutohedral" if perm else "wvn_dense_crf"
+    nbytes = getattr(lib(), name + "_workspace_bytes")(B, H, W, KT)
     if nbytes == 0:
         raise _lib.WvnError(f"dense_crf: unsupported shape B={B}, H={H}, W={W}, K={KT}")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     t1, _, b1, c1, p1 = desc[0]
     t2, _, b2, c2, p2 = desc[1] if pair else (None, 0, 0, 0, 0)
-    check(lib().wvn_dense_crf(ptr(t1), K1, b1, c1, p1, ptr(t2), K2, b2, c2, p2, ptr(image_u8), B, H, W, int(iterations), float(pos_w),
-                              float(pos_xy_std), float(bi_w), float(bi_xy_std), float(bi_rgb_std), ptr(labels), ptr(nseg), ptr(probs), ptr(dbg),
-                              ptr(ws), nbytes, stream()), "wvn_dense_crf")
+    check(getattr(lib(), name)(ptr(t1), K1, b1, c1, p1, ptr(t2), K2, b2, c2, p2, ptr(image_u8), B, H, W, int(iterations), float(pos_w),
+                               float(pos_xy_std), float(bi_w), float(bi_xy_std), float(bi_rgb_std), ptr(labels), ptr(nseg), ptr(probs),
+                               ptr(dbg), ptr(ws), nbytes, stream()), name)
     out = (labels if pair else labels[:, 0],)
     if relabel_last:
         out += (nseg,)
@@ -513,6 +519,32 @@ def dense_crf(logits, image_u8: torch.Tensor, iterations: int = 10, pos_w: float
     if _debug:
         out += (dbg,)
     return out[0] if len(out) == 1 else out
+
+
+def _permutohedral_lattice(image_u8: torch.Tensor, bilateral: bool, xy_std: float, rgb_std: float = 1.0) -> list:
+    """Tests: the lattice ``dense_crf(method="permutohedral")`` builds for one kernel of every frame of image_u8 [B,H,W,3]
+    (include/wvn_hip.h wvn_debug_permutohedral_lattice).  Per frame a dict of CPU tensors: M, keys int32 [M, d] (ascending),
+    bary fp32 [H W, d + 1], vert int32 [H W, d + 1] (table rows 1..M), nbr int32 [d + 1, M, 2] (rows, 0 = absent)."""
+    require_cuda(image_u8, "image_u8")
+    image_u8 = image_u8.contiguous()
+    B, H, W, _ = image_u8.shape
+    d = 5 if bilateral else 2
+    E, dev = H * W * (d + 1), image_u8.device
+    M = torch.empty(B, dtype=torch.int32, device=dev)
+    keys = torch.empty(B, E, d, dtype=torch.int32, device=dev)
+    bary = torch.empty(B, E, dtype=torch.float32, device=dev)
+    vert = torch.empty(B, E, dtype=torch.int32, device=dev)
+    nbr = torch.empty(B, d + 1, E, 2, dtype=torch.int32, device=dev)
+    nbytes = lib().wvn_dense_crf_permutohedral_workspace_bytes(B, H, W, 1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(lib().wvn_debug_permutohedral_lattice(ptr(image_u8), B, H, W, int(bilateral), float(xy_std), float(rgb_std), ptr(M), ptr(keys),
+                                                ptr(bary), ptr(vert), ptr(nbr), ptr(ws), nbytes, stream()), "wvn_debug_permutohedral_lattice")
+    out = []
+    for b in range(B):
+        m = int(M[b])
+        out.append(dict(M=m, keys=keys[b, :m].cpu(), bary=bary[b].reshape(H * W, d + 1).cpu(), vert=vert[b].reshape(H * W, d + 1).cpu(),
+                        nbr=nbr[b, :, :m].cpu()))
+    return out
 
 
 def gemm_f32(a, b, bias=None, epi=_lib.F32_NONE, trans_a=False, trans_b=True, out=None, mask=None):
