@@ -55,7 +55,7 @@ int wvn_version(void);
  * ------------------------------------------------------------------------------------------- */
 /* wvn_vit_model.flags: which single-kernel forms of the block stages wvn_vit_forward MAY use (WVN_PREC_BF16, D = 384).  They are
  * persistent one-workgroup-per-CU kernels and pay off once the token matrix fills the chip; below that (a single live frame)
- * wvn_vit_forward runs the separate LayerNorm / GEMM kernels whatever the flags say (thresholds: csrc/api.hip).
+ * wvn_vit_forward runs the separate LayerNorm / GEMM kernels whatever the flags say (thresholds: csrc/vit_forward.hip).
  * WVN_VIT_MLP_FUSED (F % 64 == 0): every layer also carries fc2_w_fused = fc2.weight with the hidden (input) index permuted --
  * bits 2 and 3 swapped inside each aligned group of 16, fc2_w_fused[n][k] = fc2.weight[n][swap23(k)] -- and the block MLP,
  * including its LayerNorm (blocks.i.norm2), runs as ONE kernel that keeps the normalised rows and the hidden activation in

@@ -63,7 +63,7 @@ def test_fused_block_kernels_agree_with_separate_kernels(dev, S, B, fuse_mlp, fu
     img = torch.rand(B, 3, S, S, generator=g(7))
     want = OV.vit_tokens(sd, OI.normalize(img), 8, 6)[:, 1:]
     default = VitBackbone(sd, S, 8, 6, device=dev, precision="bf16")
-    assert default.fuse_mlp and default.fuse_qkv          # allowed; used from about half a chip of row blocks on (csrc/api.hip)
+    assert default.fuse_mlp and default.fuse_qkv          # allowed; used from about half a chip of row blocks on (csrc/vit_forward.hip)
     fused = VitBackbone(sd, S, 8, 6, device=dev, precision="bf16", fuse_mlp=True, fuse_qkv=True)   # explicit True: at every size
     a = fused.forward_tokens(img.to(dev)).cpu()
     if not (fuse_mlp or fuse_qkv):   # at these sizes the default takes the separate kernels: bit-identical to asking for them

@@ -8,7 +8,7 @@
 //                         LayerNorm outputs, q / k / v, GELU outputs and softmax probabilities (<= 2^12 under the lazy running
 //                         max, attention_bf16.hip) are O(1..1e3), and all accumulation, residuals and statistics stay fp32.
 // Every source that includes this header is compiled twice by csrc/build.py (the second time with -DWVN_OPERAND_F16=1); its
-// launchers are named through WVN_OPSYM so that both sets link into one library and api.hip picks by precision.  Storage in
+// launchers are named through WVN_OPSYM so that both sets link into one library and vit_forward.hip picks by precision.  Storage in
 // HBM / LDS is raw 16-bit words (op16_t) in both cases.
 #pragma once
 #include "common.h"

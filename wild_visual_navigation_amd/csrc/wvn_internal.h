@@ -1,4 +1,5 @@
-// Internal (C++) launcher interfaces shared between the .hip translation units and api.hip.
+// Internal (C++) launcher interfaces shared between the .hip translation units, api.hip (the C entry points) and
+// vit_forward.hip (the kernel routing of the ViT forward).
 // The public, C-ABI surface is include/wvn_hip.h.
 #pragma once
 #include "common.h"
@@ -99,6 +100,21 @@ int wvn_gemm_n384_mx_launch(const GemmBf16Params& p, int epi, hipStream_t st);
 // the MX form of the A-stationary kernel (LayerNorm on load; EPI_GELU_FRAG -> MX fragment planes, EPI_QKV -> fp16 q | k | v^T); W packed by backbone.pack_a384_mx
 int wvn_gemm_a384_mx_launch(const GemmBf16Params& p, int epi, hipStream_t st);
 
+// Descriptor builders of the split-operand / MX block kernels (vit_forward.hip): one per kernel, used by the forward and by the
+// stand-alone wvn_debug_* entries, which pass the planes the forward does not (dbg, A_h8, C_h8).
+// A-stationary K = 384 kernels (gemm_a384_x3 and its MX form).  A == nullptr: the A operand comes from wvn_desc_ln_on_load;
+// W_lo == nullptr: the two planes (MX: the two images) of W are stacked, the second N * 384 elements behind the first
+GemmBf16Params wvn_desc_a384(const void* A, const void* A_lo, int lda, const void* W, const void* W_lo, const float* bias, void* C, void* C_lo,
+                             int ldc, int M, int N, long long* dbg = nullptr, void* C_h8 = nullptr);
+// ... A = LayerNorm(x) formed on load from the row statistics {mean, rstd}
+void wvn_desc_ln_on_load(GemmBf16Params& p, const float* x, int ldx, const float* stats, const float* g, const float* b);
+// row-panel N = 384 residual updates (gemm_n384_x3: row-major, fragment and MX forms); ln_stats_out: leave {mean, rstd} of the updated rows
+GemmBf16Params wvn_desc_n384(const void* A, const void* A_lo, int lda, const void* W, const void* W_lo, const float* bias, const float* ls, float* C,
+                             int ldc, int M, int K, float* ln_stats_out = nullptr, long long* dbg = nullptr, const void* A_h8 = nullptr);
+// the EPI_QKV fields: q | k [B,h,npad,64], v^T [B,h,64,npad]; *_lo and qkv_f16 as in GemmBf16Params
+void wvn_desc_qkv_epilogue(GemmBf16Params& p, void* q, void* k, void* vt, int heads, int npad, int ntok, int ntok_s, float q_scale, int qkv_f16 = 0,
+                           void* q_lo = nullptr, void* k_lo = nullptr, void* vt_lo = nullptr);
+
 // ---- fp8 (e4m3) MFMA GEMM with per-row scales of both operands (gemm_fp8.hip) + the row quantisers (fp8.hip) -----------
 struct GemmFp8Params {
   const unsigned char* A; int lda;   // [M,K] e4m3, lda in elements (= bytes)
@@ -175,6 +191,13 @@ int wvn_layernorm_launch(const float* x, const float* gamma, const float* beta, 
                          float* y2, int ldy2, int rows_out, int D, float eps, int drop_cls, int ntok,
                          int ntok_s, hipStream_t st, void* y_lo = nullptr);  // y_lo: exact mode, lo plane of the bf16 output
 int wvn_cast_f32_bf16_launch(const float* src, int lds_, bf16_t* dst, int ldd, int rows, int cols, hipStream_t st, int f16 = 0);
+
+// ---- the ViT forward (vit_forward.hip) behind wvn_vit_forward* / wvn_vit_workspace_bytes (api.hip) -------------------
+struct wvn_vit_model;
+size_t wvn_vit_workspace_bytes_impl(const wvn_vit_model* m, int batch);
+// img_u8: raw uint8 pixels; ing: optional NEAREST resize + crop tables; cols_mirror: see vit_forward.hip
+int wvn_vit_forward_impl(const wvn_vit_model* m, const void* img, int img_u8, const WvnIngest* ing, int batch, float* tokens_f32, void* tokens_lowp,
+                         int ld_lowp, void* workspace, size_t workspace_bytes, void* stream, const int* cols_mirror = nullptr);
 
 // ---- attention (attention_bf16.hip / attention_f32.hip) ---------------------------------------
 int wvn_attention_f32_launch(const float* q, const float* k, const float* v, float* out, int B, int heads, int ntok,
