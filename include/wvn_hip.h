@@ -385,12 +385,38 @@ int wvn_project_render_fmin(const wvn_render_node* nodes_dev, int n, const float
  * SLIC superpixels (FeatureExtractor default segmentation_type, feature_extractor.py:84-90,221-225: fast_slic on the CPU in
  * the reference).  Integer-arithmetic SLIC (csrc/slic.hip): img [3][H][W] uint8 or float in [0,1]; labels [H][W] int32 in
  * [0, wvn_slic_num_clusters()).  lut_lin [256], lut_f [4096]: sRGB->linear and CIELAB f(t) tables (device, int32; built by the
- * caller in double precision: wild_visual_navigation_amd/ops.py slic_tables).  Parity with fast_slic is unpinned.
+ * caller in double precision: wild_visual_navigation_amd/ops.py slic_tables).  Parity with fast_slic is unpinned.  The map is the
+ * k-means result; fast_slic's connectivity post-pass is the separate, opt-in wvn_slic_connectivity below.
  * ------------------------------------------------------------------------------------------- */
 int wvn_slic_num_clusters(int H, int W, int num_components);
 size_t wvn_slic_scratch_bytes(int H, int W, int num_components);
 int wvn_slic(const void* img, int img_is_u8, int H, int W, int num_components, float compactness, int iters, const int* lut_lin,
              const int* lut_f, int* labels, void* scratch, size_t scratch_bytes, void* stream);
+/* Connectivity enforcement (csrc/slic_connectivity.hip): the post-processing step of SLIC (Achanta et al. 2012; fast_slic's Slic(...)
+ * does it by default) as an opt-in pass over [B][H][W] int32 label maps with ids in [0, K) -- SLIC's or any other.  The definition the
+ * kernels are held to, bit for bit (tests/slic_connectivity_ref.py):
+ *   1. A component is a maximal 4-connected set of pixels with equal label; its size is its pixel count.
+ *   2. A component is anchored if its size is >= min_size.  If no component is anchored, the output is the input.
+ *   3. Round: all decisions read the state at the start of the round.  For every component C that is not yet anchored, take all
+ *      pairs (p, q) with p in C, q a 4-neighbour of p inside the frame, q anchored.  No such pair: C waits.  Otherwise count the pairs
+ *      per current label of q; C takes the label with the highest count, the lowest id on a tie; all its pixels are anchored from
+ *      the next round on.
+ *   4. Rounds repeat until every pixel is anchored.
+ * The result is a pure function of (labels, min_size): no dependence on launch geometry, on the order of atomics or on the batch
+ * position.  Ids stay in [0, K): an id that lost all its pixels behaves as an empty id does.  This is an order-independent form of
+ * Achanta's sequential scan; PARITY WITH fast_slic's OWN POST-PASS IS UNPINNED (the package is absent, as for the SLIC itself).
+ * min_size: the caller's integer (ops.py: max(1, int(0.25 * H * W / K)), fast_slic's default factor).  labels_out may be labels_in.
+ * The launch sequence contains no host read: WVN_SLIC_CC_PAR_ROUNDS rounds run one wave per waiting component across the GPU, then one
+ * workgroup per image runs rounds until the image's counter of waiting components is zero.  That counter is the int32 at
+ * scratch + 16 * b for image b: zero after the call (in stream order) whatever the input.  K is validated (>= 1) and otherwise unused:
+ * labels are only ever compared.  WVN_ERR_ARG: null pointer, B / H / W / K / min_size < 1, B * H * W >= 2^29, short scratch.
+ * The component labelling works on WVN_SLIC_CC_TILE_H x WVN_SLIC_CC_TILE_W tiles in LDS, merged across tile borders. */
+#define WVN_SLIC_CC_TILE_W 32
+#define WVN_SLIC_CC_TILE_H 8
+#define WVN_SLIC_CC_PAR_ROUNDS 8
+size_t wvn_slic_connectivity_scratch_bytes(int B, int H, int W, int K);
+int wvn_slic_connectivity(const int* labels_in, int* labels_out, int B, int H, int W, int K, int min_size, void* scratch,
+                          size_t scratch_bytes, void* stream);
 /* SegmentExtractor.centers (segment_extractor.py:70-92): centers [S,2] fp32 (x,y). scratch: 3*S u64. */
 int wvn_seg_centers(const int* seg, float* centers, void* scratch, int H, int W, int S, void* stream);
 /* SegmentExtractor.adjacency_list (segment_extractor.py:39-67): edges [max_edges,2] int64 sorted by

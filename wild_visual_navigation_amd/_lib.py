@@ -148,6 +148,8 @@ _SIGNATURES = {
     "wvn_slic_num_clusters": ([_i, _i, _i], _i),
     "wvn_slic_scratch_bytes": ([_i, _i, _i], _sz),
     "wvn_slic": ([_p, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _sz, _p], _i),
+    "wvn_slic_connectivity_scratch_bytes": ([_i, _i, _i, _i], _sz),
+    "wvn_slic_connectivity": ([_p, _p, _i, _i, _i, _i, _i, _p, _sz, _p], _i),
     "wvn_seg_centers": ([_p, _p, _p, _i, _i, _i, _p], _i),
     "wvn_seg_adjacency": ([_p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "wvn_normalize_rows": ([_p, _i, _p, _i, _i, _p], _i),

@@ -379,6 +379,11 @@ int wvn_slic(const void* img, int img_is_u8, int H, int W, int num_components, f
   return wvn_slic_launch(img, img_is_u8, H, W, num_components, compactness, iters, lut_lin, lut_f, labels, scratch, scratch_bytes,
                          (hipStream_t)stream);
 }
+size_t wvn_slic_connectivity_scratch_bytes(int B, int H, int W, int K) { return wvn_slic_connectivity_scratch_bytes_impl(B, H, W, K); }
+int wvn_slic_connectivity(const int* labels_in, int* labels_out, int B, int H, int W, int K, int min_size, void* scratch,
+                          size_t scratch_bytes, void* stream) {
+  return wvn_slic_connectivity_launch(labels_in, labels_out, B, H, W, K, min_size, scratch, scratch_bytes, (hipStream_t)stream);
+}
 int wvn_seg_centers(const int* seg, float* centers, void* scratch, int H, int W, int S, void* stream) {
   return wvn_centers_launch(seg, centers, (unsigned long long*)scratch, H, W, S, (hipStream_t)stream);
 }

@@ -9,8 +9,10 @@
 //   * distances in 64-bit integers, ties to the lowest cluster id;
 //   * centre updates from 64-bit integer sums (atomics; integer addition is order-independent), rounded integer division.
 // oracle/slic.py restates the same integer arithmetic in numpy; labels must match bit for bit.  Like fast_slic's output the map
-// holds ids in [0, number of clusters); connectivity enforcement (fast_slic's post-pass that re-assigns stray islands) is not
-// performed -- ids without pixels give NaN feature rows exactly as an empty id does in the reference (feature_extractor.py:394).
+// holds ids in [0, number of clusters).  Connectivity enforcement (fast_slic's post-pass that re-assigns stray islands; the last step
+// of the published algorithm) is a separate, opt-in pass over this map: csrc/slic_connectivity.hip (ops.slic(enforce_connectivity=True),
+// FeatureExtractor(slic_enforce_connectivity=True)); its parity with fast_slic's own post-pass is unpinned too.  Ids without pixels
+// give NaN feature rows exactly as an empty id does in the reference (feature_extractor.py:394).
 #include "common.h"
 #include "wvn_internal.h"
 

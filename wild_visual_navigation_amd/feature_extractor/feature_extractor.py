@@ -68,6 +68,10 @@ class FeatureExtractor:
             # the GPU in integer arithmetic (csrc/slic.hip; parity with fast_slic's own variant is unpinned)
             self._slic_num_components = kwargs.get("slic_num_components", 100)
             self._slic_compactness = kwargs.get("slic_compactness", 10)
+            # fast_slic's Slic(...) enforces connectivity by default; here it is an opt-in pass after the k-means (csrc/slic_connectivity.hip):
+            # off, the labels are the k-means result as before
+            self._slic_enforce_connectivity = bool(kwargs.get("slic_enforce_connectivity", False))
+            self._slic_min_size_factor = float(kwargs.get("slic_min_size_factor", 0.25))
         elif self.segmentation_type == "stego" and self._feature_type != "stego":
             raise TypeError("segmentation_type 'stego' requires feature_type 'stego' (as in the reference)")
 
@@ -135,7 +139,9 @@ class FeatureExtractor:
                       **kwargs) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Batched hot path (no graph structure): img [B,3,H,H] -> (feat [B,S,D], seg [B,H,H] int32,
         n_segments [B] int32).  Rows of ids that do not occur in an image are NaN (the reference's empty
-        mean).  Supported segmentations: grid, stego.  ``backbone_out``: the tokens ``backbone_stage(img)`` returned."""
+        mean).  Supported segmentations: grid, slic, stego.  SLIC with ``slic_enforce_connectivity=True`` adds one batched
+        connectivity pass over the B maps (ops.slic_enforce_connectivity: fragments below slic_min_size_factor of a superpixel go to a
+        neighbour; ids stay cluster ids, emptied ids give NaN rows); the pass has no host synchronisation.  ``backbone_out``: the tokens ``backbone_stage(img)`` returned."""
         img = img.to(self._device)
         B, _, H, W = img.shape
         G = self._grid()
@@ -161,7 +167,8 @@ class FeatureExtractor:
             tokens = self._extractor.feature_tokens
             labels_patch = self._extractor._labels_patch
         elif self._segmentation_type == "slic":
-            seg = torch.stack([ops.slic(img[b], self._slic_num_components, self._slic_compactness) for b in range(B)])
+            seg = ops.slic(img, self._slic_num_components, self._slic_compactness, enforce_connectivity=self._slic_enforce_connectivity,
+                           min_size_factor=self._slic_min_size_factor)   # (the enforcement is one batched call)
             n_seg = ops.slic_num_clusters(H, W, self._slic_num_components)
             nseg = torch.full((B,), n_seg, dtype=torch.int32, device=self._device)
             tokens = backbone_out if backbone_out is not None else self._feature_tokens(img)
@@ -284,8 +291,10 @@ class FeatureExtractor:
 
     def segment_slic(self, img, **kwargs):
         """feature_extractor.py:221-225 without the host round trip: [1,3,H,W] (float in [0,1], truncated to 8 bits like the
-        reference's np.uint8(img * 255), or uint8) -> [1,1,H,W] int64 ids in [0, number of SLIC clusters)."""
-        seg = ops.slic(img[0].to(self._device), self._slic_num_components, self._slic_compactness)
+        reference's np.uint8(img * 255), or uint8) -> [1,1,H,W] int64 ids in [0, number of SLIC clusters); with
+        ``slic_enforce_connectivity=True`` after the connectivity pass (fast_slic's default post-processing)."""
+        seg = ops.slic(img[0].to(self._device), self._slic_num_components, self._slic_compactness,
+                       enforce_connectivity=self._slic_enforce_connectivity, min_size_factor=self._slic_min_size_factor)
         return seg[None, None].to(torch.long)
 
     def segment_random(self, img, **kwargs):

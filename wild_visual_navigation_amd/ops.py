@@ -210,18 +210,68 @@ def slic_tables(device):
     return _SLIC_TABLES[key]
 
 
-def slic(img: torch.Tensor, num_components: int = 100, compactness: float = 10.0, iters: int = 10) -> torch.Tensor:
-    """img [3,H,W] uint8 or float in [0,1] (CUDA) -> SLIC label map [H,W] int32 in [0, slic_num_clusters)."""
+def slic(img: torch.Tensor, num_components: int = 100, compactness: float = 10.0, iters: int = 10,
+         enforce_connectivity: bool = False, min_size_factor: float = 0.25) -> torch.Tensor:
+    """img [3,H,W] uint8 or float in [0,1] (CUDA) -> SLIC label map [H,W] int32 in [0, slic_num_clusters); [B,3,H,W] -> [B,H,W].
+    ``enforce_connectivity``: the post-processing step of SLIC (fast_slic's default) as ONE batched pass over the B maps
+    (``slic_enforce_connectivity`` with min_size = max(1, int(min_size_factor * H * W / slic_num_clusters))); off by default, and
+    then the labels are the k-means result exactly as before."""
     require_cuda(img, "img")
+    if img.dim() not in (3, 4) or img.shape[-3] != 3:
+        raise _lib.WvnError(f"slic: img must be [3,H,W] or [B,3,H,W], not {tuple(img.shape)}")
     u8 = img.dtype == torch.uint8
     img = img.contiguous() if u8 else img.contiguous().float()
-    _, H, W = img.shape
+    single = img.dim() == 3
+    frames = img[None] if single else img
+    B, _, H, W = frames.shape
     lin, f = slic_tables(img.device)
-    labels = torch.empty(H, W, dtype=torch.int32, device=img.device)
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=img.device)
     scratch = torch.empty(lib().wvn_slic_scratch_bytes(H, W, num_components), dtype=torch.uint8, device=img.device)
-    check(lib().wvn_slic(ptr(img), int(u8), H, W, num_components, float(compactness), iters, ptr(lin), ptr(f), ptr(labels),
-                         ptr(scratch), scratch.numel(), stream()), "wvn_slic")
-    return labels
+    for b in range(B):   # (launches only: the frames share the scratch buffer in stream order)
+        check(lib().wvn_slic(ptr(frames[b]), int(u8), H, W, num_components, float(compactness), iters, ptr(lin), ptr(f), ptr(labels[b]),
+                             ptr(scratch), scratch.numel(), stream()), "wvn_slic")
+    if enforce_connectivity:
+        K = slic_num_clusters(H, W, num_components)
+        slic_enforce_connectivity(labels, K, slic_min_size(H, W, K, min_size_factor), out=labels)
+    return labels[0] if single else labels
+
+
+def slic_min_size(H: int, W: int, n_clusters: int, min_size_factor: float = 0.25) -> int:
+    """Smallest fragment that connectivity enforcement leaves alone: a fraction (fast_slic's default: a quarter) of the mean superpixel."""
+    return max(1, int(min_size_factor * H * W / n_clusters))
+
+
+# tile of the component-labelling kernel (rows, columns): WVN_SLIC_CC_TILE_H / _W of include/wvn_hip.h (the tests pick sizes around it)
+SLIC_CC_TILE = (8, 32)
+
+
+def slic_enforce_connectivity(labels: torch.Tensor, n_clusters: int, min_size: int, out: Optional[torch.Tensor] = None,
+                              return_waiting: bool = False):
+    """Connectivity enforcement of label maps (csrc/slic_connectivity.hip; the definition is in include/wvn_hip.h): labels [H,W] or
+    [B,H,W] int32 (CUDA) with ids in [0, n_clusters) -- SLIC's or any other -> the same shape, every 4-connected fragment below
+    ``min_size`` pixels handed to the neighbouring label with the longest common border (lowest id on a tie), in rounds, until none is
+    left.  One launch sequence for the whole batch and no host synchronisation.  ``out`` may be ``labels`` (in place).
+    ``return_waiting``: also returns the kernels' per-image counters of components still waiting at the end, [B] int32 on the device --
+    zero by construction (the tests assert it)."""
+    require_cuda(labels, "labels")
+    if labels.dtype != torch.int32 or labels.dim() not in (2, 3):
+        raise _lib.WvnError("slic_enforce_connectivity: labels must be int32 [H,W] or [B,H,W]")
+    labels = labels.contiguous()
+    H, W = labels.shape[-2:]
+    B = 1 if labels.dim() == 2 else labels.shape[0]
+    if out is None:
+        out = torch.empty_like(labels)
+    elif out.dtype != torch.int32 or out.shape != labels.shape or not out.is_contiguous() or out.device != labels.device:
+        raise _lib.WvnError("slic_enforce_connectivity: out must be a contiguous int32 tensor of labels' shape on labels' device")
+    nbytes = lib().wvn_slic_connectivity_scratch_bytes(B, H, W, int(n_clusters))
+    if nbytes == 0:
+        raise _lib.WvnError(f"slic_enforce_connectivity: unsupported shape B={B} H={H} W={W} n_clusters={n_clusters}")
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=labels.device)
+    check(lib().wvn_slic_connectivity(ptr(labels), ptr(out), B, H, W, int(n_clusters), int(min_size), ptr(scratch), scratch.numel(),
+                                      stream()), "wvn_slic_connectivity")
+    if return_waiting:
+        return out, scratch[:16 * B].view(torch.int32)[::4].clone()
+    return out
 
 
 def slic_num_clusters(H: int, W: int, num_components: int) -> int:
