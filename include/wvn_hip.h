@@ -599,19 +599,26 @@ int wvn_mlp_confidence(const float* out, int ldo, const float* x, int ldx, float
  * without building the dense tensor (308 MB / frame at 448^2) and with layer 1 evaluated at token resolution
  * (csrc/pixel_mlp.hip).  bf16 MFMA operands, fp32 accumulation: the speed mode; the exact mode is
  * wvn_upsample_bilinear + wvn_mlp_forward + wvn_mlp_confidence (or the exact-mode form below).  H1 = 256, H2 = 32 and D = 384 (DINO
- * ViT-S features) or D = 90 (STEGO code, the live node's default feature_type); 0 / WVN_ERR_ARG otherwise.
+ * ViT-S features), D = 768 (ViT-Base features: DINO ViT-B/8, DINOv2 ViT-B/14) or D = 90 (STEGO code, the live node's default
+ * feature_type); 0 / WVN_ERR_ARG otherwise.
+ * Sizes, with T = ceil(D / 32) + 1 W3 tiles (13 / 25 / 4) and DX = the x columns of a zx row (384 / 768 / 128):
+ *   W23 = 16384 + T * 2048 bytes (W2 and W3 fragment images, bf16), NBIAS = 256 + 32 + 32 * T floats
+ *   wvn_pixel_mlp_pack_bytes             = 256 * DX * 2 + W23 + 4 * NBIAS
+ *   wvn_pixel_mlp_zx_cols                = 256 + DX
+ *   wvn_pixel_mlp_exact_pack_bytes       = 2 * W23 + 4 * NBIAS                    (hi and lo images)
+ *   wvn_pixel_mlp_exact_workspace_bytes  = rows * 256 * 4 + 2 * rows * (256 + 32 * (T - 1)) * 2 + 256,  rows = batch * grid^2
  *
  * packed : wvn_pixel_mlp_pack_bytes() bytes, rebuilt by wvn_pixel_mlp_pack whenever the parameters change
  *          (the node reloads them at 1 Hz, wvn_feature_extractor_node.py:407-432).
- * zx     : [batch*grid*grid rows][ldzx >= wvn_pixel_mlp_zx_cols()] bf16 (640 for D = 384, 384 for D = 90).  Columns from 256 on
- *          hold the features on entry (D = 384: hand wvn_vit_forward tokens_lowp = zx + 256, ld_lowp = ldzx; D = 90: the 90
+ * zx     : [batch*grid*grid rows][ldzx >= wvn_pixel_mlp_zx_cols()] bf16 (640 for D = 384, 1024 for D = 768, 384 for D = 90).  Columns from 256 on
+ *          hold the features on entry (D = 384 / 768: hand wvn_vit_forward tokens_lowp = zx + 256, ld_lowp = ldzx; D = 90: the 90
  *          code values followed by ZEROS up to column 384); columns [0,256) are scratch (layer-1 pre-activations).
  * trav / conf / loss_reco : [batch][out_h][out_w] fp32, each may be NULL.  mean/std/std_factor: ConfidenceGenerator state;
  * conf_state (may be NULL): the same three floats in DEVICE memory, read by the kernel instead of the scalars -- lets the call
  * sit in a captured HIP graph while the confidence statistics keep moving.
  * Requires 15*(grid-1)/(out-1) < 2 in both directions (out >= ~7.5 x grid: 224/28, 448/56 ...), WVN_ERR_ARG otherwise.
  * ------------------------------------------------------------------------------------------- */
-#define WVN_PIXEL_ZX_COLS 640
+#define WVN_PIXEL_ZX_COLS 640   /* D = 384; wvn_pixel_mlp_zx_cols() for any supported D */
 #define WVN_PIXEL_X_COL 256
 size_t wvn_pixel_mlp_pack_bytes(const wvn_mlp_desc* d);
 int wvn_pixel_mlp_zx_cols(const wvn_mlp_desc* d);
@@ -623,7 +630,7 @@ int wvn_pixel_mlp_infer(const wvn_mlp_desc* d, const void* packed, void* zx, int
 /* Exact-mode form of the same fused kernel: every MFMA operand is split into hi + lo bf16 parts and every product is formed
  * as hi*hi + hi*lo + lo*hi (fp32 accumulation), the token-resolution layer-1 GEMM runs on the fp32 FMA path: results agree
  * with the fp32 reference sequence to ~1e-5 relative (the 1e-3 bar of the exact mode), at 2.3x the MFMA work of the bf16
- * form.  tokens: [batch*grid*grid][ld_tokens >= D] fp32 features (D = 384: wvn_vit_forward tokens_f32; D = 90: the STEGO code);
+ * form.  tokens: [batch*grid*grid][ld_tokens >= D] fp32 features (D = 384 / 768: wvn_vit_forward tokens_f32; D = 90: the STEGO code);
  * params: the flat fp32 parameter buffer (W1 is read from it); packed: wvn_pixel_mlp_exact_pack_bytes() bytes from
  * wvn_pixel_mlp_exact_pack; workspace: wvn_pixel_mlp_exact_workspace_bytes() bytes, no initialisation needed. */
 size_t wvn_pixel_mlp_exact_pack_bytes(const wvn_mlp_desc* d);

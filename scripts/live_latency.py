@@ -29,10 +29,11 @@ def wall(fn, iters):
     return (time.perf_counter() - t0) / iters * 1e3
 
 
-def run(dev, S, ftype, precision="bf16"):
-    sd = synthetic_vit_state_dict(depth=12, pretrain_grid=28)
-    fe = FeatureExtractor(device=dev, segmentation_type="stego" if ftype == "stego" else "grid", feature_type=ftype, patch_size=8,
-                          backbone_type="vit_small", input_size=S, pretrained_weights=sd, precision=precision)
+def run(dev, S, ftype, precision="bf16", arch="vit_small"):
+    v2 = ftype == "dinov2"
+    sd = synthetic_vit_state_dict(arch, 14 if v2 else 8, depth=12, pretrain_grid=37 if v2 else 28, dinov2=v2)
+    fe = FeatureExtractor(device=dev, segmentation_type="stego" if ftype == "stego" else "grid", feature_type=ftype, patch_size=14 if v2 else 8,
+                          backbone_type=arch, input_size=S, pretrained_weights=sd, precision=precision)
     params = ExperimentParams()
     params.model.simple_mlp_cfg.input_size = fe.feature_dim
     model = get_model(params.model).to(dev)
@@ -43,7 +44,7 @@ def run(dev, S, ftype, precision="bf16"):
     eager = wall(lambda: fe.predict_per_pixel(frame, model, cg), 50)
     # the segmentation + pooling half of the node's frame (extract): k-means / grid segments, pooled rows
     seg_ms = wall(lambda: fe.extract(frame), 30)
-    return {"frame": f"{S}x{S} uint8", "features": ftype, "precision": precision, "predict_per_pixel_ms": round(eager, 3), "extract_ms": round(seg_ms, 3)}
+    return {"frame": f"{S}x{S} uint8", "features": ftype, "backbone": arch, "precision": precision, "predict_per_pixel_ms": round(eager, 3), "extract_ms": round(seg_ms, 3)}
 
 
 def main():
@@ -52,6 +53,9 @@ def main():
     # (round 5: the class default is precision="mixed", the <= 1e-3 mode; the 16-bit speed paths beside it)
     out = []
     for prec in ("mixed", "fp16", "bf16"):
+        if os.environ.get("LIVE_VIT_BASE", "0") not in ("", "0"):   # 768-d features: DINO ViT-B/8 at 448^2, DINOv2 ViT-B/14 at 518^2
+            out += [run(dev, 448, "dino", prec, "vit_base"), run(dev, 518, "dinov2", prec, "vit_base")]
+            continue
         out += [run(dev, 448, "dino", prec), run(dev, 224, "stego", prec), run(dev, 224, "dino", prec)]
     print(json.dumps(out))
 

@@ -25,6 +25,16 @@
 //
 // bf16 operands, fp32 accumulation: this is the speed mode.  The exact (fp32 FMA) mode is wvn_upsample_bilinear +
 // wvn_mlp_forward + wvn_mlp_confidence.
+//
+// D = 768 (ViT-Base features: DINO ViT-B/8, DINOv2 ViT-B/14).  Same design, 24 reconstruction tiles, zx rows of 1024 columns:
+// 16 + 16 + 24 x 4 + 2 = 130 MFMAs per 32 pixels (bf16), 24 + 48 + 24 x 9 + 6 = 294 (exact).
+//   bf16 form : token planes 32,896 + W2 16,384 + W3 (25 tiles) 51,200 + biases 4,352 = 104,832 bytes of LDS: ONE workgroup per CU
+//               (Cfg::WGS_PER_CU sets __launch_bounds__ and the grid cap; 384 and 90 keep two), 98 VGPRs, no scratch.
+//   exact form: hi + lo token planes 65,792 + W2 hi/lo 32,768 + W3 hi/lo 102,400 + biases 4,352 = 205,312 > 160 KB.  The W3 lo
+//               image (51,200 bytes) stays in the packed blob in global memory; each wave reads its two 1 KB fragments per
+//               reconstruction tile with 16-byte global loads, requested one tile (9 MFMAs) ahead.  LDS 154,112 bytes, 225 VGPRs,
+//               no scratch, one workgroup per CU.  The blob is the same 50 KB for every wave on the chip (L2-resident), at the
+//               price of 50 KB of L2 / L1 reads per wave per 16x16-pixel tile (400 KB per workgroup and tile).
 #include <cstdlib>
 
 #include "common.h"
@@ -36,15 +46,17 @@ constexpr int H1 = 256, H2 = 32;
 constexpr int W2_BYTES = 16 * 2 * 32 * 16;          // [16 k-steps][2 lane halves][32 rows][8 bf16] = 16,384
 constexpr int TILE = 16;                            // pixels per tile edge; a wave owns 2 rows x 16 columns
 
-// D = MLP input size: 384 (DINO ViT-S features) or 90 (STEGO code, the live node's default feature_type).  For D = 90 the
-// x part of a zx row is zero-padded to 128 columns (K of the layer-1 GEMM) and three 32-channel blocks are interpolated.
+// D = MLP input size: 384 (DINO ViT-S features), 768 (DINO ViT-B/8, DINOv2 ViT-B/14) or 90 (STEGO code, the live node's default
+// feature_type).  For D = 90 the x part of a zx row is zero-padded to 128 columns (K of the layer-1 GEMM) and three 32-channel
+// blocks are interpolated.
+constexpr int LDS_PER_CU = 160 * 1024;
 template <int D>
 struct Cfg {
   static constexpr int DREAL = D;
-  static constexpr int NT = (D + 31) / 32;              // 32-channel reconstruction tiles (12 / 3)
-  static constexpr int DX = D == 384 ? 384 : 128;       // x columns of a zx row
-  static constexpr int ZXC = H1 + DX;                   // zx row length the caller provides (640 / 384)
-  static constexpr int NCH = H1 + 32 * NT;              // channels staged and interpolated per token (640 / 352)
+  static constexpr int NT = (D + 31) / 32;              // 32-channel reconstruction tiles (12 / 24 / 3)
+  static constexpr int DX = D == 384 || D == 768 ? D : 128;  // x columns of a zx row
+  static constexpr int ZXC = H1 + DX;                   // zx row length the caller provides (640 / 1024 / 384)
+  static constexpr int NCH = H1 + 32 * NT;              // channels staged and interpolated per token (640 / 1024 / 352)
   static constexpr int PLANE = NCH * 16 + 64;           // bytes of one 8-token plane [NCH ch][8 tok] (+64: planes 16 banks apart)
   static constexpr int TOK_BYTES = 2 * PLANE;
   static constexpr int W3_TILES = NT + 1;               // + 1 tile whose row 0 is the traversability unit
@@ -55,16 +67,20 @@ struct Cfg {
   static constexpr int OFF_W2 = TOK_BYTES;
   static constexpr int OFF_W3 = OFF_W2 + W2_BYTES;
   static constexpr int OFF_BIAS = OFF_W3 + W3_BYTES;
-  static constexpr int LDS_BYTES = OFF_BIAS + NBIAS * 4; // 66,432 at D = 384: two workgroups per CU
+  static constexpr int LDS_BYTES = OFF_BIAS + NBIAS * 4; // 66,432 at D = 384: two workgroups per CU; 104,832 at D = 768: one
+  static constexpr int WGS_PER_CU = 2 * LDS_BYTES <= LDS_PER_CU ? 2 : 1;   // occupancy bound and grid cap of the bf16 form
   static constexpr int NFETCH = 16 * (NCH / 8);          // 16-byte chunks of one token window
   static constexpr int NPRE = (NFETCH + 511) / 512;
-  // exact mode (hi + lo): lo planes after the hi planes, then W2H | W3H | W2L | W3L | bias
+  // exact mode (hi + lo): lo planes after the hi planes, then W2H | W3H | W2L | W3L | bias.  Where that exceeds the CU's LDS
+  // (D = 768: 205,312 bytes) the W3 lo image stays in global memory and its fragments are streamed from L2 (W3L_STREAM):
+  // W2H | W3H | W2L | bias.
   static constexpr int XTOKL = TOK_BYTES;
   static constexpr int XOFFW = 2 * TOK_BYTES;
   static constexpr int XW2H = XOFFW, XW3H = XW2H + W2_BYTES, XW2L = XW3H + W3_BYTES, XW3L = XW2L + W2_BYTES;
-  static constexpr int XBIAS = XW3L + W3_BYTES;
-  static constexpr int XWIMG_BYTES = 2 * (W2_BYTES + W3_BYTES) + NBIAS * 4;
-  static constexpr int XLDS_BYTES = XBIAS + NBIAS * 4;   // 130,048 at D = 384
+  static constexpr int XWIMG_BYTES = 2 * (W2_BYTES + W3_BYTES) + NBIAS * 4;   // the packed blob (always holds W3 lo)
+  static constexpr bool W3L_STREAM = XOFFW + XWIMG_BYTES > LDS_PER_CU;
+  static constexpr int XBIAS = W3L_STREAM ? XW3L : XW3L + W3_BYTES;
+  static constexpr int XLDS_BYTES = XBIAS + NBIAS * 4;   // 130,048 at D = 384; 154,112 at D = 768
   static constexpr int XNPRE = (2 * NFETCH + 511) / 512;
 };
 
@@ -108,7 +124,7 @@ __device__ inline bf16x8_t relu_pack8(const f32x16_t& a, int r0) {
 }
 
 template <int WSPLIT, int D>
-__global__ __launch_bounds__(512, 2) void pixel_mlp_kernel(PixParams p) {
+__global__ __launch_bounds__(512, Cfg<D>::WGS_PER_CU) void pixel_mlp_kernel(PixParams p) {
   using K = Cfg<D>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -120,7 +136,7 @@ __global__ __launch_bounds__(512, 2) void pixel_mlp_kernel(PixParams p) {
   for (int i = tid; i < K::WIMG_BYTES / 16; i += 512) *(u32x4_t*)(smem + K::OFF_W2 + i * 16) = ((const u32x4_t*)p.wimg)[i];
   const float* bias_l = (const float*)(smem + K::OFF_BIAS);
 
-  // this thread's share of a token window: chunks tid, tid + 512, tid + 1024 of [16 tokens][80 x 16 B]
+  // this thread's share of a token window: chunks tid, tid + 512, ... of [16 tokens][NCH / 8 x 16 B]
   u32x4_t pre[K::NPRE];
   auto fetch = [&](int tile) {
     const int b = tile / tiles_per_frame, r = tile - b * tiles_per_frame;
@@ -324,7 +340,12 @@ __global__ __launch_bounds__(512, 1) void pixel_mlp_x3_kernel(PixX3Params p) {
   const int tiles_per_frame = p.nty * p.ntx;
   const int ntiles = p.B * tiles_per_frame;
 
-  for (int i = tid; i < K::XWIMG_BYTES / 16; i += 512) *(u32x4_t*)(smem + K::XOFFW + i * 16) = ((const u32x4_t*)p.wimg)[i];
+  // resident weight images: the whole blob, or W2H | W3H | W2L and the biases from behind the W3 lo image that stays in global memory
+  constexpr int NRES = K::W3L_STREAM ? K::XW3L - K::XOFFW : K::XWIMG_BYTES;
+  for (int i = tid; i < NRES / 16; i += 512) *(u32x4_t*)(smem + K::XOFFW + i * 16) = ((const u32x4_t*)p.wimg)[i];
+  if constexpr (K::W3L_STREAM)
+    for (int i = tid; i < K::NBIAS * 4 / 16; i += 512)
+      *(u32x4_t*)(smem + K::XBIAS + i * 16) = ((const u32x4_t*)(p.wimg + K::XWIMG_BYTES - K::NBIAS * 4))[i];
   const float* bias_l = (const float*)(smem + K::XBIAS);
 
   u32x4_t pre[K::XNPRE];
@@ -409,14 +430,25 @@ __global__ __launch_bounds__(512, 1) void pixel_mlp_x3_kernel(PixX3Params p) {
     relu_split8(a2, 0, gh[0], gl[0]);
     relu_split8(a2, 8, gh[1], gl[1]);
 
+    // W3 lo fragment of (tile t, k-step u): from LDS, or (W3L_STREAM) from the packed blob in global memory -- the same 50 KB
+    // for every wave of every workgroup, L2-resident; tile t + 1's pair is requested before tile t's MFMAs
+    const unsigned char* w3lg = p.wimg + 2 * W2_BYTES + K::W3_BYTES + lw;
+    bf16x8_t wln[2];
+    if constexpr (K::W3L_STREAM) { wln[0] = *(const bf16x8_t*)w3lg; wln[1] = *(const bf16x8_t*)(w3lg + 1024); }
     float lsum = 0.f;
 #pragma unroll
     for (int t = 0; t < K::NT; ++t) {
       f32x16_t a3 = bias16(bias_l + H1 + H2 + 32 * t, h);
+      bf16x8_t wlc[2];
+      if constexpr (K::W3L_STREAM) {
+        wlc[0] = wln[0]; wlc[1] = wln[1];
+        wln[0] = *(const bf16x8_t*)(w3lg + (2 * t + 2) * 1024);   // (t + 1 == NT: the traversability tile)
+        wln[1] = *(const bf16x8_t*)(w3lg + (2 * t + 3) * 1024);
+      }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const bf16x8_t wh = *(const bf16x8_t*)(smem + K::XW3H + (2 * t + u) * 1024 + lw);
-        const bf16x8_t wl = *(const bf16x8_t*)(smem + K::XW3L + (2 * t + u) * 1024 + lw);
+        const bf16x8_t wl = K::W3L_STREAM ? wlc[u] : *(const bf16x8_t*)(smem + K::XW3L + (2 * t + u) * 1024 + lw);
         MFMA3(a3, wh, wl, gh[u], gl[u]);
       }
       const bf16x8_t th = *(const bf16x8_t*)(tokh + (H1 / 32 + t) * 512), tl = *(const bf16x8_t*)(tokl + (H1 / 32 + t) * 512);
@@ -428,7 +460,7 @@ __global__ __launch_bounds__(512, 1) void pixel_mlp_x3_kernel(PixX3Params p) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const bf16x8_t wh = *(const bf16x8_t*)(smem + K::XW3H + (2 * (K::NT) + u) * 1024 + lw);
-      const bf16x8_t wl = *(const bf16x8_t*)(smem + K::XW3L + (2 * (K::NT) + u) * 1024 + lw);
+      const bf16x8_t wl = K::W3L_STREAM ? wln[u] : *(const bf16x8_t*)(smem + K::XW3L + (2 * (K::NT) + u) * 1024 + lw);
       MFMA3(at, wh, wl, gh[u], gl[u]);
     }
 
@@ -492,7 +524,7 @@ __global__ void pixel_mlp_pack_x3_kernel(const float* __restrict__ prm, unsigned
   }
 }
 
-// zf [rows][256] fp32 (layer-1 pre-activations) and tokens [rows][ldt] fp32 -> hi / lo rows [ Z | x ] of 640 bf16
+// zf [rows][256] fp32 (layer-1 pre-activations) and tokens [rows][ldt] fp32 -> hi / lo rows [ Z | x ] of NCH bf16
 template <int D>
 __global__ void pixel_split_rows_kernel(const float* __restrict__ zf, const float* __restrict__ tok, int ldt,
                                         bf16_t* __restrict__ zxh, bf16_t* __restrict__ zxl, long long rows) {
@@ -547,7 +579,7 @@ int pix_infer(const void* packed, void* zx, int ldzx, int B, int G, int out_h, i
   static LdsOptIn lds_opt_in;   // per device (common.h)
   if (const int rc = lds_opt_in(K::LDS_BYTES, (const void*)kern)) return rc;
   const int ntiles = B * p.nty * p.ntx;
-  const int cap = 2 * pix_num_cus();
+  const int cap = K::WGS_PER_CU * pix_num_cus();
   hipLaunchKernelGGL(kern, dim3(ntiles < cap ? ntiles : cap), dim3(512), K::LDS_BYTES, st, p);
   WVN_LAUNCH_CHECK();
   return WVN_OK;
@@ -600,19 +632,22 @@ int pix_infer_exact(const float* params, const void* packed, const float* tokens
   return WVN_OK;
 }
 
-bool pix_supported(int D, int h1, int h2) { return (D == 384 || D == 90) && h1 == H1 && h2 == H2; }
+bool pix_supported(int D, int h1, int h2) { return (D == 384 || D == 768 || D == 90) && h1 == H1 && h2 == H2; }
 
 }  // namespace
 
-// D = 384 (DINO ViT-S features) or 90 (STEGO code); 0 / WVN_ERR_ARG for anything else
+// D = 384 (DINO ViT-S features), 768 (ViT-B features) or 90 (STEGO code); 0 / WVN_ERR_ARG for anything else
 size_t wvn_pixel_mlp_pack_bytes_impl(int D) {
-  return D == 384 ? (size_t)Cfg<384>::W1_BYTES + Cfg<384>::WIMG_BYTES : D == 90 ? (size_t)Cfg<90>::W1_BYTES + Cfg<90>::WIMG_BYTES : 0;
+  return D == 384 ? (size_t)Cfg<384>::W1_BYTES + Cfg<384>::WIMG_BYTES
+       : D == 768 ? (size_t)Cfg<768>::W1_BYTES + Cfg<768>::WIMG_BYTES
+       : D == 90 ? (size_t)Cfg<90>::W1_BYTES + Cfg<90>::WIMG_BYTES : 0;
 }
-int wvn_pixel_mlp_zx_cols_impl(int D) { return D == 384 ? Cfg<384>::ZXC : D == 90 ? Cfg<90>::ZXC : 0; }
+int wvn_pixel_mlp_zx_cols_impl(int D) { return D == 384 ? Cfg<384>::ZXC : D == 768 ? Cfg<768>::ZXC : D == 90 ? Cfg<90>::ZXC : 0; }
 
 int wvn_pixel_mlp_pack_launch(int D, int h1, int h2, const float* params, void* packed, hipStream_t st) {
   if (!pix_supported(D, h1, h2) || !params || !packed || ((uintptr_t)packed & 15)) return WVN_ERR_ARG;
   if (D == 384) hipLaunchKernelGGL(pixel_mlp_pack_kernel<384>, dim3(96), dim3(256), 0, st, params, (unsigned char*)packed);
+  else if (D == 768) hipLaunchKernelGGL(pixel_mlp_pack_kernel<768>, dim3(96), dim3(256), 0, st, params, (unsigned char*)packed);
   else hipLaunchKernelGGL(pixel_mlp_pack_kernel<90>, dim3(96), dim3(256), 0, st, params, (unsigned char*)packed);
   WVN_LAUNCH_CHECK();
   return WVN_OK;
@@ -623,19 +658,21 @@ int wvn_pixel_mlp_infer_launch(int D, int h1, int h2, const void* packed, void* 
                                float* conf, float* loss, hipStream_t st) {
   if (!pix_supported(D, h1, h2) || !packed || !zx || B <= 0 || G < 2 || out_h < 2 || out_w < 2) return WVN_ERR_ARG;
   return D == 384 ? pix_infer<384>(packed, zx, ldzx, B, G, out_h, out_w, mean, std, std_factor, conf_state, trav, conf, loss, st)
+       : D == 768 ? pix_infer<768>(packed, zx, ldzx, B, G, out_h, out_w, mean, std, std_factor, conf_state, trav, conf, loss, st)
                   : pix_infer<90>(packed, zx, ldzx, B, G, out_h, out_w, mean, std, std_factor, conf_state, trav, conf, loss, st);
 }
 
 size_t wvn_pixel_mlp_exact_pack_bytes_impl(int D) {
-  return D == 384 ? (size_t)Cfg<384>::XWIMG_BYTES : D == 90 ? (size_t)Cfg<90>::XWIMG_BYTES : 0;
+  return D == 384 ? (size_t)Cfg<384>::XWIMG_BYTES : D == 768 ? (size_t)Cfg<768>::XWIMG_BYTES : D == 90 ? (size_t)Cfg<90>::XWIMG_BYTES : 0;
 }
 size_t wvn_pixel_mlp_exact_workspace_bytes_impl(int D, int B, int G) {
-  return D == 384 ? pix_exact_ws<384>(B, G) : D == 90 ? pix_exact_ws<90>(B, G) : 0;
+  return D == 384 ? pix_exact_ws<384>(B, G) : D == 768 ? pix_exact_ws<768>(B, G) : D == 90 ? pix_exact_ws<90>(B, G) : 0;
 }
 
 int wvn_pixel_mlp_exact_pack_launch(int D, int h1, int h2, const float* params, void* packed, hipStream_t st) {
   if (!pix_supported(D, h1, h2) || !params || !packed || ((uintptr_t)packed & 15)) return WVN_ERR_ARG;
   if (D == 384) hipLaunchKernelGGL(pixel_mlp_pack_x3_kernel<384>, dim3(96), dim3(256), 0, st, params, (unsigned char*)packed);
+  else if (D == 768) hipLaunchKernelGGL(pixel_mlp_pack_x3_kernel<768>, dim3(96), dim3(256), 0, st, params, (unsigned char*)packed);
   else hipLaunchKernelGGL(pixel_mlp_pack_x3_kernel<90>, dim3(96), dim3(256), 0, st, params, (unsigned char*)packed);
   WVN_LAUNCH_CHECK();
   return WVN_OK;
@@ -648,6 +685,8 @@ int wvn_pixel_mlp_infer_exact_launch(int D, int h1, int h2, const float* params,
   if (!pix_supported(D, h1, h2) || !params || !packed || !tokens || !workspace || B <= 0 || G < 2 || out_h < 2 || out_w < 2)
     return WVN_ERR_ARG;
   return D == 384 ? pix_infer_exact<384>(params, packed, tokens, ldt, B, G, out_h, out_w, mean, std, std_factor, conf_state, trav,
+                                         conf, loss, workspace, workspace_bytes, st)
+       : D == 768 ? pix_infer_exact<768>(params, packed, tokens, ldt, B, G, out_h, out_w, mean, std, std_factor, conf_state, trav,
                                          conf, loss, workspace, workspace_bytes, st)
                   : pix_infer_exact<90>(params, packed, tokens, ldt, B, G, out_h, out_w, mean, std, std_factor, conf_state, trav,
                                         conf, loss, workspace, workspace_bytes, st);

@@ -188,8 +188,11 @@ class FeatureExtractor:
         quick_start.py:176-210) in one call: img [B,3,H,W] (fp32 in [0,1] or uint8) -> (trav [B,H,H], conf [B,H,H],
         loss_reco | None).  Equivalent to ``extract(..., return_dense_features=True)`` -> ``model.forward(Data(x=dense
         rows))`` -> column 0 / ``confidence_generator.inference_without_update(mse(pred[:, 1:], x))``, but the dense
-        [B,D,H,H] tensor is never built and layer 1 runs at patch resolution (csrc/pixel_mlp.hip).  DINO (384-d) or STEGO
-        (90-d code) features; bf16 extractor -> bf16 MFMA kernel, fp32 (exact) extractor -> the hi + lo split form (<= 1e-3 of the reference).  Like the reference (dino_interface.py:87-90) the map is H x H for an H x W frame."""
+        [B,D,H,H] tensor is never built and layer 1 runs at patch resolution (csrc/pixel_mlp.hip).  DINO / DINOv2 ViT-S (384-d),
+        ViT-Base (768-d: DINO ViT-B/8, DINOv2 ViT-B/14) or STEGO (90-d code) features; bf16 / fp8 / fp16 extractor -> bf16 MFMA
+        kernel (fp16 tokens are rounded to bf16 once), fp32 (exact) extractor -> the hi + lo split form (<= 1e-3 of the reference).
+        ``model.input_size`` must equal the extractor's ``feature_dim`` (WvnError otherwise).  Like the reference
+        (dino_interface.py:87-90) the map is H x H for an H x W frame."""
         mean, std, f = 0.0, 1.0, 0.5
         if confidence_generator is not None:
             mean, std, f = float(confidence_generator.mean), float(confidence_generator.std), float(confidence_generator.std_factor)
@@ -201,6 +204,9 @@ class FeatureExtractor:
         stego = self._feature_type == "stego"
         prec = self._extractor._precision
         exact = prec in ("exact", "fp32", "mixed")
+        if self.feature_dim != model.input_size:
+            raise _lib.WvnError(f"predict_per_pixel: the extractor's feature_dim is {self.feature_dim}, the model's input_size is "
+                                f"{model.input_size}")
         if exact:   # fp32 extractor: hi + lo split MFMA operands in the fused kernel
             tokens = self.backbone_stage(img)
             return model.forward_per_pixel_exact(tokens.reshape(B * G * G, -1), B, G, (H, H), mean, std, f, want_loss=want_loss,
@@ -211,7 +217,7 @@ class FeatureExtractor:
             zx[:, model.X_COL: model.X_COL + code.shape[1]] = code
         else:
             zx = torch.empty(B * G * G, model.ZX_COLS, dtype=torch.bfloat16, device=self._device)
-            if prec == "fp16":   # the per-pixel kernel takes bf16 features: hand it the fp32 tokens rounded once
+            if self._extractor._model.lowp_dtype != torch.bfloat16:   # (fp16) the kernel takes bf16 features: the fp32 tokens rounded once
                 ops.cast_rows_bf16(self._extractor._model.forward_tokens(img).reshape(B * G * G, -1), zx[:, model.X_COL:])
             else:
                 self._extractor._model.forward_tokens(img, lowp_out=zx[:, model.X_COL:])

@@ -92,7 +92,8 @@ class SimpleMLP(torch.nn.Module):
 
     @property
     def ZX_COLS(self) -> int:
-        """Row length of the zx buffer: 640 for 384-d DINO features, 384 for the 90-d STEGO code (0: unsupported size)."""
+        """Row length of the zx buffer: 640 for 384-d DINO ViT-S features, 1024 for 768-d ViT-Base features (DINO ViT-B/8,
+        DINOv2 ViT-B/14), 384 for the 90-d STEGO code (0: unsupported size)."""
         return int(_lib.lib().wvn_pixel_mlp_zx_cols(C.byref(self.desc)))
 
     def pack_per_pixel(self) -> torch.Tensor:
@@ -102,7 +103,8 @@ class SimpleMLP(torch.nn.Module):
         _lib.require_cuda(flat, "parameters")
         n = _lib.lib().wvn_pixel_mlp_pack_bytes(C.byref(self.desc))
         if n == 0:
-            raise _lib.WvnError("fused per-pixel inference needs SimpleMLP(384 | 90, [256, 32, 1], reconstruction=True)")
+            raise _lib.WvnError(f"fused per-pixel inference needs SimpleMLP(384 | 768 | 90, [256, 32, 1], reconstruction=True), "
+                                f"got input_size = {self.input_size}")
         if self._pix_packed is None or self._pix_packed.device != flat.device:
             self._pix_packed = torch.empty(n, dtype=torch.uint8, device=flat.device)
         rc = _lib.lib().wvn_pixel_mlp_pack(C.byref(self.desc), flat.data_ptr(), self._pix_packed.data_ptr(), _lib.stream())
@@ -140,7 +142,8 @@ class SimpleMLP(torch.nn.Module):
                                 std: float = 1.0, std_factor: float = 0.5, want_loss: bool = False,
                                 conf_state: Optional[torch.Tensor] = None):
         """Exact-mode form of ``forward_per_pixel`` (hi + lo split MFMA operands, fp32 layer-1 GEMM at token resolution):
-        ``tokens`` [batch*grid*grid, 384] fp32 (the backbone's final patch tokens) -> (trav, conf, loss_reco | None),
+        ``tokens`` [batch*grid*grid, D] fp32 (the backbone's final patch tokens, D = 384 or 768, or the 90-d STEGO code) ->
+        (trav, conf, loss_reco | None),
         within 1e-3 of the reference sequence on the dense fp32 features."""
         _lib.require_cuda(tokens, "tokens")
         if tokens.dtype != torch.float32 or tokens.dim() != 2 or tokens.shape[0] != batch * grid * grid or tokens.stride(1) != 1 \
@@ -150,7 +153,8 @@ class SimpleMLP(torch.nn.Module):
         flat = self.flat_params()
         n = h.wvn_pixel_mlp_exact_pack_bytes(C.byref(self.desc))
         if n == 0:
-            raise _lib.WvnError("fused per-pixel inference needs SimpleMLP(384, [256, 32, 1], reconstruction=True)")
+            raise _lib.WvnError(f"fused per-pixel inference needs SimpleMLP(384 | 768 | 90, [256, 32, 1], reconstruction=True), "
+                                f"got input_size = {self.input_size}")
         if self._pix_packed_x3 is None or self._pix_packed_x3.device != flat.device:
             self._pix_packed_x3 = torch.empty(n, dtype=torch.uint8, device=flat.device)
         _lib.check(h.wvn_pixel_mlp_exact_pack(C.byref(self.desc), flat.data_ptr(), self._pix_packed_x3.data_ptr(), _lib.stream()),
