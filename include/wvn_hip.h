@@ -324,6 +324,9 @@ int wvn_upsample_nearest_i32(const int* labels, int* out, int B, int G, int H, v
 /* FeatureExtractor.sparsify_features (feature_extractor.py:390-396) fused with the bilinear
  * up-sampling that precedes it: feat[b][s][:] = mean over {seg[b]==s} of upsample(tokens[b]).
  * seg [B,H,W] int32 (-1 = ignore), tokens [B,G*G,ld] fp32, feat [B,S,D].
+ * Square frames only: H == W.  Both axes are resampled with the tap scale (G-1)/(H-1), as the reference's H x H dense map
+ * is; H != W returns WVN_ERR_ARG before anything is written or launched.  Also WVN_ERR_ARG: null pointer, S < 1, D < 1,
+ * D > 1024, scratch_w not 8-byte aligned.
  * scratch_w: B*S*G*G 8-byte words (the tap weights accumulate in 64-bit fixed point: integer atomics are order-independent,
  * so the result is deterministic), scratch_cnt: B*S ints (receives the pixel count per segment). */
 int wvn_segpool_bilinear_mean(const int* seg, const float* tokens, int ld, float* feat, void* scratch_w,

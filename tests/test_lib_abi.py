@@ -133,6 +133,18 @@ def test_attention_planes_refuses_what_the_kernel_does_not_support():
     assert call(npad=800) == 1001                     # npad % 128 (the launcher's own check)
 
 
+def test_segpool_refuses_non_square_frames_before_touching_a_buffer():
+    """wvn_segpool_bilinear_mean resamples both axes with (G-1)/(H-1): H != W returns WVN_ERR_ARG before any memset or launch, so
+    host buffers (never dereferenced) and no GPU are enough to see it."""
+    h = _lib.lib()
+    words = (C.c_longlong * 64)()
+    p = C.addressof(words)
+    assert p % 8 == 0
+    for H, W in ((64, 96), (96, 64)):
+        assert h.wvn_segpool_bilinear_mean(p, p, 4, p, p, p, 1, H, W, 8, 2, 4, None) == 1001
+    assert all(w == 0 for w in words)
+
+
 def test_no_cpu_fallback():
     import torch
 

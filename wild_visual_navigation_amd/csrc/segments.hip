@@ -429,13 +429,16 @@ int wvn_segpool_launch(const int* seg, const float* tok, int ldf, float* feat, v
                        int Wd, int G, int S, int D, hipStream_t st) {
   unsigned long long* W = (unsigned long long*)Wv;
   if (!seg || !tok || !feat || !W || !cnt || S <= 0 || D <= 0 || D > 1024 || ((uintptr_t)W & 7)) return WVN_ERR_ARG;
+  // Square frames only: both axes use the tap scale (G-1)/(H-1) (the reference's dense map is H x H), so a column x > H-1
+  // of a wider frame would get a left tap x0 >= G -- past its row of the G x G weight table.
+  if (H != Wd) return WVN_ERR_ARG;
   const int P = G * G;
   hipError_t e = hipMemsetAsync(W, 0, (size_t)B * S * P * sizeof(unsigned long long), st);
   if (e != hipSuccess) return (int)e;
   e = hipMemsetAsync(cnt, 0, (size_t)B * S * sizeof(int), st);
   if (e != hipSuccess) return (int)e;
   const size_t band_lds = (size_t)2 * S * G * sizeof(unsigned long long) + (size_t)S * sizeof(int);
-  if (band_lds <= 48 * 1024 && H == Wd)   // few segments (k-means maps): per-band LDS tables, ~12x fewer global atomics
+  if (band_lds <= 48 * 1024)   // few segments (k-means maps): per-band LDS tables, ~12x fewer global atomics
     hipLaunchKernelGGL(segpool_weights_band_kernel, dim3(G, B), dim3(512), band_lds, st, seg, W, cnt, H, Wd, G, S);
   else
     hipLaunchKernelGGL(segpool_weights_kernel, dim3(ceil_div(H * Wd, 256), B), dim3(256), 0, st, seg, W, cnt, H, Wd, G, S);

@@ -36,10 +36,13 @@ def upsample_nearest_labels(labels: torch.Tensor, out_size: int) -> torch.Tensor
 def segpool_bilinear_mean(seg: torch.Tensor, tokens: torch.Tensor, grid: int, n_seg: int,
                           return_counts: bool = False):
     """Fused up-sample + per-segment mean (feature_extractor.py:390-396 on dino_interface.py:87-90).
-    seg [B,H,W] int (-1 ignored), tokens [B,G*G,D] fp32 -> feat [B,S,D] fp32 (NaN row for an empty id)."""
+    seg [B,H,H] int (-1 ignored), tokens [B,G*G,D] fp32 -> feat [B,S,D] fp32 (NaN row for an empty id).
+    Square frames only: both axes are resampled with the reference's (G-1)/(H-1) tap scale."""
     require_cuda(tokens, "tokens")
     seg = _i32(seg).contiguous()
     B, H, W = seg.shape
+    if H != W:
+        raise _lib.WvnError(f"segpool_bilinear_mean: square frames only (seg is [B,H,H]); got H={H}, W={W}")
     tokens = tokens.contiguous()
     D = tokens.shape[-1]
     dev = tokens.device
