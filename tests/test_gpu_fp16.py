@@ -47,6 +47,34 @@ def test_gemm_f16_against_fp64(dev, M, N, K, epi):
     assert err < tol, err
 
 
+def test_gemm_f16_unaligned_odd_ldc_output_with_n_tail(dev):
+    """The output is columns 1..N of a sentinel-filled [M, N + 3] buffer: ldc is odd and C is off 16-byte alignment, so the tiled
+    kernel stores element by element (csrc/tile_epilogue.h, vec_ok == false), and N % 8 = N % 4 = 2 ends both store loops in
+    their scalar tail.  Values as in test_gemm_f16_against_fp64; nothing outside the N columns is written."""
+    M, N, K = 130, 90, 128
+    a = torch.randn(M, K, generator=g(1)).to(dev).half()
+    w = (torch.randn(N, K, generator=g(2)) * 0.05).to(dev).half()
+    bias = (torch.randn(N, generator=g(3)) * 0.1).to(dev)
+    ref = a.double() @ w.double().T + bias.double()
+
+    def edge_bits(buf):
+        edge = torch.cat([buf[:, :1], buf[:, N + 1:]], 1).contiguous()
+        return edge.view(torch.int16 if edge.element_size() == 2 else torch.int32)
+
+    buf = torch.full((M, N + 3), -7.0, dtype=torch.float16, device=dev)
+    clean = edge_bits(buf)
+    ops.gemm_bf16(a, w, bias, _lib.EPI_BF16, out=buf[:, 1:1 + N])
+    assert (buf[:, 1:1 + N].double() - ref).abs().max().item() < 4e-3
+    assert torch.equal(edge_bits(buf), clean)
+    c0 = torch.randn(M, N, generator=g(4)).to(dev)
+    buf = torch.full((M, N + 3), -7.0, device=dev)
+    clean = edge_bits(buf)
+    buf[:, 1:1 + N] = c0
+    ops.gemm_bf16(a, w, bias, _lib.EPI_RESID_F32, out=buf[:, 1:1 + N])
+    assert (buf[:, 1:1 + N].double() - (ref + c0.double())).abs().max().item() < 2e-4
+    assert torch.equal(edge_bits(buf), clean)
+
+
 def _attn(dev, q_in, k, v, ntok, dtype, variant=-1):
     B, h = q_in.shape[:2]
     npad = (ntok + 127) // 128 * 128

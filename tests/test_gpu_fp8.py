@@ -69,6 +69,40 @@ def test_gemm_fp8_against_fp64_on_the_quantised_operands(dev, M, N, K, epi):
         assert rel < 0.06, rel
 
 
+def test_gemm_fp8_unaligned_odd_ldc_output_with_n_tail(dev):
+    """The output is columns 1..N of a sentinel-filled [M, N + 3] buffer: ldc is odd and C is off 16-byte alignment, so the tiled
+    kernel stores element by element (csrc/tile_epilogue.h, vec_ok == false), and N % 8 = N % 4 = 2 ends both store loops in
+    their scalar tail (every other N tested here is a multiple of 8).  Values as in
+    test_gemm_fp8_against_fp64_on_the_quantised_operands; nothing outside the N columns is written."""
+    M, N, K = 130, 90, 128
+    a = torch.randn(M, K, generator=g(2)) * torch.logspace(-1, 1, M)[:, None]
+    w = torch.randn(N, K, generator=g(3)) * 0.05 * torch.logspace(-1, 0.5, N)[:, None]
+    bias = (torch.randn(N, generator=g(4)) * 0.1).to(dev)
+    aq, sa = ops.quantize_rows_fp8(a.to(dev))
+    wq, sw = ops.quantize_rows_fp8(w.to(dev))
+    ref = (aq.double() * sa.double()[:, None]) @ (wq.double() * sw.double()[:, None]).T + bias.double()
+    mag = (aq.double().abs() * sa.double()[:, None]) @ (wq.double().abs() * sw.double()[:, None]).T + 1.0
+
+    def edge_bits(buf):
+        edge = torch.cat([buf[:, :1], buf[:, N + 1:]], 1).contiguous()
+        return edge.view(torch.int16 if edge.element_size() == 2 else torch.int32)
+
+    buf = torch.full((M, N + 3), -7.0, dtype=torch.bfloat16, device=dev)
+    clean = edge_bits(buf)
+    ops.gemm_fp8(aq, sa, wq, sw, bias, _lib.EPI_BF16, out=buf[:, 1:1 + N])
+    err = ((buf[:, 1:1 + N].double() - ref).abs() / mag).max().item()
+    assert err < 2.0 ** -8, err
+    assert torch.equal(edge_bits(buf), clean)
+    c0 = torch.randn(M, N, generator=g(5)).to(dev)
+    buf = torch.full((M, N + 3), -7.0, device=dev)
+    clean = edge_bits(buf)
+    buf[:, 1:1 + N] = c0
+    ops.gemm_fp8(aq, sa, wq, sw, bias, _lib.EPI_RESID_F32, out=buf[:, 1:1 + N])
+    err = ((buf[:, 1:1 + N].double() - (ref + c0.double())).abs() / mag).max().item()
+    assert err < 2e-5, err
+    assert torch.equal(edge_bits(buf), clean)
+
+
 @pytest.mark.parametrize("arch,patch,heads,S,depth,B", [("vit_small", 8, 6, 224, 4, 2), ("vit_base", 14, 12, 518, 12, 1)])
 def test_backbone_fp8_accuracy_gate(dev, arch, patch, heads, S, depth, B):
     """configs[4]: DINOv2 ViT-B/14 at 518^2 (and ViT-S/8) with the block linears on e4m3.  Gate: relative L2 error of the final

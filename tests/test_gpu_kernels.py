@@ -68,6 +68,49 @@ def test_gemm_bf16_transpose_detecting_and_strided(dev):
     assert torch.equal(out[:, :N].float().cpu(), want.clamp(min=0)) and float(out[:, N:].abs().sum()) == 0.0
 
 
+def _edge_bits(buf, N):
+    """columns 0 and N + 1.. of a [..., N + 3] buffer, as integers"""
+    edge = torch.cat([buf[..., :1], buf[..., N + 1:]], -1).contiguous()
+    return edge.view(torch.int16 if edge.element_size() == 2 else torch.int32)
+
+
+def test_gemm_bf16_unaligned_odd_ldc_output_with_n_tail(dev):
+    """The output is columns 1..N of a sentinel-filled [M, N + 3] buffer: ldc is odd and C is off 16-byte alignment, so the tiled
+    kernel stores element by element (csrc/tile_epilogue.h, vec_ok == false), and N % 8 = N % 4 = 2 ends both store loops in
+    their scalar tail.  Values as in test_gemm_bf16_epilogues; nothing outside the N columns is written."""
+    M, N, K = 130, 90, 128
+    a = bf(torch.randn(M, K, generator=g(1)))
+    w = bf(torch.randn(N, K, generator=g(2)) * 0.1)
+    bias = torch.randn(N, generator=g(3))
+    ref = a.float() @ w.float().T + bias
+    ad, wd, bd = a.to(dev), w.to(dev), bias.to(dev)
+    scale = ref.abs().max().item()
+    buf = torch.full((M, N + 3), -7.0, dtype=torch.bfloat16, device=dev)
+    clean = _edge_bits(buf, N)
+    ops.gemm_bf16(ad, wd, bd, _lib.EPI_BF16, out=buf[:, 1:1 + N])
+    assert (buf[:, 1:1 + N].float().cpu() - ref).abs().max().item() < 8e-3 * scale, "bf16-out epilogue (1 bf16 ulp of the result)"
+    assert torch.equal(_edge_bits(buf, N), clean)
+    c0 = torch.randn(M, N, generator=g(4))
+    buf = torch.full((M, N + 3), -7.0, device=dev)
+    clean = _edge_bits(buf, N)
+    buf[:, 1:1 + N] = c0.to(dev)
+    ops.gemm_bf16(ad, wd, bd, _lib.EPI_RESID_F32, out=buf[:, 1:1 + N])
+    assert (buf[:, 1:1 + N].cpu() - (c0 + ref)).abs().max().item() < 2e-5 * scale * math.sqrt(K)
+    assert torch.equal(_edge_bits(buf, N), clean)
+
+
+def test_gemm_bf16_accum_epilogue_is_the_residual_arithmetic(dev):
+    """EPI_ACCUM_F32 (the second GEMM of a sum) is documented as the arithmetic of EPI_RESID_F32: the same bits."""
+    M, N, K = 130, 90, 128
+    ad = bf(torch.randn(M, K, generator=g(1))).to(dev)
+    wd = bf(torch.randn(N, K, generator=g(2)) * 0.1).to(dev)
+    bd = torch.randn(N, generator=g(3)).to(dev)
+    c0 = torch.randn(M, N, generator=g(4)).to(dev)
+    resid = ops.gemm_bf16(ad, wd, bd, _lib.EPI_RESID_F32, out=c0.clone())
+    assert torch.equal(ops.gemm_bf16(ad, wd, bd, _lib.EPI_ACCUM_F32, out=c0.clone()), resid)
+    assert not torch.equal(resid, c0)
+
+
 @pytest.mark.parametrize("ta,tb", [(False, True), (False, False), (True, False), (True, True)])
 def test_gemm_f32_layouts_and_epilogues(dev, ta, tb):
     M, N, K = 150, 97, 203

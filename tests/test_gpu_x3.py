@@ -60,6 +60,50 @@ def test_gemm_x3_is_fp32_class(dev, M, N, K, epi):
     assert err < (2.0 ** -9) / 50
 
 
+def test_gemm_x3_unaligned_odd_ldc_output_with_n_tail(dev):
+    """The output is columns 1..N of a sentinel-filled [2, M, N + 3] (planes) or [M, N + 3] (fp32) buffer: ldc is odd and C is off
+    16-byte alignment, so the tiled kernel stores element by element (csrc/tile_epilogue.h, vec_ok == false), and N % 8 = N % 4 = 2
+    ends both store loops in their scalar tail.  Values as in test_gemm_x3_is_fp32_class; nothing outside the N columns is written."""
+    M, N, K = 130, 90, 128
+    a = torch.randn(M, K, generator=g(1)).to(dev)
+    w = (torch.randn(N, K, generator=g(2)) * 0.05).to(dev)
+    bias = (torch.randn(N, generator=g(3)) * 0.1).to(dev)
+    ref = a.double() @ w.double().T + bias.double()
+    mag = a.double().abs() @ w.double().abs().T + bias.double().abs()
+    ap, wp = ops.split_planes(a), ops.split_planes(w)
+
+    def edge_bits(buf):
+        edge = torch.cat([buf[..., :1], buf[..., N + 1:]], -1).contiguous()
+        return edge.view(torch.int16 if edge.element_size() == 2 else torch.int32)
+
+    buf = torch.full((2, M, N + 3), -7.0, dtype=torch.bfloat16, device=dev)
+    clean = edge_bits(buf)
+    ops.gemm_x3(ap, wp, bias, _lib.EPI_BF16, out=buf[:, :, 1:1 + N])
+    err = ((unsplit(buf[:, :, 1:1 + N]) - ref).abs() / mag).max().item()
+    assert err < 4e-5, err
+    assert torch.equal(edge_bits(buf), clean)
+    c0 = torch.randn(M, N, generator=g(4)).to(dev)
+    buf = torch.full((M, N + 3), -7.0, device=dev)
+    clean = edge_bits(buf)
+    buf[:, 1:1 + N] = c0
+    ops.gemm_x3(ap, wp, bias, _lib.EPI_RESID_F32, out=buf[:, 1:1 + N])
+    err = ((buf[:, 1:1 + N].double() - (ref + c0.double())).abs() / (mag + c0.double().abs())).max().item()
+    assert err < 4e-5, err
+    assert torch.equal(edge_bits(buf), clean)
+
+
+def test_gemm_x3_accum_epilogue_is_the_residual_arithmetic(dev):
+    """EPI_ACCUM_F32 (the second GEMM of a sum) is documented as the arithmetic of EPI_RESID_F32: the same bits."""
+    M, N, K = 130, 90, 128
+    ap = ops.split_planes(torch.randn(M, K, generator=g(1)).to(dev))
+    wp = ops.split_planes((torch.randn(N, K, generator=g(2)) * 0.05).to(dev))
+    bias = (torch.randn(N, generator=g(3)) * 0.1).to(dev)
+    c0 = torch.randn(M, N, generator=g(4)).to(dev)
+    resid = ops.gemm_x3(ap, wp, bias, _lib.EPI_RESID_F32, out=c0.clone())
+    assert torch.equal(ops.gemm_x3(ap, wp, bias, _lib.EPI_ACCUM_F32, out=c0.clone()), resid)
+    assert not torch.equal(resid, c0)
+
+
 def _attention_ref(q, k, v, scale):
     s = (q.double() @ k.double().transpose(-1, -2)) * scale
     return (s.softmax(-1) @ v.double())

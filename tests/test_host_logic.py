@@ -122,7 +122,7 @@ def test_gelu_polynomial_is_within_a_quarter_bf16_ulp_of_erf_gelu():
 
 
 def test_gelu_degree6_form_is_within_3e_7_of_erf_gelu():
-    """The split-operand fc1 epilogue (csrc/gemm_a384_x3.hip) evaluates GELU as max(x, 0) - a 2^R(a), a = min(|x|, 7), R a degree-6
+    """The split-operand and fp8 fc1 epilogues (gelu_pair, csrc/common.h) evaluate GELU as max(x, 0) - a 2^R(a), a = min(|x|, 7), R a degree-6
     polynomial fitted to log2 erfc(a / sqrt 2) - 1.  This pins the claim in its comment: within 2.8e-7 ABSOLUTE of the exact erf GELU of
     torch.nn.GELU on the whole line with fp32 Horner evaluation (the Abramowitz-Stegun form it replaced: 1.5e-7 on erf)."""
     import numpy as np

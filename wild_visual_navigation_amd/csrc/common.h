@@ -150,6 +150,37 @@ __device__ inline float bilerp_fixed(float v00, float v01, float v10, float v11,
 }
 
 __device__ inline float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+#if defined(__HIPCC__)
+// erf GELU to fp32 rounding with ONE transcendental: for a = |x|
+//     gelu(x) = max(x, 0) - a * erfc(a / sqrt 2) / 2 = max(x, 0) - a * 2^R(a),     R(a) = log2 erfc(a / sqrt 2) - 1
+// R is smooth and nearly quadratic; a degree-6 polynomial fitted with the weight a * erfc(a / sqrt 2) (the derivative of the result with
+// respect to R) reproduces gelu within 2.8e-7 absolute on the whole line (float64 erfc reference, fp32 Horner; weighted least squares
+// reweighted towards minimax on [0, 7]; tests/test_host_logic.py pins the bound) -- the same as Abramowitz-Stegun 7.1.26 (1.5e-7 on erf), which this
+// replaces: that form costs 15 VALU operations and TWO transcendentals (v_rcp, v_exp: four issue slots each) per value, and the fc1
+// epilogue of gemm_a384_x3.hip rides in the shadow of the MFMAs of a wave that is alone on its SIMD (fc1 18.6 -> 17.6 ms per 64-frame step of the mixed mode).
+// (The same idea with a cubic R in the fp16 path's mlp_fused kernel: 22.8 -> 22.55 ms per step, headline within the noise, and it gives
+//  up that path's RELATIVE accuracy on the negative tail -- not adopted.)
+// Beyond a = 7 the subtracted term is below 1e-11: a is clamped there (the polynomial is only trusted on the fitted interval).
+// Two values at a time: the polynomial and the final fma on v_pk_fma_f32 (written on vectors: left to hipcc the scalar form becomes
+// v_fmaak_f32 with literal constants, one issue slot per value and step).
+__device__ inline void gelu_pair(float& x0, float& x1) {
+  typedef __attribute__((ext_vector_type(2))) float f2;
+  const f2 a = {__builtin_amdgcn_fmed3f(__builtin_fabsf(x0), 0.f, 7.0f), __builtin_amdgcn_fmed3f(__builtin_fabsf(x1), 0.f, 7.0f)};
+  const f2 c6 = {3.309327076e-05f, 3.309327076e-05f}, c5 = {-7.692237268e-04f, -7.692237268e-04f}, c4 = {8.080729283e-03f, 8.080729283e-03f},
+           c3 = {-5.341212451e-02f, -5.341212451e-02f}, c2 = {-4.587709606e-01f, -4.587709606e-01f}, c1 = {-1.151201725e+00f, -1.151201725e+00f},
+           c0 = {-9.999930859e-01f, -9.999930859e-01f};
+  f2 r = __builtin_elementwise_fma(a, c6, c5);
+  r = __builtin_elementwise_fma(a, r, c4);
+  r = __builtin_elementwise_fma(a, r, c3);
+  r = __builtin_elementwise_fma(a, r, c2);
+  r = __builtin_elementwise_fma(a, r, c1);
+  r = __builtin_elementwise_fma(a, r, c0);
+  const f2 e = {__builtin_amdgcn_exp2f(r[0]), __builtin_amdgcn_exp2f(r[1])};
+  const f2 m = {__builtin_amdgcn_fmed3f(x0, 0.f, 3.0e38f), __builtin_amdgcn_fmed3f(x1, 0.f, 3.0e38f)};   // max(x, 0) in ONE v_med3 (fmaxf: canonicalise + v_max)
+  const f2 g = __builtin_elementwise_fma(-a, e, m);
+  x0 = g[0]; x1 = g[1];
+}
+#endif
 __device__ inline float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // Observed dispatch places block b on XCD b % 8 (guide T1).  Remap the linear block id so each XCD

@@ -77,35 +77,6 @@ __device__ inline void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
   const float ah = __uint_as_float(hi << 16), bh = __uint_as_float(hi & 0xffff0000u);
   lo = pack_bf16x2(a - ah, b - bh);
 }
-// erf GELU to fp32 rounding with ONE transcendental: for a = |x|
-//     gelu(x) = max(x, 0) - a * erfc(a / sqrt 2) / 2 = max(x, 0) - a * 2^R(a),     R(a) = log2 erfc(a / sqrt 2) - 1
-// R is smooth and nearly quadratic; a degree-6 polynomial fitted with the weight a * erfc(a / sqrt 2) (the derivative of the result with
-// respect to R) reproduces gelu within 2.8e-7 absolute on the whole line (float64 erfc reference, fp32 Horner; weighted least squares
-// reweighted towards minimax on [0, 7]; tests/test_host_logic.py pins the bound) -- the same as Abramowitz-Stegun 7.1.26 (1.5e-7 on erf), which this
-// replaces: that form costs 15 VALU operations and TWO transcendentals (v_rcp, v_exp: four issue slots each) per value, and the fc1
-// epilogue rides in the shadow of the MFMAs of a wave that is alone on its SIMD (fc1 18.6 -> 17.6 ms per 64-frame step of the mixed mode).
-// (The same idea with a cubic R in the fp16 path's mlp_fused kernel: 22.8 -> 22.55 ms per step, headline within the noise, and it gives
-//  up that path's RELATIVE accuracy on the negative tail -- not adopted.)
-// Beyond a = 7 the subtracted term is below 1e-11: a is clamped there (the polynomial is only trusted on the fitted interval).
-// Two values at a time: the polynomial and the final fma on v_pk_fma_f32 (written on vectors: left to hipcc the scalar form becomes
-// v_fmaak_f32 with literal constants, one issue slot per value and step).
-__device__ inline void gelu_pair(float& x0, float& x1) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  const f2 a = {__builtin_amdgcn_fmed3f(__builtin_fabsf(x0), 0.f, 7.0f), __builtin_amdgcn_fmed3f(__builtin_fabsf(x1), 0.f, 7.0f)};
-  const f2 c6 = {3.309327076e-05f, 3.309327076e-05f}, c5 = {-7.692237268e-04f, -7.692237268e-04f}, c4 = {8.080729283e-03f, 8.080729283e-03f},
-           c3 = {-5.341212451e-02f, -5.341212451e-02f}, c2 = {-4.587709606e-01f, -4.587709606e-01f}, c1 = {-1.151201725e+00f, -1.151201725e+00f},
-           c0 = {-9.999930859e-01f, -9.999930859e-01f};
-  f2 r = __builtin_elementwise_fma(a, c6, c5);
-  r = __builtin_elementwise_fma(a, r, c4);
-  r = __builtin_elementwise_fma(a, r, c3);
-  r = __builtin_elementwise_fma(a, r, c2);
-  r = __builtin_elementwise_fma(a, r, c1);
-  r = __builtin_elementwise_fma(a, r, c0);
-  const f2 e = {__builtin_amdgcn_exp2f(r[0]), __builtin_amdgcn_exp2f(r[1])};
-  const f2 m = {__builtin_amdgcn_fmed3f(x0, 0.f, 3.0e38f), __builtin_amdgcn_fmed3f(x1, 0.f, 3.0e38f)};   // max(x, 0) in ONE v_med3 (fmaxf: canonicalise + v_max)
-  const f2 g = __builtin_elementwise_fma(-a, e, m);
-  x0 = g[0]; x1 = g[1];
-}
 
 // MX (round 6; LNA only, X_GELU_FRAG / X_QKV_F16): the operand representation of gemm_n384_x3.hip's MX kernel -- h = fp16(v), l8 = e5m2((v - h) * 2^12),
 // h8 = e5m2(v) -- for both operands: per k-step region TWO fp16 MFMAs (hi * hi of the two column halves) and ONE scaled e5m2 MFMA of K = 64 (one of

@@ -43,25 +43,6 @@ constexpr int STG = 1024;                    // per wave: HALF a bf16 tile image
 constexpr int LDS_BYTES = NS * TILE_BYTES + 4 * STG;   // 76 KB: two workgroups per CU
 static_assert(PIECES == 6, "six DMA pieces per wave and tile");
 
-// erf GELU to fp32 rounding with one transcendental (gemm_a384_x3.hip: gelu_pair; tests/test_host_logic.py pins its 2.8e-7 bound)
-__device__ inline void gelu_pair8(float& x0, float& x1) {
-  typedef __attribute__((ext_vector_type(2))) float f2;
-  const f2 a = {__builtin_amdgcn_fmed3f(__builtin_fabsf(x0), 0.f, 7.0f), __builtin_amdgcn_fmed3f(__builtin_fabsf(x1), 0.f, 7.0f)};
-  const f2 c6 = {3.309327076e-05f, 3.309327076e-05f}, c5 = {-7.692237268e-04f, -7.692237268e-04f}, c4 = {8.080729283e-03f, 8.080729283e-03f},
-           c3 = {-5.341212451e-02f, -5.341212451e-02f}, c2 = {-4.587709606e-01f, -4.587709606e-01f}, c1 = {-1.151201725e+00f, -1.151201725e+00f},
-           c0 = {-9.999930859e-01f, -9.999930859e-01f};
-  f2 r = __builtin_elementwise_fma(a, c6, c5);
-  r = __builtin_elementwise_fma(a, r, c4);
-  r = __builtin_elementwise_fma(a, r, c3);
-  r = __builtin_elementwise_fma(a, r, c2);
-  r = __builtin_elementwise_fma(a, r, c1);
-  r = __builtin_elementwise_fma(a, r, c0);
-  const f2 e = {__builtin_amdgcn_exp2f(r[0]), __builtin_amdgcn_exp2f(r[1])};
-  const f2 m = {__builtin_amdgcn_fmed3f(x0, 0.f, 3.0e38f), __builtin_amdgcn_fmed3f(x1, 0.f, 3.0e38f)};
-  const f2 g = __builtin_elementwise_fma(-a, e, m);
-  x0 = g[0]; x1 = g[1];
-}
-
 // (Non-temporal stores and A loads were tried: the weight then stays in the XCD's L2 -- fc1's HBM reads 248 -> 92 MB -- and every kernel is a third SLOWER.
 //  Same data-register guard as wvn_store_b128_guarded, common.h.)
 __device__ inline void store_b128_nt(u32x4_t v, __amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
@@ -268,7 +249,7 @@ __global__ __launch_bounds__(256, 2) void gemm_a768_fp8_kernel(A768Params p) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           float x0 = v[2 * k], x1 = v[2 * k + 1];
-          gelu_pair8(x0, x1);
+          gelu_pair(x0, x1);
           v[2 * k] = x0; v[2 * k + 1] = x1;
           am = fmaxf(am, fmaxf(__builtin_fabsf(x0), __builtin_fabsf(x1)));
         }
@@ -317,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void gemm_a768_fp8_kernel(A768Params p) {
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
             float x0 = v[4 * g + 2 * k] * qs, x1 = v[4 * g + 2 * k + 1] * qs;
-            if constexpr (EPI == E_GELU) gelu_pair8(x0, x1);
+            if constexpr (EPI == E_GELU) gelu_pair(x0, x1);
             h[2 * g + k] = pack_bf16x2(x0, x1);
           }
         stage_and_store(h, so, false, 0);

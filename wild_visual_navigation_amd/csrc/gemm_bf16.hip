@@ -17,11 +17,13 @@
 // through the (now idle) operand LDS as a row-major image and leaves the CU as 16-byte, fully
 // coalesced stores (256 contiguous bytes per 16 lanes).  The V third of the QKV projection uses the
 // un-transposed orientation instead, so its LDS image is [d][token] and V^T ([b,h,d,token], what the
-// attention kernel's PV MFMA wants) is written with the same wide stores.
+// attention kernel's PV MFMA wants) is written with the same wide stores.  The stores of the image
+// are tile_epilogue.h, shared with gemm_x3.hip and gemm_fp8.hip.
 //
 // Fragment maps (v_mfma_f32_32x32x16_bf16): A: lane l holds row l&31, k-slots (l>>5)*8+j;
 // B: lane l holds col l&31, same k-slots; C/D: col = l&31, row = (r&3) + 8*(r>>2) + 4*(l>>5).
 #include "operand.h"
+#include "tile_epilogue.h"
 #include "wvn_internal.h"
 
 namespace {
@@ -30,33 +32,7 @@ constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int LDS_STRIDE = BK + 8;                       // bf16 elements per LDS row (144 B)
 constexpr int STAGE_ELEMS = (BM + BN) * LDS_STRIDE;      // per stage
 constexpr int GEMM_LDS_BYTES = 2 * STAGE_ELEMS * 2;      // 73,728 B
-constexpr int CT_BF16_STRIDE = 128 + 8;                  // output-tile image, bf16 elements per row (272 B)
-constexpr int CT_F32_STRIDE = 128 + 4;                   // output-tile image, floats per row (528 B)
 static_assert(128 * CT_F32_STRIDE * 4 <= GEMM_LDS_BYTES, "fp32 tile image must fit in the operand LDS");
-
-// erf by Abramowitz-Stegun 7.1.26 (|abs err| < 1.5e-7, far below bf16 resolution of the output)
-__device__ inline float gelu_bf16path(float x) {
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = __frcp_rn(fmaf(0.3275911f, z, 1.0f));
-  float p = fmaf(t, 1.061405429f, -1.453152027f);
-  p = fmaf(t, p, 1.421413741f);
-  p = fmaf(t, p, -0.284496736f);
-  p = fmaf(t, p, 0.254829592f);
-  const float e = 1.0f - p * t * __expf(-z * z);
-  return 0.5f * x * (1.0f + copysignf(e, x));
-}
-
-template <int EPI>
-__device__ inline float activate(float v) {
-  if constexpr (EPI == EPI_GELU_BF16) return gelu_bf16path(v);
-  if constexpr (EPI == EPI_RELU_BF16) return fmaxf(v, 0.f);
-  return v;
-}
-
-template <int EPI>
-constexpr bool out_is_bf16() {
-  return EPI == EPI_BF16 || EPI == EPI_GELU_BF16 || EPI == EPI_RELU_BF16 || EPI == EPI_QKV;
-}
 
 // TR = true : accumulators hold C^T (lane = row m, regs = cols n)  -> LDS image [m][n]
 // TR = false: accumulators hold C   (lane = col n, regs = rows m)  -> LDS image [n][m]   (V^T tiles)
@@ -172,7 +148,7 @@ __device__ inline void gemm_tile(const GemmBf16Params& p, int tm, int tn, unsign
 
   // ---------------- epilogue, part 1: registers -> LDS tile image (bias + activation applied) ----------
   // image row = "lane" dimension, image col = "register" dimension (4 consecutive per register group)
-  constexpr bool OB = out_is_bf16<EPI>();
+  constexpr bool OB = out_is_16bit<EPI>();
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -203,7 +179,7 @@ __device__ inline void gemm_tile(const GemmBf16Params& p, int tm, int tn, unsign
         }
         if constexpr (OB) {
           u32x2_t o = {pack_op2(v[0], v[1]), pack_op2(v[2], v[3])};
-          *(u32x2_t*)((op16_t*)smem + lane_dim * CT_BF16_STRIDE + c) = o;
+          *(u32x2_t*)((op16_t*)smem + lane_dim * CT_16_STRIDE + c) = o;
         } else {
           f32x4_t o = {v[0], v[1], v[2], v[3]};
           *(f32x4_t*)((float*)smem + lane_dim * CT_F32_STRIDE + c) = o;
@@ -212,78 +188,15 @@ __device__ inline void gemm_tile(const GemmBf16Params& p, int tm, int tn, unsign
     }
   __syncthreads();
 
-  // ---------------- epilogue, part 2: LDS image -> global, 16-byte coalesced --------------------------
+  // ---------------- epilogue, part 2: LDS image -> global, 16-byte coalesced (tile_epilogue.h) -----------
   if constexpr (EPI == EPI_QKV) {
     const int D = p.N / 3;
     const int which = n0 / D;  // tile-uniform (D % 128 == 0)
-    const int cbase = n0 - which * D;
-    if constexpr (TR) {  // q / k : image [m][n]; dst[(b*h + head)*npad + t][d]
-      op16_t* dst = which == 0 ? p.q : p.k;
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int ch = tid + 256 * it, row = ch >> 4, c8 = (ch & 15) * 8;
-        const int m = m0 + row;
-        if (m >= p.M) continue;
-        const int b = m / p.ntok_s, t = m - b * p.ntok_s;
-        const int cc = cbase + c8, head = cc >> 6, d = cc & 63;
-        const u32x4_t val = *(const u32x4_t*)((const op16_t*)smem + row * CT_BF16_STRIDE + c8);
-        *(u32x4_t*)(dst + (((size_t)b * p.heads + head) * p.npad + t) * 64 + d) = val;
-      }
-    } else {  // v : image [n = (head, d)][m]; vt[(b*h + head)*64 + d][t], 8 tokens per store
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int ch = tid + 256 * it, row = ch >> 4, c8 = (ch & 15) * 8;
-        const int m = m0 + c8;
-        if (m >= p.M) continue;  // M % 16 == 0 (ntok_s % 16 == 0): a chunk (and its permutation group of 16) is entirely in or out
-        const int b = m / p.ntok_s, t = m - b * p.ntok_s;
-        const int cc = cbase + row, head = cc >> 6, d = cc & 63;
-        const u32x4_t val = *(const u32x4_t*)((const op16_t*)smem + row * CT_BF16_STRIDE + c8);
-        *(u32x4_t*)(p.vt + (((size_t)b * p.heads + head) * 64 + d) * p.npad + t) = val;
-      }
-    }
+    tile_store_qkv<TR>(p, (const op16_t*)smem, TR ? (which == 0 ? p.q : p.k) : p.vt, m0, n0 - which * D);
   } else if constexpr (OB) {
-    op16_t* C = (op16_t*)p.C;
-    const bool vec_ok = ((p.ldc & 7) == 0) && (((uintptr_t)C & 15) == 0);
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int ch = tid + 256 * it, row = ch >> 4, c8 = (ch & 15) * 8;
-      const int m = m0 + row, n = n0 + c8;
-      if (m >= p.M || n >= p.N) continue;
-      const op16_t* src = (const op16_t*)smem + row * CT_BF16_STRIDE + c8;
-      if (vec_ok && n + 8 <= p.N) {
-        *(u32x4_t*)(C + (size_t)m * p.ldc + n) = *(const u32x4_t*)src;
-      } else {
-        for (int e = 0; e < 8 && n + e < p.N; ++e) C[(size_t)m * p.ldc + n + e] = src[e];
-      }
-    }
+    tile_store_16bit(p, (const op16_t*)smem, (op16_t*)p.C, m0, n0);
   } else {
-    float* C = (float*)p.C;
-    const bool vec_ok = ((p.ldc & 3) == 0) && (((uintptr_t)C & 15) == 0);
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      const int ch = tid + 256 * it, row = ch >> 5, c4 = (ch & 31) * 4;
-      const int m = m0 + row, n = n0 + c4;
-      if (m >= p.M || n >= p.N) continue;
-      f32x4_t v = *(const f32x4_t*)((const float*)smem + row * CT_F32_STRIDE + c4);
-      size_t orow = (size_t)m;
-      if constexpr (EPI == EPI_PATCH) {
-        const int b = m / p.npatch, pp = m - b * p.npatch;
-        orow = (size_t)b * p.ntok_s + 1 + pp;
-        const f32x4_t pe = *(const f32x4_t*)(p.pos + (size_t)(1 + pp) * p.ldc + n);  // ldc == D, n % 4 == 0
-        v += pe;
-      }
-      float* dst = C + orow * p.ldc + n;
-      if (vec_ok && n + 4 <= p.N) {
-        if constexpr (EPI == EPI_RESID_F32 || EPI == EPI_ACCUM_F32) v += *(const f32x4_t*)dst;
-        *(f32x4_t*)dst = v;
-      } else {
-        for (int e = 0; e < 4 && n + e < p.N; ++e) {
-          float o = v[e];
-          if constexpr (EPI == EPI_RESID_F32 || EPI == EPI_ACCUM_F32) o += dst[e];
-          dst[e] = o;
-        }
-      }
-    }
+    tile_store_f32<EPI>(p, (const float*)smem, (float*)p.C, m0, n0);
   }
 }
 

@@ -14,8 +14,10 @@
 //   loop is unrolled by two so register slots and LDS stages are compile-time.
 //
 // Outputs that feed another MFMA (LayerNorm'd activations, q/k/v, the GELU'd hidden layer) leave the epilogue as hi/lo
-// planes; the residual stream stays fp32.  GELU is the exact erf form (torch.nn.GELU default, as the oracle), erf to 1.5e-7.
+// planes; the residual stream stays fp32.  GELU is the exact erf form (torch.nn.GELU default, as the oracle), erf to 1.5e-7
+// (tile_epilogue.h: gelu_as, with the stores of the tile images, which this kernel shares with gemm_bf16.hip and gemm_fp8.hip).
 #include "common.h"
+#include "tile_epilogue.h"
 #include "wvn_internal.h"
 
 namespace {
@@ -25,9 +27,7 @@ constexpr int LSTR = BK + 8;                          // bf16 elements per LDS r
 constexpr int PLANE = 128 * LSTR;                     // one operand plane of a stage
 constexpr int STAGE = 4 * PLANE;                      // A hi | A lo | W hi | W lo
 constexpr int X3_LDS_BYTES = 2 * STAGE * 2;           // 81,920 B
-constexpr int CT_BF16_STRIDE = 128 + 8;               // output image, bf16 elements per row
-constexpr int CT_PLANE = 128 * CT_BF16_STRIDE;        // one output plane image (34,816 B)
-constexpr int CT_F32_STRIDE = 128 + 4;
+constexpr int CT_PLANE = 128 * CT_16_STRIDE;          // one output plane image (34,816 B)
 static_assert(2 * CT_PLANE * 2 <= X3_LDS_BYTES, "two bf16 plane images must fit in the operand LDS");
 static_assert(128 * CT_F32_STRIDE * 4 <= X3_LDS_BYTES, "fp32 tile image must fit in the operand LDS");
 
@@ -36,31 +36,6 @@ __device__ inline void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
   hi = pack_bf16x2(a, b);
   const float ah = __uint_as_float(hi << 16), bh = __uint_as_float(hi & 0xffff0000u);
   lo = pack_bf16x2(a - ah, b - bh);
-}
-
-// exact erf GELU with erf by Abramowitz-Stegun 7.1.26 (|abs err| < 1.5e-7: fp32-class, like everything else in this mode)
-// instead of libm's erff, whose ~40 VALU per element doubled the fc1 kernel's time
-__device__ inline float gelu_as(float x) {
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = __frcp_rn(fmaf(0.3275911f, z, 1.0f));
-  float p = fmaf(t, 1.061405429f, -1.453152027f);
-  p = fmaf(t, p, 1.421413741f);
-  p = fmaf(t, p, -0.284496736f);
-  p = fmaf(t, p, 0.254829592f);
-  const float e = 1.0f - p * t * __expf(-z * z);
-  return 0.5f * x * (1.0f + copysignf(e, x));
-}
-
-template <int EPI>
-__device__ inline float activate(float v) {
-  if constexpr (EPI == EPI_GELU_BF16) return gelu_as(v);
-  if constexpr (EPI == EPI_RELU_BF16) return fmaxf(v, 0.f);
-  return v;
-}
-
-template <int EPI>
-constexpr bool out_is_planes() {
-  return EPI == EPI_BF16 || EPI == EPI_GELU_BF16 || EPI == EPI_RELU_BF16 || EPI == EPI_QKV;
 }
 
 // TR = true : accumulators hold C^T (lane = row m, regs = cols n)  -> LDS image [m][n]
@@ -159,7 +134,7 @@ __device__ inline void gemm_x3_tile(const GemmBf16Params& p, int tm, int tn, uns
   }
 
   // ---------------- epilogue, part 1: registers -> LDS tile image(s) (bias + activation applied) ----------
-  constexpr bool OP = out_is_planes<EPI>();
+  constexpr bool OP = out_is_16bit<EPI>();
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -193,12 +168,12 @@ __device__ inline void gemm_x3_tile(const GemmBf16Params& p, int tm, int tn, uns
               wvn_split2_f16(v[0] * qs, v[1] * qs, h0, l0);
               wvn_split2_f16(v[2] * qs, v[3] * qs, h1, l1);
               const u32x2_t oh = {h0, h1}, ol = {l0, l1};
-              *(u32x2_t*)((bf16_t*)smem + lane_dim * CT_BF16_STRIDE + c) = oh;
-              *(u32x2_t*)((bf16_t*)smem + CT_PLANE + lane_dim * CT_BF16_STRIDE + c) = ol;
+              *(u32x2_t*)((bf16_t*)smem + lane_dim * CT_16_STRIDE + c) = oh;
+              *(u32x2_t*)((bf16_t*)smem + CT_PLANE + lane_dim * CT_16_STRIDE + c) = ol;
               continue;
             }
             const u32x2_t oh = {pack_f16x2(v[0] * qs, v[1] * qs), pack_f16x2(v[2] * qs, v[3] * qs)};
-            *(u32x2_t*)((bf16_t*)smem + lane_dim * CT_BF16_STRIDE + c) = oh;
+            *(u32x2_t*)((bf16_t*)smem + lane_dim * CT_16_STRIDE + c) = oh;
             continue;
           }
         }
@@ -207,8 +182,8 @@ __device__ inline void gemm_x3_tile(const GemmBf16Params& p, int tm, int tn, uns
           split2(v[0], v[1], h0, l0);
           split2(v[2], v[3], h1, l1);
           const u32x2_t oh = {h0, h1}, ol = {l0, l1};
-          *(u32x2_t*)((bf16_t*)smem + lane_dim * CT_BF16_STRIDE + c) = oh;
-          *(u32x2_t*)((bf16_t*)smem + CT_PLANE + lane_dim * CT_BF16_STRIDE + c) = ol;
+          *(u32x2_t*)((bf16_t*)smem + lane_dim * CT_16_STRIDE + c) = oh;
+          *(u32x2_t*)((bf16_t*)smem + CT_PLANE + lane_dim * CT_16_STRIDE + c) = ol;
         } else {
           f32x4_t o = {v[0], v[1], v[2], v[3]};
           *(f32x4_t*)((float*)smem + lane_dim * CT_F32_STRIDE + c) = o;
@@ -217,86 +192,22 @@ __device__ inline void gemm_x3_tile(const GemmBf16Params& p, int tm, int tn, uns
     }
   __syncthreads();
 
-  // ---------------- epilogue, part 2: LDS image -> global, 16-byte coalesced --------------------------
+  // ---------------- epilogue, part 2: LDS image(s) -> global, 16-byte coalesced (tile_epilogue.h), a plane at a time ----------
   if constexpr (EPI == EPI_QKV) {
     const int D = p.N / 3;
     const int which = n0 / D;  // tile-uniform (D % 128 == 0)
-    const int cbase = n0 - which * D;
 #pragma unroll
     for (int pl = 0; pl < 2; ++pl) {
       if (pl == 1 && p.qkv_f16 && !(p.q_lo && which == 0)) break;   // (uniform) single fp16 plane, except a two-plane q
-      const bf16_t* img = (const bf16_t*)smem + pl * CT_PLANE;
-      if constexpr (TR) {  // q / k : image [m][n]; dst[(b*h + head)*npad + t][d]
-        bf16_t* dst = which == 0 ? (pl ? p.q_lo : p.q) : (pl ? p.k_lo : p.k);
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int ch = tid + 256 * it, row = ch >> 4, c8 = (ch & 15) * 8;
-          const int m = m0 + row;
-          if (m >= p.M) continue;
-          const int b = m / p.ntok_s, t = m - b * p.ntok_s;
-          const int cc = cbase + c8, head = cc >> 6, d = cc & 63;
-          *(u32x4_t*)(dst + (((size_t)b * p.heads + head) * p.npad + t) * 64 + d) = *(const u32x4_t*)(img + row * CT_BF16_STRIDE + c8);
-        }
-      } else {  // v : image [n = (head, d)][m]; vt[(b*h + head)*64 + d][t], 8 tokens per store
-        bf16_t* dst = pl ? p.vt_lo : p.vt;
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int ch = tid + 256 * it, row = ch >> 4, c8 = (ch & 15) * 8;
-          const int m = m0 + c8;
-          if (m >= p.M) continue;  // M % 16 == 0: a chunk (and its permutation group of 16) is entirely in or out
-          const int b = m / p.ntok_s, t = m - b * p.ntok_s;
-          const int cc = cbase + row, head = cc >> 6, d = cc & 63;
-          *(u32x4_t*)(dst + (((size_t)b * p.heads + head) * 64 + d) * p.npad + t) = *(const u32x4_t*)(img + row * CT_BF16_STRIDE + c8);
-        }
-      }
+      bf16_t* dst = TR ? (which == 0 ? (pl ? p.q_lo : p.q) : (pl ? p.k_lo : p.k)) : (pl ? p.vt_lo : p.vt);
+      tile_store_qkv<TR>(p, (const bf16_t*)smem + pl * CT_PLANE, dst, m0, n0 - which * D);
     }
   } else if constexpr (OP) {
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl) {
-      bf16_t* C = pl ? (bf16_t*)p.C_lo : (bf16_t*)p.C;
-      const bf16_t* img = (const bf16_t*)smem + pl * CT_PLANE;
-      const bool vec_ok = ((p.ldc & 7) == 0) && (((uintptr_t)C & 15) == 0);
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int ch = tid + 256 * it, row = ch >> 4, c8 = (ch & 15) * 8;
-        const int m = m0 + row, n = n0 + c8;
-        if (m >= p.M || n >= p.N) continue;
-        const bf16_t* src = img + row * CT_BF16_STRIDE + c8;
-        if (vec_ok && n + 8 <= p.N) {
-          *(u32x4_t*)(C + (size_t)m * p.ldc + n) = *(const u32x4_t*)src;
-        } else {
-          for (int e = 0; e < 8 && n + e < p.N; ++e) C[(size_t)m * p.ldc + n + e] = src[e];
-        }
-      }
-    }
+    for (int pl = 0; pl < 2; ++pl)
+      tile_store_16bit(p, (const bf16_t*)smem + pl * CT_PLANE, pl ? (bf16_t*)p.C_lo : (bf16_t*)p.C, m0, n0);
   } else {
-    float* C = (float*)p.C;
-    const bool vec_ok = ((p.ldc & 3) == 0) && (((uintptr_t)C & 15) == 0);
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      const int ch = tid + 256 * it, row = ch >> 5, c4 = (ch & 31) * 4;
-      const int m = m0 + row, n = n0 + c4;
-      if (m >= p.M || n >= p.N) continue;
-      f32x4_t v = *(const f32x4_t*)((const float*)smem + row * CT_F32_STRIDE + c4);
-      size_t orow = (size_t)m;
-      if constexpr (EPI == EPI_PATCH) {
-        const int b = m / p.npatch, pp = m - b * p.npatch;
-        orow = (size_t)b * p.ntok_s + 1 + pp;
-        const f32x4_t pe = *(const f32x4_t*)(p.pos + (size_t)(1 + pp) * p.ldc + n);  // ldc == D, n % 4 == 0
-        v += pe;
-      }
-      float* dst = C + orow * p.ldc + n;
-      if (vec_ok && n + 4 <= p.N) {
-        if constexpr (EPI == EPI_RESID_F32 || EPI == EPI_ACCUM_F32) v += *(const f32x4_t*)dst;
-        *(f32x4_t*)dst = v;
-      } else {
-        for (int e = 0; e < 4 && n + e < p.N; ++e) {
-          float o = v[e];
-          if constexpr (EPI == EPI_RESID_F32 || EPI == EPI_ACCUM_F32) o += dst[e];
-          dst[e] = o;
-        }
-      }
-    }
+    tile_store_f32<EPI>(p, (const float*)smem, (float*)p.C, m0, n0);
   }
 }
 
