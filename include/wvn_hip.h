@@ -496,8 +496,22 @@ typedef struct wvn_mlp_desc {
   int D;  /* input features (384 dino / 90 stego) */
   int H1; /* 256 */
   int H2; /* 32  */
-  int reserved;
+  int reserved; /* model kind: 0 = SimpleMLP, WVN_MLP_KIND_DOUBLE = DoubleMLP (below) */
 } wvn_mlp_desc;
+/* DoubleMLP (model/double_mlp.py): two independent networks on one input, networks.0 : D -> H1 -> H2 -> 1 (sigmoid, column 0 of
+ * the output) and networks.1 : D -> H1 -> H2 -> D (columns 1 .. D), same [R, 1 + D] output as SimpleMLP.  A desc with
+ * reserved = WVN_MLP_KIND_DOUBLE selects it in wvn_mlp_param_count, wvn_mlp_workspace_bytes, wvn_mlp_forward (h1 / h2: both NULL or
+ * [R][2 H1] / [R][2 H2], networks.0 first; no workspace needed), every wvn_mlp_train_phase_* entry point and wvn_segment_predict
+ * (csrc/double_mlp.hip).  Flat layout of parameters, gradients and Adam moments:
+ *   [W1a | b1a | W2a | b2a | W3a | b3a | W1b | b1b | W2b | b2b | W3b | b3b],  a = networks.0, b = networks.1, Wi in Linear layout
+ * so the data-parallel exchange stays one all-reduce of param_count + 2 floats.  Limits: 1 <= D <= 1024, 1 <= H1, H2 <= 256
+ * (WVN_ERR_ARG / 0 otherwise).  The four-launch step (sync_word / fused, as for SimpleMLP) applies to H1 = 64, H2 = 32 and
+ * rows <= 2048: wvn_double_mlp_fused_ok; other shapes take the general path whatever the flags say.  wvn_double_mlp_row_tile: the
+ * rows one workgroup of these kernels owns.  The wvn_pixel_mlp_* entry points refuse such a desc (0 / WVN_ERR_ARG).
+ * reserved = 0 is the SimpleMLP, unchanged. */
+#define WVN_MLP_KIND_DOUBLE 1
+int wvn_double_mlp_row_tile(void);
+int wvn_double_mlp_fused_ok(const wvn_mlp_desc* d, int rows);
 size_t wvn_mlp_param_count(const wvn_mlp_desc* d);
 size_t wvn_mlp_workspace_bytes(const wvn_mlp_desc* d, int rows);
 

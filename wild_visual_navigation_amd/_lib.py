@@ -77,6 +77,9 @@ class MlpDesc(C.Structure):
     _fields_ = [("D", C.c_int), ("H1", C.c_int), ("H2", C.c_int), ("reserved", C.c_int)]
 
 
+MLP_KIND_DOUBLE = 1   # include/wvn_hip.h: WVN_MLP_KIND_DOUBLE (MlpDesc.reserved)
+
+
 _lib = None
 _lock = threading.Lock()
 
@@ -171,6 +174,8 @@ _SIGNATURES = {
     "wvn_kmeans_cosine": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "wvn_mlp_param_count": ([_p], _sz),
     "wvn_mlp_workspace_bytes": ([_p, _i], _sz),
+    "wvn_double_mlp_row_tile": ([], _i),
+    "wvn_double_mlp_fused_ok": ([_p, _i], _i),
     "wvn_mlp_forward": ([_p, _p, _p, _i, _i, _p, _p, _p, _p, _sz, _p], _i),
     "wvn_mlp_train_phase_a": ([_p, _p, _p, _i, _p, _i, _p, _p, _sz, _p], _i),
     "wvn_mlp_train_phase_b": ([_p, _p, _p, _i, _p, _p, _i, _p, _f, _f, _f, _p, _p, _p, _sz, _p], _i),

@@ -58,8 +58,14 @@ class SimpleMlpCfgParams(_Node):
 
 
 @dataclass
+class DoubleMlpCfgParams(_Node):
+    input_size: int = 384
+    hidden_sizes: List[int] = field(default_factory=lambda: [64, 32, 1])
+
+
+@dataclass
 class OtherModelCfgParams(_Node):
-    """Config slots of the non-default models (DoubleMLP / SimpleGCN / LinearRnvp, experiment_params.py:113-139): callers write
+    """Config slots of the models outside this build (SimpleGCN / LinearRnvp, experiment_params.py:113-139): callers write
     ``input_size`` into all four unconditionally (quick_start.py:131-134); the models themselves are outside this build."""
     input_size: int = 384
 
@@ -69,7 +75,7 @@ class ModelParams(_Node):
     name: str = "SimpleMLP"
     load_ckpt: Optional[str] = None
     simple_mlp_cfg: SimpleMlpCfgParams = field(default_factory=SimpleMlpCfgParams)
-    double_mlp_cfg: OtherModelCfgParams = field(default_factory=OtherModelCfgParams)
+    double_mlp_cfg: DoubleMlpCfgParams = field(default_factory=DoubleMlpCfgParams)
     simple_gcn_cfg: OtherModelCfgParams = field(default_factory=OtherModelCfgParams)
     linear_rnvp_cfg: OtherModelCfgParams = field(default_factory=OtherModelCfgParams)
 

@@ -489,17 +489,108 @@ int mlp_wgrad(const float* G, int ldg, const float* Hm, int ldh, int M, int N, i
   if (sk > 1) RET_IF(wvn_splitk_reduce_launch(part, sk, (size_t)M * N, nullptr, N, dst, st));
   return WVN_OK;
 }
+
+// ---- DoubleMLP (desc.reserved == WVN_MLP_KIND_DOUBLE; kernels in double_mlp.hip) ----
+bool is_double(const wvn_mlp_desc* d) { return d->reserved == WVN_MLP_KIND_DOUBLE; }
+struct DmlpWs { float *h1, *h2, *out, *lr, *g_out, *g_h2, *g_h1, *trav_w, *trav_raw, *part; void* fused; size_t total; };
+DmlpWs dmlp_carve(const wvn_mlp_desc* d, int R, void* base) {
+  DmlpWs w;
+  size_t off = 0;
+  const int O = 1 + d->D, N1 = 2 * d->H1, N2 = 2 * d->H2;
+  auto take = [&](size_t n) { size_t o = off; off += align_up(n * sizeof(float), 256); return (float*)((char*)base + o); };
+  w.h1 = take((size_t)R * N1); w.h2 = take((size_t)R * N2); w.out = take((size_t)R * O); w.lr = take(R);
+  w.g_out = take((size_t)R * O); w.g_h2 = take((size_t)R * N2); w.g_h1 = take((size_t)R * N1);
+  w.trav_w = take(R); w.trav_raw = take(R);
+  size_t mx = (size_t)d->H1 * d->D;
+  if ((size_t)d->H2 * d->H1 > mx) mx = (size_t)d->H2 * d->H1;
+  if ((size_t)d->D * d->H2 > mx) mx = (size_t)d->D * d->H2;
+  w.part = take(mx * mlp_splitk(R));                                     // split-K slabs of the general path
+  w.fused = take(wvn_dmlp_scratch_bytes(R) / sizeof(float) + 1);         // per-tile partials of the four-launch step
+  w.total = off;
+  return w;
+}
+DmlpArgs dmlp_args(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, int R, const int* rows_dev, const DmlpWs& w,
+                   const ConfArgs& conf) {
+  DmlpArgs a{};
+  a.P = params; a.g = wvn_dmlp_geom(d->D, d->H1, d->H2);
+  a.x = x; a.ld_row = ldx; a.ld_frame = 0; a.S = R; a.R = R; a.rows_dev = rows_dev;
+  a.h1 = w.h1; a.h2 = w.h2; a.out = w.out; a.lr = w.lr; a.g_out = w.g_out; a.g_h2 = w.g_h2; a.g_h1 = w.g_h1;
+  a.method = conf.method; a.balanced = conf.balanced; a.cstate = conf.state; a.minmax = conf.minmax;
+  return a;
+}
+int dmlp_phase_a(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const unsigned char* y_valid, int R,
+                 const int* rows_dev, double* stats, void* workspace, size_t workspace_bytes, unsigned int* sync_word, hipStream_t st,
+                 const ConfArgs& conf) {
+  if (!wvn_dmlp_supported(d->D, d->H1, d->H2) || ldx < d->D) return WVN_ERR_ARG;
+  const DmlpWs w = dmlp_carve(d, R, workspace);
+  if (w.total > workspace_bytes) return WVN_ERR_WORKSPACE;
+  DmlpArgs a = dmlp_args(d, params, x, ldx, R, rows_dev, w, conf);
+  a.valid = y_valid; a.stats = stats;
+  if (sync_word && wvn_dmlp_fused_ok(d->D, d->H1, d->H2, R)) {   // the four-launch step: forward + statistic in one launch
+    wvn_dmlp_scratch_carve(w.fused, R, &a.part, &a.part_mm);
+    a.ticket = sync_word;
+    return wvn_dmlp_fwd_launch(a, st);
+  }
+  a.lr = nullptr;   // (the stage kernel below forms the row losses)
+  RET_IF(wvn_dmlp_fwd_launch(a, st));
+  return wvn_mlp_rowloss_stats_launch(w.out, 1 + d->D, x, ldx, y_valid, w.lr, stats, R, d->D, st, rows_dev, conf);
+}
+int dmlp_phase_b(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const float* y, const unsigned char* y_valid,
+                 int R, const int* rows_dev, const double* stats, float std_factor, float w_trav, float w_reco, float* grads,
+                 float* confidence_out, void* workspace, size_t workspace_bytes, int fused, hipStream_t st, const ConfArgs& conf) {
+  if (!wvn_dmlp_supported(d->D, d->H1, d->H2) || ldx < d->D) return WVN_ERR_ARG;
+  const DmlpWs w = dmlp_carve(d, R, workspace);
+  if (w.total > workspace_bytes) return WVN_ERR_WORKSPACE;
+  DmlpArgs a = dmlp_args(d, params, x, ldx, R, rows_dev, w, conf);
+  a.y = y; a.valid = y_valid; a.stats = (double*)stats; a.std_factor = std_factor; a.w_trav = w_trav; a.w_reco = w_reco;
+  a.conf_out = confidence_out; a.grads = grads;
+  const DmlpGeom& g = a.g;
+  if (fused && wvn_dmlp_fused_ok(d->D, d->H1, d->H2, R)) {   // (phase A of this step ran the fused forward on this workspace)
+    wvn_dmlp_scratch_carve(w.fused, R, &a.part, &a.part_mm);
+    RET_IF(wvn_dmlp_bwd_launch(a, st));
+    return wvn_dmlp_wgrad_launch(a, st);
+  }
+  const int O = 1 + d->D, H1 = d->H1, H2 = d->H2;
+  RET_IF(wvn_mlp_gradout_launch(w.out, O, x, ldx, y, y_valid, w.lr, stats, std_factor, w_trav, w_reco, w.g_out, O, w.trav_w,
+                                w.trav_raw, confidence_out, grads + g.total, R, d->D, st, rows_dev, conf));
+  a.seed_given = 1;
+  RET_IF(wvn_dmlp_bwd_launch(a, st));
+  for (int net = 0; net < 2; ++net) {   // column 0 of the seed belongs to networks.0, columns 1 .. D to networks.1
+    const int M3 = net ? d->D : 1;
+    RET_IF(mlp_wgrad(w.g_out + net, O, w.h2 + net * H2, 2 * H2, M3, H2, R, w.part, grads + g.W3[net], st));
+    RET_IF(wvn_colsum_launch(w.g_out + net, O, R, M3, grads + g.b3[net], st));
+    RET_IF(mlp_wgrad(w.g_h2 + net * H2, 2 * H2, w.h1 + net * H1, 2 * H1, H2, H1, R, w.part, grads + g.W2[net], st));
+    RET_IF(wvn_colsum_launch(w.g_h2 + net * H2, 2 * H2, R, H2, grads + g.b2[net], st));
+    RET_IF(mlp_wgrad(w.g_h1 + net * H1, 2 * H1, x, ldx, H1, d->D, R, w.part, grads + g.W1[net], st));
+    RET_IF(wvn_colsum_launch(w.g_h1 + net * H1, 2 * H1, R, H1, grads + g.b1[net], st));
+  }
+  return WVN_OK;
+}
+size_t mlp_total(const wvn_mlp_desc* d) { return is_double(d) ? wvn_dmlp_geom(d->D, d->H1, d->H2).total : mlp_off(d).total; }
 }  // namespace
 
-size_t wvn_mlp_param_count(const wvn_mlp_desc* d) { return d ? mlp_off(d).total : 0; }
+int wvn_double_mlp_row_tile(void) { return wvn_dmlp_row_tile(); }
+int wvn_double_mlp_fused_ok(const wvn_mlp_desc* d, int rows) {
+  return d && is_double(d) && wvn_dmlp_fused_ok(d->D, d->H1, d->H2, rows) ? 1 : 0;
+}
+
+size_t wvn_mlp_param_count(const wvn_mlp_desc* d) { return d ? mlp_total(d) : 0; }
 size_t wvn_mlp_workspace_bytes(const wvn_mlp_desc* d, int rows) {
   if (!d || rows <= 0) return 0;
+  if (is_double(d)) return wvn_dmlp_supported(d->D, d->H1, d->H2) ? dmlp_carve(d, rows, nullptr).total : 0;
   return mlp_carve(d, rows, nullptr).total;
 }
 
 int wvn_mlp_forward(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, int R, float* out, float* h1,
                     float* h2, void* workspace, size_t workspace_bytes, void* stream) {
   if (!d || !params || !x || !out || R <= 0) return WVN_ERR_ARG;
+  if (is_double(d)) {   // one launch, nothing but out (and h1 [R][2 H1] / h2 [R][2 H2] where asked for) leaves the chip
+    if (ldx < d->D || (h1 == nullptr) != (h2 == nullptr)) return WVN_ERR_ARG;
+    DmlpArgs a{};
+    a.P = params; a.g = wvn_dmlp_geom(d->D, d->H1, d->H2);
+    a.x = x; a.ld_row = ldx; a.S = R; a.R = R; a.out = out; a.h1 = h1; a.h2 = h2;
+    return wvn_dmlp_fwd_launch(a, (hipStream_t)stream);
+  }
   if (!h1 || !h2) {
     if (!workspace) return WVN_ERR_ARG;
     MlpWs w = mlp_carve(d, R, workspace);
@@ -521,6 +612,7 @@ int mlp_phase_a(const wvn_mlp_desc* d, const float* params, const float* x, int 
                 const ConfArgs& conf) {
   if (!d || !params || !x || !y_valid || !stats || !workspace || R <= 0) return WVN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
+  if (is_double(d)) return dmlp_phase_a(d, params, x, ldx, y_valid, R, rows_dev, stats, workspace, workspace_bytes, sync_word, st, conf);
   MlpWs w = mlp_carve(d, R, workspace);
   if (w.total > workspace_bytes) return WVN_ERR_WORKSPACE;
   if (sync_word && wvn_mlp_train_fused_ok(d->D, d->H1, d->H2, R)) {   // the four-launch step (mlp_train.hip): forward + statistic
@@ -577,6 +669,9 @@ int mlp_phase_b(const wvn_mlp_desc* d, const float* params, const float* x, int 
                 float* confidence_out, void* workspace, size_t workspace_bytes, int fused, void* stream, const ConfArgs& conf) {
   if (!d || !params || !x || !y || !y_valid || !stats || !grads || !workspace || R <= 0) return WVN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
+  if (is_double(d))
+    return dmlp_phase_b(d, params, x, ldx, y, y_valid, R, rows_dev, stats, std_factor, w_trav, w_reco, grads, confidence_out, workspace,
+                        workspace_bytes, fused, st, conf);
   MlpWs w = mlp_carve(d, R, workspace);
   if (w.total > workspace_bytes) return WVN_ERR_WORKSPACE;
   const MlpOff o = mlp_off(d);
@@ -635,9 +730,9 @@ int wvn_mlp_train_phase_c(const wvn_mlp_desc* d, float* params, const float* gra
                           void* stream) {
   if (!d || !params || !grads || !adam_m || !adam_v || !stats || step <= 0) return WVN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const MlpOff o = mlp_off(d);
+  const size_t total = mlp_total(d);
   // Adam and the step's losses in ONE launch
-  return wvn_adam_launch(params, grads, adam_m, adam_v, (int)o.total, step, lr, 0.9f, 0.999f, 1e-8f, st, stats, grads + o.total, w_trav,
+  return wvn_adam_launch(params, grads, adam_m, adam_v, (int)total, step, lr, 0.9f, 0.999f, 1e-8f, st, stats, grads + total, w_trav,
                          w_reco, losses);
 }
 int wvn_mlp_train_phase_c_conf(const wvn_mlp_desc* d, float* params, const float* grads, float* adam_m, float* adam_v, int step,
@@ -646,49 +741,49 @@ int wvn_mlp_train_phase_c_conf(const wvn_mlp_desc* d, float* params, const float
   ConfArgs a;
   RET_IF(conf_args(conf, &a));
   if (!d || !params || !grads || !adam_m || !adam_v || !stats || !losses || step <= 0) return WVN_ERR_ARG;   // (losses: the commit rides on it)
-  const MlpOff o = mlp_off(d);
-  return wvn_adam_launch(params, grads, adam_m, adam_v, (int)o.total, step, lr, 0.9f, 0.999f, 1e-8f, (hipStream_t)stream, stats,
-                         grads + o.total, w_trav, w_reco, losses, a);
+  const size_t total = mlp_total(d);
+  return wvn_adam_launch(params, grads, adam_m, adam_v, (int)total, step, lr, 0.9f, 0.999f, 1e-8f, (hipStream_t)stream, stats,
+                         grads + total, w_trav, w_reco, losses, a);
 }
 
 // fused per-pixel inference (pixel_mlp.hip)
 size_t wvn_pixel_mlp_pack_bytes(const wvn_mlp_desc* d) {
-  if (!d || d->H1 != 256 || d->H2 != 32) return 0;
+  if (!d || d->reserved != 0 || d->H1 != 256 || d->H2 != 32) return 0;
   return wvn_pixel_mlp_pack_bytes_impl(d->D);
 }
 int wvn_pixel_mlp_zx_cols(const wvn_mlp_desc* d) {
-  if (!d || d->H1 != 256 || d->H2 != 32) return 0;
+  if (!d || d->reserved != 0 || d->H1 != 256 || d->H2 != 32) return 0;
   return wvn_pixel_mlp_zx_cols_impl(d->D);
 }
 int wvn_pixel_mlp_pack(const wvn_mlp_desc* d, const float* params, void* packed, void* stream) {
-  if (!d) return WVN_ERR_ARG;
+  if (!d || d->reserved != 0) return WVN_ERR_ARG;
   return wvn_pixel_mlp_pack_launch(d->D, d->H1, d->H2, params, packed, (hipStream_t)stream);
 }
 int wvn_pixel_mlp_infer(const wvn_mlp_desc* d, const void* packed, void* zx, int ldzx, int batch, int grid, int out_h,
                         int out_w, float mean, float std, float std_factor, const float* conf_state, float* trav,
                         float* conf, float* loss_reco, void* stream) {
-  if (!d) return WVN_ERR_ARG;
+  if (!d || d->reserved != 0) return WVN_ERR_ARG;
   return wvn_pixel_mlp_infer_launch(d->D, d->H1, d->H2, packed, zx, ldzx, batch, grid, out_h, out_w, mean, std, std_factor,
                                     conf_state, trav, conf, loss_reco, (hipStream_t)stream);
 }
 
 size_t wvn_pixel_mlp_exact_pack_bytes(const wvn_mlp_desc* d) {
-  if (!d || d->H1 != 256 || d->H2 != 32) return 0;
+  if (!d || d->reserved != 0 || d->H1 != 256 || d->H2 != 32) return 0;
   return wvn_pixel_mlp_exact_pack_bytes_impl(d->D);
 }
 size_t wvn_pixel_mlp_exact_workspace_bytes(const wvn_mlp_desc* d, int batch, int grid) {
-  if (!d || d->H1 != 256 || d->H2 != 32 || batch <= 0 || grid <= 0) return 0;
+  if (!d || d->reserved != 0 || d->H1 != 256 || d->H2 != 32 || batch <= 0 || grid <= 0) return 0;
   return wvn_pixel_mlp_exact_workspace_bytes_impl(d->D, batch, grid);
 }
 int wvn_pixel_mlp_exact_pack(const wvn_mlp_desc* d, const float* params, void* packed, void* stream) {
-  if (!d) return WVN_ERR_ARG;
+  if (!d || d->reserved != 0) return WVN_ERR_ARG;
   return wvn_pixel_mlp_exact_pack_launch(d->D, d->H1, d->H2, params, packed, (hipStream_t)stream);
 }
 int wvn_pixel_mlp_infer_exact(const wvn_mlp_desc* d, const float* params, const void* packed, const float* tokens,
                               int ld_tokens, int batch, int grid, int out_h, int out_w, float mean, float std,
                               float std_factor, const float* conf_state, float* trav, float* conf, float* loss_reco,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  if (!d) return WVN_ERR_ARG;
+  if (!d || d->reserved != 0) return WVN_ERR_ARG;
   return wvn_pixel_mlp_infer_exact_launch(d->D, d->H1, d->H2, params, packed, tokens, ld_tokens, batch, grid, out_h, out_w,
                                           mean, std, std_factor, conf_state, trav, conf, loss_reco, workspace,
                                           workspace_bytes, (hipStream_t)stream);
@@ -696,7 +791,8 @@ int wvn_pixel_mlp_infer_exact(const wvn_mlp_desc* d, const float* params, const 
 
 // fused per-segment inference (segment_predict.hip)
 size_t wvn_segment_predict_workspace_bytes(const wvn_mlp_desc* d, int B, int S) {
-  if (!d || !wvn_segment_predict_supported(d->D, d->H1, d->H2) || B <= 0 || S <= 0) return 0;
+  if (!d || B <= 0 || S <= 0) return 0;
+  if (!(is_double(d) ? wvn_dmlp_supported(d->D, d->H1, d->H2) : wvn_segment_predict_supported(d->D, d->H1, d->H2))) return 0;
   if ((long long)B * S > (1ll << 26)) return 0;
   return wvn_segment_predict_workspace_bytes_impl(B, S);
 }
@@ -706,7 +802,7 @@ int wvn_segment_predict(const wvn_mlp_desc* d, const float* params, const float*
                         size_t workspace_bytes, void* stream) {
   // every check is host arithmetic: a refused call touches no GPU state
   if (!d || !params || !feat || !seg || !workspace) return WVN_ERR_ARG;
-  if (!wvn_segment_predict_supported(d->D, d->H1, d->H2)) return WVN_ERR_ARG;
+  if (!(is_double(d) ? wvn_dmlp_supported(d->D, d->H1, d->H2) : wvn_segment_predict_supported(d->D, d->H1, d->H2))) return WVN_ERR_ARG;
   if (B <= 0 || S <= 0 || H <= 0 || W <= 0 || B > 65535) return WVN_ERR_ARG;
   if ((long long)B * S > (1ll << 26) || (long long)H * W > 0x7fffffffll) return WVN_ERR_ARG;
   if (seg_bytes != 4 && seg_bytes != 8) return WVN_ERR_ARG;
@@ -714,6 +810,14 @@ int wvn_segment_predict(const wvn_mlp_desc* d, const float* params, const float*
   if (((uintptr_t)params | (uintptr_t)workspace) & 15) return WVN_ERR_ARG;
   if (((uintptr_t)seg & (seg_bytes - 1)) || ((uintptr_t)feat & 3)) return WVN_ERR_ARG;
   if (workspace_bytes < wvn_segment_predict_workspace_bytes_impl(B, S)) return WVN_ERR_WORKSPACE;
+  if (is_double(d)) {   // the table from double_mlp.hip's forward, the paint of segment_predict.hip: two launches as well
+    DmlpArgs a{};
+    a.P = params; a.g = wvn_dmlp_geom(d->D, d->H1, d->H2);
+    a.x = feat; a.ld_row = ld_row; a.ld_frame = ld_frame; a.S = S; a.R = B * S;
+    a.table = (float*)workspace; a.mean = mean; a.std = std; a.std_factor = std_factor; a.conf_dev = conf_state;
+    RET_IF(wvn_dmlp_fwd_launch(a, (hipStream_t)stream));
+    return wvn_segment_paint_launch(a.table, B, S, seg, seg_bytes, H, W, trav, conf, loss_reco, (hipStream_t)stream);
+  }
   return wvn_segment_predict_launch(d->D, params, feat, ld_row, ld_frame, B, S, seg, seg_bytes, H, W, mean, std, std_factor,
                                     conf_state, trav, conf, loss_reco, workspace, workspace_bytes, (hipStream_t)stream);
 }

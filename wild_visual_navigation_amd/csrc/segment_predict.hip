@@ -276,9 +276,13 @@ int wvn_segment_predict_launch(int D, const float* params, const float* feat, in
   if (const int rc = lds_opt_in((int)table_lds_bytes(DMAX), (const void*)seg_table_kernel)) return rc;
   hipLaunchKernelGGL(seg_table_kernel, dim3(ceil_div(B * S, TR)), dim3(256), lds, st, t);
   WVN_LAUNCH_CHECK();
+  return wvn_segment_paint_launch(t.table, B, S, seg, seg_bytes, H, W, trav, conf, loss, st);
+}
 
+int wvn_segment_paint_launch(const float* table, int B, int S, const void* seg, int seg_bytes, int H, int W, float* trav, float* conf,
+                             float* loss, hipStream_t st) {
   PaintParams p{};
-  p.seg = seg; p.table = t.table; p.trav = trav; p.conf = conf; p.loss = loss;
+  p.seg = seg; p.table = table; p.trav = trav; p.conf = conf; p.loss = loss;
   p.B = B; p.S = S; p.P = H * W;
   uintptr_t a = (uintptr_t)seg | (uintptr_t)trav | (uintptr_t)conf | (uintptr_t)loss;
   p.vec = (a & 15) == 0;

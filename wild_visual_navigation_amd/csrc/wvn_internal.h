@@ -284,6 +284,31 @@ int wvn_mlp_losses_launch(const double* stats, const float* extra, float w_trav,
                           hipStream_t st);
 int wvn_mlp_confidence_launch(const float* out, int ldo, const float* x, int ldx, float mean, float std,
                               float std_factor, float* trav, float* conf, int R, int D, hipStream_t st);
+// ---- DoubleMLP (double_mlp.hip): two three-layer networks on one input, flat parameters [networks.0 | networks.1] ----------
+struct DmlpGeom { int D, H1, H2; size_t W1[2], b1[2], W2[2], b2[2], W3[2], b3[2], total; };   // offsets of networks.{0, 1}
+DmlpGeom wvn_dmlp_geom(int D, int H1, int H2);
+bool wvn_dmlp_supported(int D, int H1, int H2);          // 1 <= D <= 1024, 1 <= h1, h2 <= 256
+bool wvn_dmlp_fused_ok(int D, int H1, int H2, int R);    // the four-launch step: h1 = 64, h2 = 32, R <= 2048
+int wvn_dmlp_row_tile();
+size_t wvn_dmlp_scratch_bytes(int R);                    // per-tile partials of the fused step
+void wvn_dmlp_scratch_carve(void* scratch, int R, double** part, float** part_mm);
+// One argument block for the three kernels; a launcher reads the fields of its stage, the others stay zero.
+struct DmlpArgs {
+  const float* P; DmlpGeom g;
+  const float* x; int ld_row; long long ld_frame; int S;   // row r is row r % S of frame r / S (a training batch: S = R, ld_frame = 0)
+  int R; const int* rows_dev;                              // rows_dev (optional): only the first *rows_dev rows are real
+  const float* y; const unsigned char* valid;
+  float *h1, *h2, *out, *lr;                               // [R][2 h1], [R][2 h2], [R][1 + D], [R]; each optional in the forward
+  float *g_out, *g_h2, *g_h1;                              // [R][1 + D], [R][2 h2], [R][2 h1]
+  double* part; float* part_mm; double* stats; unsigned* ticket;   // part != nullptr: the forward also folds stats (ticket: a zero word, left at zero)
+  float std_factor, w_trav, w_reco; float* conf_out; float* grads;
+  int method, balanced; const double* cstate; float* minmax;       // ConfArgs of the step
+  int seed_given;                                          // bwd: g_out already holds the gradient seed (general path, mlp.hip's gradout kernel)
+  float* table; float mean, std; const float* conf_dev;    // forward: the per-segment table {trav, conf, loss, 0} [R][4]
+};
+int wvn_dmlp_fwd_launch(const DmlpArgs& p, hipStream_t st);
+int wvn_dmlp_bwd_launch(const DmlpArgs& p, hipStream_t st);
+int wvn_dmlp_wgrad_launch(const DmlpArgs& p, hipStream_t st);   // all twelve gradients + grads[total .. total + 1] = the loss sums
 int wvn_segpool_patch_launch(const int* labels, const float* tok, int ldf, const float* wy, const float* wx,
                              float* feat, int B, int G, int S, int D, hipStream_t st);
 size_t wvn_segmean_scratch_bytes_impl(int B, int P, int S, int D);
@@ -313,6 +338,9 @@ int wvn_segment_predict_launch(int D, const float* params, const float* feat, in
                                const void* seg, int seg_bytes, int H, int W, float mean, float std, float std_factor,
                                const float* conf_state, float* trav, float* conf, float* loss, void* workspace,
                                size_t workspace_bytes, hipStream_t st);
+// the second half of the above on a table {trav, conf, loss, 0} [B*S][4] that another model's kernel has filled
+int wvn_segment_paint_launch(const float* table, int B, int S, const void* seg, int seg_bytes, int H, int W, float* trav, float* conf,
+                             float* loss, hipStream_t st);
 
 // ---- supervision path (supervision.hip) and SLIC (slic.hip) -------------------------------------------------------------
 int wvn_project_render_fmin_launch(const void* nodes, int n, const float* points, int points_batched, int npts, int C, int H,

@@ -204,6 +204,9 @@ class FeatureExtractor:
         stego = self._feature_type == "stego"
         prec = self._extractor._precision
         exact = prec in ("exact", "fp32", "mixed")
+        if not hasattr(model, "ZX_COLS"):   # refused before the backbone runs
+            raise _lib.WvnError(f"predict_per_pixel: fused per-pixel inference is not implemented for {type(model).__name__} "
+                                f"(SimpleMLP only); use predict_per_segment")
         if self.feature_dim != model.input_size:
             raise _lib.WvnError(f"predict_per_pixel: the extractor's feature_dim is {self.feature_dim}, the model's input_size is "
                                 f"{model.input_size}")

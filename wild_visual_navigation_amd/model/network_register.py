@@ -1,8 +1,11 @@
-"""get_model -- wild_visual_navigation/model/network_register.py:44-55 (class-name registry; only the
-default SimpleMLP is on the MI355X path)."""
+"""get_model -- wild_visual_navigation/model/network_register.py:44-55 (class-name registry; SimpleMLP and DoubleMLP are on
+the MI355X path)."""
+import inspect
+
+from .double_mlp import DoubleMLP
 from .simple_mlp import SimpleMLP
 
-_REGISTER = {"SimpleMLP": (SimpleMLP, "simple_mlp_cfg")}
+_REGISTER = {"SimpleMLP": (SimpleMLP, "simple_mlp_cfg"), "DoubleMLP": (DoubleMLP, "double_mlp_cfg")}
 
 
 def _get(cfg, key):
@@ -15,6 +18,7 @@ def get_model(model_cfg):
         raise KeyError(f"model '{name}' is not part of the MI355X hot path (available: {list(_REGISTER)})")
     cls, key = _REGISTER[name]
     sub = _get(model_cfg, key)
-    kw = dict(sub) if isinstance(sub, dict) else {k: getattr(sub, k) for k in ("input_size", "hidden_sizes", "reconstruction")}
+    args = [a for a in inspect.signature(cls.__init__).parameters if a != "self"]   # (DoubleMLP has no ``reconstruction``)
+    kw = dict(sub) if isinstance(sub, dict) else {k: getattr(sub, k) for k in args}
     kw["hidden_sizes"] = list(kw["hidden_sizes"])
     return cls(**kw)
