@@ -222,6 +222,44 @@ def test_compacted_batch_gives_the_same_bits(dev, method):
             assert torch.equal(v, mb.state_dict()[k]) if fused else torch.allclose(v, mb.state_dict()[k], atol=1e-5), k
 
 
+@pytest.mark.parametrize("R,D", [(33, 90), (17, 91)])
+def test_four_launch_step_equals_general_path(dev, R, D):
+    """The counterpart of tests/test_gpu_mlp.py::test_four_launch_step_equals_general_path_and_oracle at the 16-row tile: the
+    statistic's ticket and the table-driven weight gradients (shared with the SimpleMLP step) from the DoubleMLP side, ragged last
+    row tile, odd D; then a compacted batch (rows_dev) with garbage behind the count gives the bits of the truncated batch."""
+    g = torch.Generator().manual_seed(R + D)
+    x = torch.randn(R, D, generator=g)
+    yv = torch.rand(R, generator=g) < 0.16
+    yv[:2] = True
+    y = yv.float() * (0.5 + 0.5 * torch.rand(R, generator=g))
+    sd0 = _seeded_sd(D, HIDDEN, 42)
+    ma, mb = _model(sd0, D, dev), _model(sd0, D, dev)
+    assert _lib.lib().wvn_double_mlp_fused_ok(C.byref(ma.desc), R)
+    ta, tb = MlpTrainer(ma, fused=True), MlpTrainer(mb, fused=False)
+    for _ in range(3):
+        la = ta.train_step(x.to(dev), y.to(dev), yv.to(dev), want_confidence=True).cpu()
+        lb = tb.train_step(x.to(dev), y.to(dev), yv.to(dev), want_confidence=True).cpu()
+        assert torch.allclose(ta.last_confidence, tb.last_confidence, atol=1e-5)
+    print(f"R {R} D {D}: losses fused {la.tolist()} general {lb.tolist()}")
+    assert torch.allclose(la, lb, rtol=1e-5, atol=2e-6), (la, lb)
+    for k, v in ma.state_dict().items():
+        assert torch.allclose(v, mb.state_dict()[k], atol=1e-5), (k, (v - mb.state_dict()[k]).abs().max())
+    assert int(ta.sync_word.item()) == 0                                      # the arrival counter is back at zero
+    n = R - R // 3
+    rows_dev = torch.tensor([n], dtype=torch.int32, device=dev)
+    xg = x.clone()
+    xg[n:] = 1e6
+    mc, md = _model(sd0, D, dev), _model(sd0, D, dev)
+    tc, td = MlpTrainer(mc, fused=True), MlpTrainer(md, fused=True)
+    for _ in range(3):
+        lc = tc.train_step(xg.to(dev), y.to(dev), yv.to(dev), rows_dev=rows_dev).cpu()
+        ld = td.train_step(x[:n].to(dev), y[:n].to(dev), yv[:n].to(dev)).cpu()
+    assert torch.equal(lc, ld)                                                # the same tiles in the same order: identical bits
+    for k, v in mc.state_dict().items():
+        assert torch.equal(v, md.state_dict()[k]), k
+    assert int(tc.sync_word.item()) == 0
+
+
 # ---- path limits ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("R", [2048, 2049])
 def test_path_limit_matches_fp64_restatement(dev, R):

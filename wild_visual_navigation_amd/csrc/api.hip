@@ -439,7 +439,6 @@ int wvn_kmeans_cosine(const float* xn, int* labels, int* nseg, void* scratch, in
 // traversability MLP
 // ---------------------------------------------------------------------------------------------
 namespace {
-struct MlpOff { size_t W1, b1, W2, b2, W3, b3, total; int O; };
 MlpOff mlp_off(const wvn_mlp_desc* d) {
   MlpOff o;
   o.O = 1 + d->D;
@@ -448,22 +447,40 @@ MlpOff mlp_off(const wvn_mlp_desc* d) {
   return o;
 }
 int mlp_splitk(int R) { int s = (R + 511) / 512; return s < 1 ? 1 : (s > 32 ? 32 : s); }
+bool is_double(const wvn_mlp_desc* d) { return d->reserved == WVN_MLP_KIND_DOUBLE; }   // DoubleMLP (kernels in double_mlp.hip)
+// The workspace of a step, for both models: DoubleMLP's activations hold the two networks side by side, [R][2 h1] and [R][2 h2]
 struct MlpWs { float *h1, *h2, *out, *lr, *g_out, *g_h2, *g_h1, *trav_w, *trav_raw, *part; void* fused; size_t total; };
+int mlp_row_tile(const wvn_mlp_desc* d) { return is_double(d) ? wvn_dmlp_row_tile() : wvn_mlp_train_row_tile(); }
 MlpWs mlp_carve(const wvn_mlp_desc* d, int R, void* base) {
   MlpWs w;
   size_t off = 0;
-  const int O = 1 + d->D;
+  const int nets = is_double(d) ? 2 : 1, O = 1 + d->D, N1 = nets * d->H1, N2 = nets * d->H2;
   auto take = [&](size_t n) { size_t o = off; off += align_up(n * sizeof(float), 256); return (float*)((char*)base + o); };
-  w.h1 = take((size_t)R * d->H1); w.h2 = take((size_t)R * d->H2); w.out = take((size_t)R * O); w.lr = take(R);
-  w.g_out = take((size_t)R * O); w.g_h2 = take((size_t)R * d->H2); w.g_h1 = take((size_t)R * d->H1);
+  w.h1 = take((size_t)R * N1); w.h2 = take((size_t)R * N2); w.out = take((size_t)R * O); w.lr = take(R);
+  w.g_out = take((size_t)R * O); w.g_h2 = take((size_t)R * N2); w.g_h1 = take((size_t)R * N1);
   w.trav_w = take(R); w.trav_raw = take(R);
   size_t mx = (size_t)d->H1 * d->D;
   if ((size_t)d->H2 * d->H1 > mx) mx = (size_t)d->H2 * d->H1;
-  if ((size_t)O * d->H2 > mx) mx = (size_t)O * d->H2;
-  w.part = take(mx * mlp_splitk(R));
-  w.fused = take(wvn_mlp_train_fused_scratch_bytes(R) / sizeof(float) + 1);   // per-tile partials of the four-launch step
+  const size_t m3 = (size_t)(is_double(d) ? d->D : O) * d->H2;   // the largest third-layer matrix: [1 + D][h2], DoubleMLP: networks.1's [D][h2]
+  if (m3 > mx) mx = m3;
+  w.part = take(mx * mlp_splitk(R));                                                      // split-K slabs of the general path
+  w.fused = take(wvn_train_scratch_bytes(R, mlp_row_tile(d)) / sizeof(float) + 1);        // per-tile partials of the four-launch step
   w.total = off;
   return w;
+}
+// The fields of a step's argument block that both models fill alike (phase A stops at `fused`); fused: the per-tile partials of
+// the four-launch step too
+void train_args(TrainArgs& a, const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const unsigned char* y_valid, int R,
+                const int* rows_dev, const double* stats, const MlpWs& w, const ConfArgs& conf, bool fused, const float* y = nullptr,
+                float std_factor = 0.f, float w_trav = 0.f, float w_reco = 0.f, float* conf_out = nullptr, float* grads = nullptr) {
+  a.P = params; a.x = x; a.ld_row = ldx; a.R = R; a.rows_dev = rows_dev; a.valid = y_valid; a.stats = (double*)stats;
+  a.y = y; a.std_factor = std_factor; a.w_trav = w_trav; a.w_reco = w_reco; a.conf_out = conf_out; a.grads = grads;
+  a.h1 = w.h1; a.h2 = w.h2; a.out = w.out; a.lr = w.lr; a.g_out = w.g_out; a.g_h2 = w.g_h2; a.g_h1 = w.g_h1;
+  a.method = conf.method; a.balanced = conf.balanced; a.cstate = conf.state; a.minmax = conf.minmax;
+  if (fused) wvn_train_scratch_carve(w.fused, R, mlp_row_tile(d), &a.part, &a.part_mm);
+}
+bool fused_ok(const wvn_mlp_desc* d, int R) {
+  return is_double(d) ? wvn_dmlp_fused_ok(d->D, d->H1, d->H2, R) : wvn_mlp_train_fused_ok(d->D, d->H1, d->H2, R);
 }
 int mlp_fwd(const wvn_mlp_desc* d, const float* P, const float* x, int ldx, int R, float* out, float* h1, float* h2,
             hipStream_t st) {
@@ -490,79 +507,20 @@ int mlp_wgrad(const float* G, int ldg, const float* Hm, int ldh, int M, int N, i
   return WVN_OK;
 }
 
-// ---- DoubleMLP (desc.reserved == WVN_MLP_KIND_DOUBLE; kernels in double_mlp.hip) ----
-bool is_double(const wvn_mlp_desc* d) { return d->reserved == WVN_MLP_KIND_DOUBLE; }
-struct DmlpWs { float *h1, *h2, *out, *lr, *g_out, *g_h2, *g_h1, *trav_w, *trav_raw, *part; void* fused; size_t total; };
-DmlpWs dmlp_carve(const wvn_mlp_desc* d, int R, void* base) {
-  DmlpWs w;
-  size_t off = 0;
-  const int O = 1 + d->D, N1 = 2 * d->H1, N2 = 2 * d->H2;
-  auto take = [&](size_t n) { size_t o = off; off += align_up(n * sizeof(float), 256); return (float*)((char*)base + o); };
-  w.h1 = take((size_t)R * N1); w.h2 = take((size_t)R * N2); w.out = take((size_t)R * O); w.lr = take(R);
-  w.g_out = take((size_t)R * O); w.g_h2 = take((size_t)R * N2); w.g_h1 = take((size_t)R * N1);
-  w.trav_w = take(R); w.trav_raw = take(R);
-  size_t mx = (size_t)d->H1 * d->D;
-  if ((size_t)d->H2 * d->H1 > mx) mx = (size_t)d->H2 * d->H1;
-  if ((size_t)d->D * d->H2 > mx) mx = (size_t)d->D * d->H2;
-  w.part = take(mx * mlp_splitk(R));                                     // split-K slabs of the general path
-  w.fused = take(wvn_dmlp_scratch_bytes(R) / sizeof(float) + 1);         // per-tile partials of the four-launch step
-  w.total = off;
-  return w;
-}
-DmlpArgs dmlp_args(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, int R, const int* rows_dev, const DmlpWs& w,
-                   const ConfArgs& conf) {
-  DmlpArgs a{};
-  a.P = params; a.g = wvn_dmlp_geom(d->D, d->H1, d->H2);
-  a.x = x; a.ld_row = ldx; a.ld_frame = 0; a.S = R; a.R = R; a.rows_dev = rows_dev;
-  a.h1 = w.h1; a.h2 = w.h2; a.out = w.out; a.lr = w.lr; a.g_out = w.g_out; a.g_h2 = w.g_h2; a.g_h1 = w.g_h1;
-  a.method = conf.method; a.balanced = conf.balanced; a.cstate = conf.state; a.minmax = conf.minmax;
-  return a;
-}
-int dmlp_phase_a(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const unsigned char* y_valid, int R,
-                 const int* rows_dev, double* stats, void* workspace, size_t workspace_bytes, unsigned int* sync_word, hipStream_t st,
-                 const ConfArgs& conf) {
-  if (!wvn_dmlp_supported(d->D, d->H1, d->H2) || ldx < d->D) return WVN_ERR_ARG;
-  const DmlpWs w = dmlp_carve(d, R, workspace);
-  if (w.total > workspace_bytes) return WVN_ERR_WORKSPACE;
-  DmlpArgs a = dmlp_args(d, params, x, ldx, R, rows_dev, w, conf);
-  a.valid = y_valid; a.stats = stats;
-  if (sync_word && wvn_dmlp_fused_ok(d->D, d->H1, d->H2, R)) {   // the four-launch step: forward + statistic in one launch
-    wvn_dmlp_scratch_carve(w.fused, R, &a.part, &a.part_mm);
-    a.ticket = sync_word;
-    return wvn_dmlp_fwd_launch(a, st);
-  }
-  a.lr = nullptr;   // (the stage kernel below forms the row losses)
-  RET_IF(wvn_dmlp_fwd_launch(a, st));
-  return wvn_mlp_rowloss_stats_launch(w.out, 1 + d->D, x, ldx, y_valid, w.lr, stats, R, d->D, st, rows_dev, conf);
-}
-int dmlp_phase_b(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const float* y, const unsigned char* y_valid,
-                 int R, const int* rows_dev, const double* stats, float std_factor, float w_trav, float w_reco, float* grads,
-                 float* confidence_out, void* workspace, size_t workspace_bytes, int fused, hipStream_t st, const ConfArgs& conf) {
-  if (!wvn_dmlp_supported(d->D, d->H1, d->H2) || ldx < d->D) return WVN_ERR_ARG;
-  const DmlpWs w = dmlp_carve(d, R, workspace);
-  if (w.total > workspace_bytes) return WVN_ERR_WORKSPACE;
-  DmlpArgs a = dmlp_args(d, params, x, ldx, R, rows_dev, w, conf);
-  a.y = y; a.valid = y_valid; a.stats = (double*)stats; a.std_factor = std_factor; a.w_trav = w_trav; a.w_reco = w_reco;
-  a.conf_out = confidence_out; a.grads = grads;
+// the general path of DoubleMLP's phase B behind the gradient seed: its own data-path kernel, split-K GEMMs per network
+int dmlp_general_bwd(DmlpArgs& a, const MlpWs& w, int ldx, hipStream_t st) {
   const DmlpGeom& g = a.g;
-  if (fused && wvn_dmlp_fused_ok(d->D, d->H1, d->H2, R)) {   // (phase A of this step ran the fused forward on this workspace)
-    wvn_dmlp_scratch_carve(w.fused, R, &a.part, &a.part_mm);
-    RET_IF(wvn_dmlp_bwd_launch(a, st));
-    return wvn_dmlp_wgrad_launch(a, st);
-  }
-  const int O = 1 + d->D, H1 = d->H1, H2 = d->H2;
-  RET_IF(wvn_mlp_gradout_launch(w.out, O, x, ldx, y, y_valid, w.lr, stats, std_factor, w_trav, w_reco, w.g_out, O, w.trav_w,
-                                w.trav_raw, confidence_out, grads + g.total, R, d->D, st, rows_dev, conf));
+  const int D = g.D, O = 1 + D, H1 = g.H1, H2 = g.H2, R = a.R;
   a.seed_given = 1;
   RET_IF(wvn_dmlp_bwd_launch(a, st));
   for (int net = 0; net < 2; ++net) {   // column 0 of the seed belongs to networks.0, columns 1 .. D to networks.1
-    const int M3 = net ? d->D : 1;
-    RET_IF(mlp_wgrad(w.g_out + net, O, w.h2 + net * H2, 2 * H2, M3, H2, R, w.part, grads + g.W3[net], st));
-    RET_IF(wvn_colsum_launch(w.g_out + net, O, R, M3, grads + g.b3[net], st));
-    RET_IF(mlp_wgrad(w.g_h2 + net * H2, 2 * H2, w.h1 + net * H1, 2 * H1, H2, H1, R, w.part, grads + g.W2[net], st));
-    RET_IF(wvn_colsum_launch(w.g_h2 + net * H2, 2 * H2, R, H2, grads + g.b2[net], st));
-    RET_IF(mlp_wgrad(w.g_h1 + net * H1, 2 * H1, x, ldx, H1, d->D, R, w.part, grads + g.W1[net], st));
-    RET_IF(wvn_colsum_launch(w.g_h1 + net * H1, 2 * H1, R, H1, grads + g.b1[net], st));
+    const int M3 = net ? D : 1;
+    RET_IF(mlp_wgrad(w.g_out + net, O, w.h2 + net * H2, 2 * H2, M3, H2, R, w.part, a.grads + g.W3[net], st));
+    RET_IF(wvn_colsum_launch(w.g_out + net, O, R, M3, a.grads + g.b3[net], st));
+    RET_IF(mlp_wgrad(w.g_h2 + net * H2, 2 * H2, w.h1 + net * H1, 2 * H1, H2, H1, R, w.part, a.grads + g.W2[net], st));
+    RET_IF(wvn_colsum_launch(w.g_h2 + net * H2, 2 * H2, R, H2, a.grads + g.b2[net], st));
+    RET_IF(mlp_wgrad(w.g_h1 + net * H1, 2 * H1, a.x, ldx, H1, D, R, w.part, a.grads + g.W1[net], st));
+    RET_IF(wvn_colsum_launch(w.g_h1 + net * H1, 2 * H1, R, H1, a.grads + g.b1[net], st));
   }
   return WVN_OK;
 }
@@ -577,7 +535,7 @@ int wvn_double_mlp_fused_ok(const wvn_mlp_desc* d, int rows) {
 size_t wvn_mlp_param_count(const wvn_mlp_desc* d) { return d ? mlp_total(d) : 0; }
 size_t wvn_mlp_workspace_bytes(const wvn_mlp_desc* d, int rows) {
   if (!d || rows <= 0) return 0;
-  if (is_double(d)) return wvn_dmlp_supported(d->D, d->H1, d->H2) ? dmlp_carve(d, rows, nullptr).total : 0;
+  if (is_double(d) && !wvn_dmlp_supported(d->D, d->H1, d->H2)) return 0;
   return mlp_carve(d, rows, nullptr).total;
 }
 
@@ -612,17 +570,25 @@ int mlp_phase_a(const wvn_mlp_desc* d, const float* params, const float* x, int 
                 const ConfArgs& conf) {
   if (!d || !params || !x || !y_valid || !stats || !workspace || R <= 0) return WVN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (is_double(d)) return dmlp_phase_a(d, params, x, ldx, y_valid, R, rows_dev, stats, workspace, workspace_bytes, sync_word, st, conf);
-  MlpWs w = mlp_carve(d, R, workspace);
+  if (is_double(d) && (!wvn_dmlp_supported(d->D, d->H1, d->H2) || ldx < d->D)) return WVN_ERR_ARG;
+  const MlpWs w = mlp_carve(d, R, workspace);
   if (w.total > workspace_bytes) return WVN_ERR_WORKSPACE;
-  if (sync_word && wvn_mlp_train_fused_ok(d->D, d->H1, d->H2, R)) {   // the four-launch step (mlp_train.hip): forward + statistic
-    const MlpOff o = mlp_off(d);
-    const size_t off[6] = {o.W1, o.b1, o.W2, o.b2, o.W3, o.b3};
-    return wvn_mlp_train_fwd_launch(params, off, o.total, x, ldx, y_valid, R, d->D, rows_dev, w.h1, w.h2, w.out, w.lr, stats, w.fused,
-                                    sync_word, st, conf);
+  const bool fused = sync_word && fused_ok(d, R);   // the four-launch step: forward + statistic in one launch
+  if (is_double(d)) {
+    DmlpArgs a{};
+    train_args(a, d, params, x, ldx, y_valid, R, rows_dev, stats, w, conf, fused);
+    a.g = wvn_dmlp_geom(d->D, d->H1, d->H2); a.S = R; a.ticket = sync_word;
+    if (!fused) a.lr = nullptr;   // (the stage kernel below forms the row losses)
+    RET_IF(wvn_dmlp_fwd_launch(a, st));
+  } else if (fused) {
+    MlpTrainArgs a{};
+    train_args(a, d, params, x, ldx, y_valid, R, rows_dev, stats, w, conf, fused);
+    a.o = mlp_off(d); a.D = d->D; a.ticket = sync_word;
+    RET_IF(wvn_mlp_train_fwd_launch(a, st));
+  } else {
+    RET_IF(mlp_fwd(d, params, x, ldx, R, w.out, w.h1, w.h2, st));
   }
-  RET_IF(mlp_fwd(d, params, x, ldx, R, w.out, w.h1, w.h2, st));
-  return wvn_mlp_rowloss_stats_launch(w.out, 1 + d->D, x, ldx, y_valid, w.lr, stats, R, d->D, st, rows_dev, conf);
+  return fused ? WVN_OK : wvn_mlp_rowloss_stats_launch(w.out, 1 + d->D, x, ldx, y_valid, w.lr, stats, R, d->D, st, rows_dev, conf);
 }
 
 // wvn_conf_desc -> ConfArgs, checked on the host before any GPU call
@@ -669,20 +635,30 @@ int mlp_phase_b(const wvn_mlp_desc* d, const float* params, const float* x, int 
                 float* confidence_out, void* workspace, size_t workspace_bytes, int fused, void* stream, const ConfArgs& conf) {
   if (!d || !params || !x || !y || !y_valid || !stats || !grads || !workspace || R <= 0) return WVN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (is_double(d))
-    return dmlp_phase_b(d, params, x, ldx, y, y_valid, R, rows_dev, stats, std_factor, w_trav, w_reco, grads, confidence_out, workspace,
-                        workspace_bytes, fused, st, conf);
-  MlpWs w = mlp_carve(d, R, workspace);
+  const bool dbl = is_double(d);
+  if (dbl && (!wvn_dmlp_supported(d->D, d->H1, d->H2) || ldx < d->D)) return WVN_ERR_ARG;
+  const MlpWs w = mlp_carve(d, R, workspace);
   if (w.total > workspace_bytes) return WVN_ERR_WORKSPACE;
+  const bool four = fused && fused_ok(d, R);   // (phase A of this step ran the fused forward on this workspace)
   const MlpOff o = mlp_off(d);
   const int O = o.O;
-  if (fused && wvn_mlp_train_fused_ok(d->D, d->H1, d->H2, R)) {   // (phase A of this step ran the fused forward on this workspace)
-    const size_t off[6] = {o.W1, o.b1, o.W2, o.b2, o.W3, o.b3};
-    return wvn_mlp_train_bwd_launch(params, off, o.total, x, ldx, y, y_valid, R, d->D, rows_dev, w.h1, w.h2, w.out, w.lr, w.g_out, w.g_h2,
-                                    w.g_h1, stats, std_factor, w_trav, w_reco, confidence_out, grads, w.fused, st, conf);
+  if (!four)   // the general path of both models starts from the stage kernel's gradient seed and loss sums
+    RET_IF(wvn_mlp_gradout_launch(w.out, O, x, ldx, y, y_valid, w.lr, stats, std_factor, w_trav, w_reco, w.g_out, O, w.trav_w,
+                                  w.trav_raw, confidence_out, grads + mlp_total(d), R, d->D, st, rows_dev, conf));
+  if (dbl) {
+    DmlpArgs a{};
+    train_args(a, d, params, x, ldx, y_valid, R, rows_dev, stats, w, conf, four, y, std_factor, w_trav, w_reco, confidence_out, grads);
+    a.g = wvn_dmlp_geom(d->D, d->H1, d->H2); a.S = R;
+    if (!four) return dmlp_general_bwd(a, w, ldx, st);
+    RET_IF(wvn_dmlp_bwd_launch(a, st));
+    return wvn_dmlp_wgrad_launch(a, st);
   }
-  RET_IF(wvn_mlp_gradout_launch(w.out, O, x, ldx, y, y_valid, w.lr, stats, std_factor, w_trav, w_reco, w.g_out, O,
-                                w.trav_w, w.trav_raw, confidence_out, grads + o.total, R, d->D, st, rows_dev, conf));
+  if (four) {
+    MlpTrainArgs a{};
+    train_args(a, d, params, x, ldx, y_valid, R, rows_dev, stats, w, conf, four, y, std_factor, w_trav, w_reco, confidence_out, grads);
+    a.o = o; a.D = d->D;
+    return wvn_mlp_train_bwd_launch(a, st);
+  }
   // layer 3
   RET_IF(mlp_wgrad(w.g_out, O, w.h2, d->H2, O, d->H2, R, w.part, grads + o.W3, st));
   RET_IF(wvn_colsum_launch(w.g_out, O, R, O, grads + o.b3, st));

@@ -5,11 +5,13 @@
 // layout).  Three kernels, each over row tiles of TR rows, serve the forward, the training step and the per-segment prediction:
 //     dmlp_fwd_kernel   : x tile -> both h1 (ONE pass over x: the 2 h1 first-layer columns of the pair form one product) -> both h2 ->
 //                         out, the per-row reconstruction loss and, for the fused step, the statistic {n_lab, sum, sum^2, R}: the last
-//                         tile to arrive folds the per-tile partials in tile order (the ticket of mlp_train.hip).  The same kernel
-//                         fills the per-segment table {trav, conf, loss, 0} of segment_predict.hip's paint kernel.
-//     dmlp_bwd_kernel   : gradient seed (loss.py:125-147), dL/dh2 and dL/dh1 of both networks (ReLU masks), per-tile loss sums
-//     dmlp_wgrad_kernel : the six weight and six bias gradients, rows in ascending order (no split-K: one fixed order); workgroup 0
-//                         folds the loss sums behind the flat gradient
+//                         tile to arrive folds the per-tile partials in tile order (mlp_train_device.h: stat_publish_fold, shared
+//                         with mlp_train.hip).  The same kernel fills the per-segment table {trav, conf, loss, 0} of
+//                         segment_predict.hip's paint kernel.
+//     dmlp_bwd_kernel   : gradient seed (mlp_device.h: grad_seed), dL/dh2 and dL/dh1 of both networks (ReLU masks), per-tile
+//                         loss sums (mlp_train_device.h)
+//     weight gradients  : mlp_train.hip's table-driven kernel (wvn_train_wgrad_launch) on the six matrices of the pair; this
+//                         file only fills the table
 // With Adam (mlp.hip) the fused step is FOUR launches, as the fused SimpleMLP step.  The general path (any h1, h2 <= 256, any row
 // count) runs the same forward and data-path kernels with the stage kernels of mlp.hip and the split-K GEMMs of gemm_f32.hip around
 // them (api.hip).  fp32 operands, fp32 FMA chains in one fixed order per output, fp64 statistics: a row's results depend on its
@@ -17,8 +19,7 @@
 // Under TraversabilityLoss the two networks decouple: column 0 of the gradient seed reaches networks.0 only, columns 1 .. D reach
 // networks.1 only; the reconstruction loss of networks.1 still sets the confidence that weights the loss of networks.0.
 #include "common.h"
-#include "mlp_device.h"
-#include "wvn_internal.h"
+#include "mlp_train_device.h"
 
 namespace {
 
@@ -26,17 +27,8 @@ constexpr int TR = 16;       // rows per workgroup
 constexpr int HMAX = 256, DMAX = 1024;
 constexpr int FUSED_H1 = 64, FUSED_H2 = 32, FUSED_RMAX = 2048;
 
-__host__ __device__ inline int x_pitch(int D) { return (D + 3) / 4 * 4 + 4; }
 // torch.relu: NaN stays NaN (a NaN feature row of the per-segment table must not turn into a finite prediction)
 __device__ inline float relu_nan(float v) { return v < 0.f ? 0.f : v; }
-__device__ inline int real_rows(const DmlpArgs& p) { return p.rows_dev ? min(p.R, *p.rows_dev) : p.R; }
-
-// fixed-order sum over the 16 lanes 0..15: butterfly, every lane gets the total
-__device__ inline double sum16_d(double v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 size_t fwd_lds(const DmlpGeom& g) {
   return ((size_t)TR * x_pitch(g.D) + (size_t)TR * 2 * g.H1 + (size_t)TR * 2 * g.H2 + (size_t)TR * 256 + 2 * TR) * sizeof(float);
@@ -169,48 +161,7 @@ __global__ __launch_bounds__(256) void dmlp_fwd_kernel(DmlpArgs p) {
   }
   if (!p.part) return;   // (uniform) no statistic asked for: inference, the table, the general training path
   __syncthreads();
-  // ---- tile partial of the confidence statistic (fp64): rows in ascending order through a butterfly over the 16 rows ----
-  if (tid < 64) {
-    const bool real = tid < TR && row0 + tid < Rr;
-    const bool v = real && p.valid[row0 + tid] != 0;
-    const double l = v ? (double)lr_s[tid] : 0.0;
-    const double n = sum16_d(v ? 1.0 : 0.0), s1 = sum16_d(l), s2 = sum16_d(l * l);
-    float mn = INFINITY, mx = -INFINITY;
-    if (p.minmax) {   // min / max of lr over the tile's real rows (moving_average; min and max are order-free)
-      if (real) mn = mx = lr_s[tid];
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
-    }
-    if (tid == 0) {
-      double* d = p.part + (size_t)blockIdx.x * 4;
-      d[0] = n; d[1] = s1; d[2] = s2;
-      if (p.minmax) { p.part_mm[(size_t)blockIdx.x * 2] = mn; p.part_mm[(size_t)blockIdx.x * 2 + 1] = mx; }
-      // publish: the partial must be visible device-wide before the ticket (the producer form of mlp_train.hip)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned t = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (t == gridDim.x - 1) {   // the last tile to arrive folds the partials in ascending tile order
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        double a = 0, b = 0, c = 0;
-        for (unsigned i = 0; i < gridDim.x; ++i) {
-          const double* e = p.part + (size_t)i * 4;
-          a += __hip_atomic_load(e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          b += __hip_atomic_load(e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          c += __hip_atomic_load(e + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        p.stats[0] = a; p.stats[1] = b; p.stats[2] = c; p.stats[3] = (double)Rr;
-        if (p.minmax) {
-          float lo = INFINITY, hi = -INFINITY;
-          for (unsigned i = 0; i < gridDim.x; ++i) {
-            lo = fminf(lo, __hip_atomic_load(p.part_mm + (size_t)i * 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            hi = fmaxf(hi, __hip_atomic_load(p.part_mm + (size_t)i * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-          }
-          p.minmax[0] = hi; p.minmax[1] = -lo;
-        }
-        __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next step
-      }
-    }
-  }
+  if (tid < 64) stat_publish_fold<TR>(p, lr_s, row0, Rr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -231,48 +182,25 @@ __global__ __launch_bounds__(256) void dmlp_bwd_kernel(DmlpArgs p) {
       gos[i] = row0 + r < p.R ? p.g_out[(size_t)row0 * O + i] : 0.f;
     }
   } else {
-    // ---- gradient seed (loss.py:125-147): 16 threads per row ----
-    const ConfStats cs = conf_stats(p.stats);
-    const float Rtot = (float)p.stats[3], nv = (float)p.stats[0];
-    ConfPost cp{};
-    float xmin = 0.f, xmax = 0.f;
-    if (p.cstate) {   // another method: the post-update statistic from the state and this step's (global) stats
-      cp = conf_post(p.method, p.stats, p.cstate);
-      if (p.minmax) { xmax = p.minmax[0]; xmin = -p.minmax[1]; }
-    }
+    // ---- gradient seed (mlp_device.h): 16 threads per row ----
     const int r = tid >> 4, q = tid & 15, row = row0 + r;
     const bool real = row < Rr;
-    const bool v = real && p.valid[row] != 0;
-    float diff = 0.f, s = 0.f, wrow = 0.f, conf = 0.f;
-    if (real) {
-      conf = p.cstate ? conf_method(p.method, p.lr[row], cp, p.std_factor, xmin, xmax)
-                      : confidence_of(p.lr[row], cs.mean, cs.std, p.std_factor);
-      s = p.out[(size_t)row * O];
-      diff = s - p.y[row];
-      wrow = (v || !p.balanced) ? 1.f : (1.f - conf);   // anomaly_balanced = False: the plain mean of the raw trav loss
-    }
+    const Seed sd = real ? grad_seed(loss_step(p, D), p.lr[row], p.out[(size_t)row * O], p.y[row], p.valid[row] != 0) : Seed{};
     if (q == 0) {
-      const float raw = diff * diff;
-      tw[r] = real ? raw * wrow : 0.f;
-      tw[TR + r] = real ? raw : 0.f;
-      if (p.conf_out && row < p.R) p.conf_out[row] = conf;
-      const float g0 = real ? (p.w_trav / Rtot) * wrow * 2.f * diff * s * (1.f - s) : 0.f;
-      gos[r * O] = g0;
-      if (row < p.R) p.g_out[(size_t)row * O] = g0;
+      tw[r] = sd.raw * sd.wrow;
+      tw[TR + r] = sd.raw;
+      if (p.conf_out && row < p.R) p.conf_out[row] = sd.conf;
+      gos[r * O] = sd.g0;
+      if (row < p.R) p.g_out[(size_t)row * O] = sd.g0;
     }
-    const float cr = v ? (p.w_reco / (nv * (float)D)) * 2.f : 0.f;
     for (int d = q; d < D; d += 16) {
-      const float gv = real ? cr * (p.out[(size_t)row * O + 1 + d] - p.x[(size_t)row * p.ld_row + d]) : 0.f;
+      const float gv = real ? seed_elem(sd, p.out[(size_t)row * O + 1 + d], p.x[(size_t)row * p.ld_row + d]) : 0.f;
       gos[r * O + 1 + d] = gv;
       if (row < p.R) p.g_out[(size_t)row * O + 1 + d] = gv;
     }
   }
   __syncthreads();
-  // ---- tile partial of the loss sums (fp64, rows in ascending order through a butterfly) ----
-  if (!p.seed_given && tid < 64) {
-    const double a = sum16_d(tid < TR ? (double)tw[tid] : 0.0), b = sum16_d(tid < TR ? (double)tw[TR + tid] : 0.0);
-    if (tid == 0) { p.part[(size_t)blockIdx.x * 4] = a; p.part[(size_t)blockIdx.x * 4 + 1] = b; }
-  }
+  if (!p.seed_given && tid < 64) loss_sums_partial<TR>(p, tw);
   // ---- g_h2 of both networks, masked by h2 > 0: networks.0 from seed column 0 (W3a [1][H2]), networks.1 from columns 1 .. D (W3b [D][H2]) ----
   for (int item = tid; item < TR * N2; item += 256) {
     const int r = item / N2, c = item - r * N2, row = row0 + r;
@@ -307,61 +235,6 @@ __global__ __launch_bounds__(256) void dmlp_bwd_kernel(DmlpArgs p) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// wgrad: dW[m][n] = sum_r G[r][m] Hm[r][n] for the six matrices, 32 x 32 output tiles, rows in ascending order; the first column
-// tile of every matrix also forms the bias gradient sum_r G[r][m]; workgroup 0 folds the loss sums
-// ---------------------------------------------------------------------------------------------------------------------------
-struct WTile { const float* G; int ldg; const float* Hm; int ldh; int M, N; float* dW; float* db; };
-struct WTable { WTile t[6]; int first[7]; };
-
-__global__ __launch_bounds__(256) void dmlp_wgrad_kernel(WTable tab, const int* rows_dev, int R, const double* part, int ntiles_rows,
-                                                         float* sums) {
-  __shared__ float Gs[32][33], Hs[32][33];
-  int k = 0;
-  while (k < 5 && (int)blockIdx.x >= tab.first[k + 1]) ++k;
-  const WTile w = tab.t[k];
-  const int b = blockIdx.x - tab.first[k];
-  const int ntn = (w.N + 31) / 32, tm = b / ntn, tn = b - tm * ntn;
-  const int m0 = tm * 32, n0 = tn * 32;
-  const int tid = threadIdx.x, lr_ = tid >> 5, lc = tid & 31;   // loader: row lr_ + 8 i, column lc
-  const int om = tid >> 4, on = (tid & 15) * 2;                 // outputs: rows om, om + 16; columns on, on + 1
-  float acc[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
-  float bsum = 0.f;                                             // tn == 0, tid < 32: sum_r G[r][m0 + tid]
-  const int Rr = rows_dev ? min(R, *rows_dev) : R;
-  for (int r0 = 0; r0 < Rr; r0 += 32) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = r0 + lr_ + 8 * i;
-      Gs[lr_ + 8 * i][lc] = (r < Rr && m0 + lc < w.M) ? w.G[(size_t)r * w.ldg + m0 + lc] : 0.f;
-      Hs[lr_ + 8 * i][lc] = (r < Rr && n0 + lc < w.N) ? w.Hm[(size_t)r * w.ldh + n0 + lc] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) {
-      const float g0 = Gs[r][om], g1 = Gs[r][om + 16], h0 = Hs[r][on], h1 = Hs[r][on + 1];
-      acc[0][0] = fmaf(g0, h0, acc[0][0]); acc[0][1] = fmaf(g0, h1, acc[0][1]);
-      acc[1][0] = fmaf(g1, h0, acc[1][0]); acc[1][1] = fmaf(g1, h1, acc[1][1]);
-    }
-    if (tn == 0 && tid < 32)
-      for (int r = 0; r < 32; ++r) bsum += Gs[r][tid];
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int jn = 0; jn < 2; ++jn) {
-      const int m = m0 + om + 16 * i, n = n0 + on + jn;
-      if (m < w.M && n < w.N) w.dW[(size_t)m * w.N + n] = acc[i][jn];
-    }
-  if (tn == 0 && tid < 32 && m0 + tid < w.M) w.db[m0 + tid] = bsum;
-  if (blockIdx.x == 0 && tid == 0) {   // the loss sums of the bwd launch, tiles in ascending order
-    double a = 0, c = 0;
-    for (int i = 0; i < ntiles_rows; ++i) { a += part[(size_t)i * 4]; c += part[(size_t)i * 4 + 1]; }
-    sums[0] = (float)a;
-    sums[1] = (float)c;
-  }
-}
-
 int opt_in() {
   static LdsOptIn lds_opt_in;   // the largest geometry needs more than 64 KB of dynamic LDS (common.h)
   const int bytes = (int)(fwd_lds_max() > bwd_lds_max() ? fwd_lds_max() : bwd_lds_max());
@@ -393,11 +266,6 @@ int wvn_dmlp_row_tile() { return TR; }
 bool wvn_dmlp_fused_ok(int D, int H1, int H2, int R) {
   return wvn_dmlp_supported(D, H1, H2) && H1 == FUSED_H1 && H2 == FUSED_H2 && R > 0 && R <= FUSED_RMAX;
 }
-size_t wvn_dmlp_scratch_bytes(int R) { return (size_t)ceil_div(R, TR) * (4 * sizeof(double) + 2 * sizeof(float)); }
-void wvn_dmlp_scratch_carve(void* scratch, int R, double** part, float** part_mm) {
-  *part = (double*)scratch;
-  *part_mm = (float*)(*part + (size_t)ceil_div(R, TR) * 4);
-}
 
 int wvn_dmlp_fwd_launch(const DmlpArgs& p, hipStream_t st) {
   if (!wvn_dmlp_supported(p.g.D, p.g.H1, p.g.H2) || p.R <= 0 || p.S <= 0) return WVN_ERR_ARG;
@@ -424,16 +292,12 @@ int wvn_dmlp_wgrad_launch(const DmlpArgs& p, hipStream_t st) {
   const DmlpGeom& g = p.g;
   const int D = g.D, H1 = g.H1, H2 = g.H2, O = D + 1, N1 = 2 * H1, N2 = 2 * H2;
   WTable tab{};
+  tab.n = 6;
   for (int net = 0; net < 2; ++net) {
     const int M3 = net ? D : 1;
     tab.t[3 * net + 0] = WTile{p.g_out + net, O, p.h2 + net * H2, N2, M3, H2, p.grads + g.W3[net], p.grads + g.b3[net]};
     tab.t[3 * net + 1] = WTile{p.g_h2 + net * H2, N2, p.h1 + net * H1, N1, H2, H1, p.grads + g.W2[net], p.grads + g.b2[net]};
     tab.t[3 * net + 2] = WTile{p.g_h1 + net * H1, N1, p.x, p.ld_row, H1, D, p.grads + g.W1[net], p.grads + g.b1[net]};
   }
-  tab.first[0] = 0;
-  for (int k = 0; k < 6; ++k) tab.first[k + 1] = tab.first[k] + ceil_div(tab.t[k].M, 32) * ceil_div(tab.t[k].N, 32);
-  hipLaunchKernelGGL(dmlp_wgrad_kernel, dim3(tab.first[6]), dim3(256), 0, st, tab, p.rows_dev, p.R, p.part, ceil_div(p.R, TR),
-                     p.grads + g.total);
-  WVN_LAUNCH_CHECK();
-  return WVN_OK;
+  return wvn_train_wgrad_launch(tab, p.rows_dev, p.R, p.part, ceil_div(p.R, TR), p.grads + g.total, st);
 }

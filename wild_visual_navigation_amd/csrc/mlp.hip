@@ -66,50 +66,32 @@ __global__ __launch_bounds__(1024) void mlp_stats_kernel(const float* __restrict
   }
 }
 
-// gradient seed wrt the pre-sigmoid / linear outputs + per-row loss terms.  One wave per row.
+// gradient seed wrt the pre-sigmoid / linear outputs + per-row loss terms (mlp_device.h: grad_seed).  One wave per row.
 __global__ __launch_bounds__(256) void mlp_gradout_kernel(const float* __restrict__ out, int ldo,
                                                           const float* __restrict__ x, int ldx,
                                                           const float* __restrict__ y,
                                                           const unsigned char* __restrict__ valid,
-                                                          const float* __restrict__ lr,
-                                                          const double* __restrict__ stats, float std_factor,
-                                                          float w_trav, float w_reco, float* __restrict__ g, int ldg,
+                                                          const float* __restrict__ lr, LossStep c, float* __restrict__ g, int ldg,
                                                           float* __restrict__ trav_w, float* __restrict__ trav_raw,
-                                                          float* __restrict__ conf_out, int R, int D,
-                                                          const int* __restrict__ rows_dev, int method, int balanced,
-                                                          const double* __restrict__ cstate, const float* __restrict__ minmax) {
+                                                          float* __restrict__ conf_out, int R,
+                                                          const int* __restrict__ rows_dev) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= R) return;
   if (rows_dev && row >= *rows_dev) {   // absent row: zero gradient seed, zero loss terms (the GEMMs still walk it)
     if (lane == 0) { trav_raw[row] = 0.f; trav_w[row] = 0.f; if (conf_out) conf_out[row] = 0.f; }
-    for (int d = lane; d < D + 1; d += 64) g[(size_t)row * ldg + d] = 0.f;
+    for (int d = lane; d < c.D + 1; d += 64) g[(size_t)row * ldg + d] = 0.f;
     return;
   }
-  const ConfStats cs = conf_stats(stats);
-  const float Rtot = (float)stats[3], nv = (float)stats[0];
-  const bool v = valid[row] != 0;
-  float conf;
-  if (cstate) {   // another method: the post-update statistic from the state and this step's (global) stats
-    const ConfPost cp = conf_post(method, stats, cstate);
-    const float xmax = minmax ? minmax[0] : 0.f, xmin = minmax ? -minmax[1] : 0.f;
-    conf = conf_method(method, lr[row], cp, std_factor, xmin, xmax);
-  } else {
-    conf = confidence_of(lr[row], cs.mean, cs.std, std_factor);
-  }
-  const float s = out[(size_t)row * ldo];
-  const float diff = s - y[row];
-  const float raw = diff * diff;
-  const float wrow = (v || !balanced) ? 1.f : (1.f - conf);   // anomaly_balanced = False: the plain mean of the raw trav loss
+  const Seed sd = grad_seed(c, lr[row], out[(size_t)row * ldo], y[row], valid[row] != 0);
   if (lane == 0) {
-    trav_raw[row] = raw;
-    trav_w[row] = raw * wrow;
-    if (conf_out) conf_out[row] = conf;
-    g[(size_t)row * ldg] = (w_trav / Rtot) * wrow * 2.f * diff * s * (1.f - s);
+    trav_raw[row] = sd.raw;
+    trav_w[row] = sd.raw * sd.wrow;
+    if (conf_out) conf_out[row] = sd.conf;
+    g[(size_t)row * ldg] = sd.g0;
   }
-  const float cr = v ? (w_reco / (nv * (float)D)) * 2.f : 0.f;
-  for (int d = lane; d < D; d += 64)
-    g[(size_t)row * ldg + 1 + d] = cr * (out[(size_t)row * ldo + 1 + d] - x[(size_t)row * ldx + d]);
+  for (int d = lane; d < c.D; d += 64)
+    g[(size_t)row * ldg + 1 + d] = seed_elem(sd, out[(size_t)row * ldo + 1 + d], x[(size_t)row * ldx + d]);
 }
 
 // extra[0] = sum(trav_w), extra[1] = sum(trav_raw)   (fp64 tree, single workgroup) -> fp32
@@ -267,9 +249,9 @@ int wvn_mlp_gradout_launch(const float* out, int ldo, const float* x, int ldx, c
                            const unsigned char* valid, const float* lr, const double* stats, float std_factor,
                            float w_trav, float w_reco, float* g, int ldg, float* trav_w, float* trav_raw,
                            float* conf_out, float* extra, int R, int D, hipStream_t st, const int* rows_dev, const ConfArgs& conf) {
-  hipLaunchKernelGGL(mlp_gradout_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, st, out, ldo, x, ldx, y, valid, lr, stats,
-                     std_factor, w_trav, w_reco, g, ldg, trav_w, trav_raw, conf_out, R, D, rows_dev, conf.method, conf.balanced,
-                     (const double*)conf.state, (const float*)conf.minmax);
+  const LossStep c{stats, conf.state, conf.minmax, conf.method, conf.balanced, std_factor, w_trav, w_reco, D};
+  hipLaunchKernelGGL(mlp_gradout_kernel, dim3(ceil_div(R, 4)), dim3(256), 0, st, out, ldo, x, ldx, y, valid, lr, c, g, ldg, trav_w,
+                     trav_raw, conf_out, R, rows_dev);
   WVN_LAUNCH_CHECK();
   hipLaunchKernelGGL(mlp_losssum_kernel, dim3(1), dim3(1024), 0, st, trav_w, trav_raw, R, extra);
   WVN_LAUNCH_CHECK();

@@ -1,6 +1,7 @@
-// Device helpers shared by the traversability-MLP training kernels (mlp.hip: one kernel per stage; mlp_train.hip: the
-// four-launch step): the confidence statistic and the confidence of a reconstruction loss, for the four ConfidenceGenerator
-// methods.  Reference: wild_visual_navigation/utils/confidence_generator.py, kalman_filter.py.
+// Device helpers shared by the traversability-MLP training kernels (mlp.hip: one kernel per stage; mlp_train.hip and
+// double_mlp.hip: the four-launch steps): the confidence statistic and the confidence of a reconstruction loss, for the four
+// ConfidenceGenerator methods, and the gradient seed of TraversabilityLoss that is built on them.
+// Reference: wild_visual_navigation/utils/confidence_generator.py, kalman_filter.py, loss.py.
 #pragma once
 #include "common.h"
 #include "../../include/wvn_hip.h"
@@ -106,3 +107,39 @@ __device__ inline float conf_method(int method, float x, const ConfPost& c, floa
   }
   return confidence_of(x, c.mean, c.std, f);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The gradient seed of TraversabilityLoss (loss.py:125-147), per row.  Every training kernel forms it here, with its own thread
+// mapping and destinations: mlp_gradout_kernel (64 lanes per row), mlp_train_bwd_kernel (8), dmlp_bwd_kernel (16).
+// ---------------------------------------------------------------------------------------------------------------------------
+struct LossStep {                  // the constants of a step
+  const double* stats;             // [4] the (global) statistic {n_lab, sum, sum^2, R}
+  const double* cstate;            // nullptr: latest_measurement from stats alone; else the method's state
+  const float* minmax;             // {max, -min} of loss_reco over the step (moving_average), or nullptr
+  int method, balanced;
+  float std_factor, w_trav, w_reco;
+  int D;
+};
+struct Seed { float conf, wrow, raw, g0, cr; };   // confidence, weight and raw value of the row's trav loss, d/d(out[0]), factor of the reco gradient
+
+// a real row: lr = its reconstruction loss, s = out[row][0] (behind the sigmoid); an absent row's seed is Seed{} (all zero)
+__device__ inline Seed grad_seed(const LossStep& c, float lr, float s, float y, bool valid) {
+  Seed o;
+  const ConfStats cs = conf_stats(c.stats);
+  if (c.cstate) {   // another method: the post-update statistic from the state and this step's (global) stats
+    const ConfPost cp = conf_post(c.method, c.stats, c.cstate);
+    const float xmax = c.minmax ? c.minmax[0] : 0.f, xmin = c.minmax ? -c.minmax[1] : 0.f;
+    o.conf = conf_method(c.method, lr, cp, c.std_factor, xmin, xmax);
+  } else {
+    o.conf = confidence_of(lr, cs.mean, cs.std, c.std_factor);
+  }
+  const float Rtot = (float)c.stats[3], nv = (float)c.stats[0];
+  const float diff = s - y;
+  o.wrow = (valid || !c.balanced) ? 1.f : (1.f - o.conf);   // anomaly_balanced = False: the plain mean of the raw trav loss
+  o.raw = diff * diff;
+  o.g0 = (c.w_trav / Rtot) * o.wrow * 2.f * diff * s * (1.f - s);
+  o.cr = valid ? (c.w_reco / (nv * (float)c.D)) * 2.f : 0.f;
+  return o;
+}
+// element d of the seed: d/d(out[1 + d])
+__device__ inline float seed_elem(const Seed& sd, float out, float x) { return sd.cr * (out - x); }

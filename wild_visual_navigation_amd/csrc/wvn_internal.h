@@ -259,17 +259,37 @@ int wvn_mlp_rowloss_stats_launch(const float* out, int ldo, const float* x, int 
                                  const ConfArgs& conf = ConfArgs());
 int wvn_compact_segment_rows_launch(const float* feat, int D, const float* side, int Ds, const int* nseg, int B, int S, float* x,
                                     float* side_out, int* count, hipStream_t st);
-// mlp_train.hip: the four-launch optimisation step (fwd | bwd + wgrad | adam).  off: {W1, b1, W2, b2, W3, b3} offsets into the flat
-// parameter / gradient vectors; scratch: wvn_mlp_train_fused_scratch_bytes(R); sync_word: a zero device word, left at zero
+// The four-launch optimisation step (fwd | bwd + wgrad | adam) of both traversability models.  TrainArgs: the fields SimpleMLP
+// (mlp_train.hip) and DoubleMLP (double_mlp.hip) share; the device code both steps share (mlp_train_device.h) takes it.  A launcher
+// reads the fields of its stage, the others stay zero.
+struct TrainArgs {
+  const float* P;                                          // flat parameters
+  const float* x; int ld_row;                              // [R][D], row stride ld_row
+  int R; const int* rows_dev;                              // rows_dev (optional): only the first *rows_dev rows are real
+  const float* y; const unsigned char* valid;              // [R], [R]
+  float *h1, *h2, *out, *lr;                               // activations of the step, [R][1 + D], [R]
+  float *g_out, *g_h2, *g_h1;                              // their gradients
+  double* part; float* part_mm;                            // per-tile partials (wvn_train_scratch_carve): fwd {n, s1, s2} and {min, max} of lr; bwd {sum trav_w, sum trav_raw}
+  double* stats;                                           // [4] {n_lab, sum, sum^2, R}: out (fwd) / in (bwd)
+  unsigned* ticket;                                        // arrival counter of the fwd launch: a zero word, left at zero
+  float std_factor, w_trav, w_reco; float* conf_out; float* grads;   // conf_out: optional [R]; grads: [ntotal + 2], the two loss sums behind the gradient
+  int method, balanced; const double* cstate; float* minmax;         // ConfArgs of the step (cstate == nullptr: latest_measurement, no state)
+};
+size_t wvn_train_scratch_bytes(int R, int tile);           // part + part_mm for row tiles of `tile` rows
+void wvn_train_scratch_carve(void* scratch, int R, int tile, double** part, float** part_mm);
+// the weight gradients of a fused step (mlp_train.hip): dW[m][n] = sum_r G[r][m] Hm[r][n] and db[m] = sum_r G[r][m] per entry, all in one launch
+struct WTile { const float* G; int ldg; const float* Hm; int ldh; int M, N; float* dW; float* db; };
+struct WTable { WTile t[6]; int n; int first[7]; };        // n entries; first: filled by the launcher (workgroup -> entry)
+// part [ntiles_rows][4]: the loss-sum partials of the bwd launch, folded in tile order into sums[0 .. 1]
+int wvn_train_wgrad_launch(WTable tab, const int* rows_dev, int R, const double* part, int ntiles_rows, float* sums, hipStream_t st);
+
+// ---- SimpleMLP D -> 256 -> 32 -> 1 + D (mlp_train.hip); scratch: wvn_train_scratch_bytes(R, wvn_mlp_train_row_tile()) ----
+struct MlpOff { size_t W1, b1, W2, b2, W3, b3, total; int O; };   // offsets into the flat parameter / gradient vectors
+struct MlpTrainArgs : TrainArgs { MlpOff o; int D; };             // h1 [R][256], h2 [R][32]
 bool wvn_mlp_train_fused_ok(int D, int H1, int H2, int R);
-size_t wvn_mlp_train_fused_scratch_bytes(int R);
-int wvn_mlp_train_fwd_launch(const float* P, const size_t* off, size_t ntotal, const float* x, int ldx, const unsigned char* valid, int R,
-                             int D, const int* rows_dev, float* h1, float* h2, float* out, float* lr, double* stats, void* scratch,
-                             unsigned* sync_word, hipStream_t st, const ConfArgs& conf = ConfArgs());
-int wvn_mlp_train_bwd_launch(const float* P, const size_t* off, size_t ntotal, const float* x, int ldx, const float* y,
-                             const unsigned char* valid, int R, int D, const int* rows_dev, float* h1, float* h2, float* out, float* lr,
-                             float* g_out, float* g_h2, float* g_h1, const double* stats, float std_factor, float w_trav, float w_reco,
-                             float* conf_out, float* grads, void* scratch, hipStream_t st, const ConfArgs& conf = ConfArgs());
+int wvn_mlp_train_row_tile();
+int wvn_mlp_train_fwd_launch(const MlpTrainArgs& p, hipStream_t st);
+int wvn_mlp_train_bwd_launch(const MlpTrainArgs& p, hipStream_t st);   // bwd + wgrad
 int wvn_mlp_gradout_launch(const float* out, int ldo, const float* x, int ldx, const float* y,
                            const unsigned char* valid, const float* lr, const double* stats, float std_factor,
                            float w_trav, float w_reco, float* g, int ldg, float* trav_w, float* trav_raw,
@@ -290,19 +310,11 @@ DmlpGeom wvn_dmlp_geom(int D, int H1, int H2);
 bool wvn_dmlp_supported(int D, int H1, int H2);          // 1 <= D <= 1024, 1 <= h1, h2 <= 256
 bool wvn_dmlp_fused_ok(int D, int H1, int H2, int R);    // the four-launch step: h1 = 64, h2 = 32, R <= 2048
 int wvn_dmlp_row_tile();
-size_t wvn_dmlp_scratch_bytes(int R);                    // per-tile partials of the fused step
-void wvn_dmlp_scratch_carve(void* scratch, int R, double** part, float** part_mm);
-// One argument block for the three kernels; a launcher reads the fields of its stage, the others stay zero.
-struct DmlpArgs {
-  const float* P; DmlpGeom g;
-  const float* x; int ld_row; long long ld_frame; int S;   // row r is row r % S of frame r / S (a training batch: S = R, ld_frame = 0)
-  int R; const int* rows_dev;                              // rows_dev (optional): only the first *rows_dev rows are real
-  const float* y; const unsigned char* valid;
-  float *h1, *h2, *out, *lr;                               // [R][2 h1], [R][2 h2], [R][1 + D], [R]; each optional in the forward
-  float *g_out, *g_h2, *g_h1;                              // [R][1 + D], [R][2 h2], [R][2 h1]
-  double* part; float* part_mm; double* stats; unsigned* ticket;   // part != nullptr: the forward also folds stats (ticket: a zero word, left at zero)
-  float std_factor, w_trav, w_reco; float* conf_out; float* grads;
-  int method, balanced; const double* cstate; float* minmax;       // ConfArgs of the step
+// One argument block for the forward and backward kernels; a launcher reads the fields of its stage, the others stay zero.
+// h1 [R][2 h1], h2 [R][2 h2] (networks.0 | networks.1); h1, h2, out, lr: each optional in the forward; part != nullptr: the forward also folds stats
+struct DmlpArgs : TrainArgs {
+  DmlpGeom g;
+  long long ld_frame; int S;                               // row r is row r % S of frame r / S (a training batch: S = R, ld_frame = 0)
   int seed_given;                                          // bwd: g_out already holds the gradient seed (general path, mlp.hip's gradout kernel)
   float* table; float mean, std; const float* conf_dev;    // forward: the per-segment table {trav, conf, loss, 0} [R][4]
 };
