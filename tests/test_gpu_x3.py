@@ -155,7 +155,9 @@ def test_vit_exact_mode_on_mfma_within_1e3(dev, S, depth, B, precision):
 
 def test_mixed_mode_is_batch_invariant_and_matches_exact(dev):
     """WVN_PREC_MIX against WVN_PREC_X3 on the same frames (the difference is the attention products' operand format), and the same
-    frame alone / inside a batch (kernel selection by batch size must not change a bit)."""
+    frame alone / inside a batch: bit for bit.  At 64 x 64 five frames are 400 token rows, so this is the TILED route only; the split-operand
+    / MX block kernels (from 8192 rows on) have their own invariance checks in tests/test_gpu_block_kernels_wrap.py, and bits are not
+    invariant ACROSS that threshold (MX planes)."""
     sd = OV.make_vit_state_dict("vit_small", 8, pretrain_grid=28, seed=3, depth=3)
     img = torch.rand(5, 3, 64, 64, generator=g(5)).to(dev)
     a = VitBackbone(sd, 64, 8, 6, device=dev, precision="mixed", max_chunk=5).forward_tokens(img)
@@ -167,6 +169,8 @@ def test_mixed_mode_is_batch_invariant_and_matches_exact(dev):
 
 
 def test_exact_agrees_with_fp32_fma_mode_and_is_batch_invariant(dev):
+    """WVN_PREC_X3 against the fp32 FMA mode, and the same frame alone / inside a batch, bit for bit -- on the TILED route only: 400 token
+    rows never reach the split-operand block kernels, whose invariance tests/test_gpu_block_kernels_wrap.py checks at 9456 / 18912 rows."""
     sd = OV.make_vit_state_dict("vit_small", 8, pretrain_grid=28, seed=0, depth=3)
     img = torch.rand(5, 3, 64, 64, generator=g(2)).to(dev)
     a = VitBackbone(sd, 64, 8, 6, device=dev, precision="exact", max_chunk=5).forward_tokens(img)
