@@ -1,6 +1,6 @@
 """Per-pixel traversability inference at BASELINE.json's 448x448 frame size: the fused kernel (csrc/pixel_mlp.hip)
 beside the reference-shaped sequence on the same library (dense upsample -> SimpleMLP forward -> confidence), both fed
-from patch tokens already in HBM.  Prints one JSON line.  WVN_PIXEL_WSPLIT=0 selects the single-bf16 weight variant.
+from patch tokens already in HBM.  Prints one JSON line.
 PIX_D = 384 (default, ViT-S) or 768 (ViT-Base); PIX_H / PIX_G = frame edge and token grid (448 / 56 by default; 518 / 37 is
 DINOv2 ViT-B/14)."""
 import json
@@ -60,19 +60,17 @@ def main():
     t_x3, c_x3, _ = model.forward_per_pixel_exact(tok2d[: G * G], 1, G, (H, H), 0.9, 0.25, 0.5)
     t_bf, c_bf, _ = model.forward_per_pixel(zx[: G * G], 1, G, (H, H), 0.9, 0.25, 0.5, repack=False)
     err = lambda a, b: round(float((a.reshape(-1) - b.reshape(-1)).abs().max()), 6)  # noqa: E731
-    # per 32 pixels: 8 Z blocks and D / 32 reconstruction tiles with 2 (split) or 1 interpolation MFMAs each, 16 (layer 2),
-    # 2 per tile (layer 3), 2 (traversability row): 82 / 62 at D = 384, 130 / 98 at D = 768
-    wsplit = os.environ.get("WVN_PIXEL_WSPLIT", "1") != "0"
+    # per 32 pixels: 8 Z blocks and D / 32 reconstruction tiles with 2 interpolation MFMAs each (split bilinear weights), 16 (layer 2),
+    # 2 per tile (layer 3), 2 (traversability row): 82 at D = 384, 130 at D = 768
     nt = (D + 31) // 32
-    mfma = (2 if wsplit else 1) * (8 + nt) + 16 + 2 * nt + 2
+    mfma = 2 * (8 + nt) + 16 + 2 * nt + 2
     flops = (H * H / 32) * mfma * 32 * 32 * 16 * 2 + G * G * D * 256 * 2
     print(json.dumps({"D": D, "frame": f"{H}x{H}", "grid": G, "batch": B, "fused_ms_per_frame": round(fused_ms, 4),
                       "fused_frames_per_s": round(1e3 / fused_ms, 1), "fused_mfma_tflops": round(flops / fused_ms / 1e9, 1),
                       "unfused_ms_per_frame": round(unfused_ms, 3), "speedup": round(unfused_ms / fused_ms, 1),
                       "exact_fused_ms_per_frame": round(exact_ms, 4), "exact_speedup": round(unfused_ms / exact_ms, 1),
                       "max_abs_err_trav": {"exact_fused": err(t_x3, t_ref), "bf16_fused": err(t_bf, t_ref)},
-                      "max_abs_err_conf": {"exact_fused": err(c_x3, c_ref), "bf16_fused": err(c_bf, c_ref)},
-                      "weight_split": wsplit}))
+                      "max_abs_err_conf": {"exact_fused": err(c_x3, c_ref), "bf16_fused": err(c_bf, c_ref)}}))
 
 
 if __name__ == "__main__":

@@ -10,6 +10,7 @@ tensor).  Two oracles, two tolerances:
   * "reference": the oracle on the fp32 weights -- adds the 2^-9 operand rounding every bf16 GEMM path has.
 Tolerances are written next to each assert."""
 import ctypes as C
+import functools
 
 import pytest
 import torch
@@ -205,6 +206,99 @@ def test_stego_code_features_90d(dev, B, G, H, W):
     t1, l1, c1 = _oracle(tb.float(), G, H, W, sd_bf)
     assert (trav.cpu() - t1).abs().max().item() < 4e-3
     assert ((loss.cpu() - l1).abs() / l1).max().item() < 4e-3
+
+
+def test_stego_code_features_90d_second_pass_of_the_tile_loop(dev):
+    """D = 90, bf16 form, 3 x 14 x 14 = 588 tiles against the grid cap of 2 workgroups x 256 CUs: the persistent tile loop and its
+    token prefetch run a second iteration (the cases above stop at 480 tiles).  Oracle and tolerances of test_stego_code_features_90d."""
+    B, G, H, W = 3, 28, 224, 224
+    sd = OM.make_mlp_state_dict(90, seed=17)
+    tb = (0.5 * torch.randn(B, G * G, 90, generator=g(B + G + 1))).to(torch.bfloat16)
+    model = _model(dev, sd, D=90)
+    zx = torch.zeros(B * G * G, 384, dtype=torch.bfloat16, device=dev)
+    zx[:, :256] = float("nan")                                        # scratch columns need no init
+    zx[:, 256:346] = tb.reshape(B * G * G, 90).to(dev)
+    trav, conf, loss = model.forward_per_pixel(zx, B, G, (H, W), MEAN, STD, FAC, want_loss=True)
+    sd_bf = {k: (bf(v) if k.endswith("weight") else v) for k, v in sd.items()}
+    t1, l1, c1 = _oracle(tb.float(), G, H, W, sd_bf)
+    e_t, e_l = (trav.cpu() - t1).abs().max().item(), ((loss.cpu() - l1).abs() / l1).max().item()
+    print(f"D=90 bf16 {B, G, H, W}: same operands trav {e_t:.2e} rel loss {e_l:.2e}")
+    assert e_t < 4e-3
+    assert e_l < 4e-3
+
+
+# ---- the packed blobs against a host statement of the fragment map (csrc/pixel_mlp.hip: w2_source, w3_source, bias_entry) ----
+def _w2_image(W2):
+    """W2 [32, 256] -> image [16 s][2 h][32 m][8 e] <- W2[m, 32 (s >> 1) + 16 (s & 1) + 8 (e >> 2) + 4 h + (e & 3)]"""
+    s, h, m, e = torch.meshgrid(torch.arange(16), torch.arange(2), torch.arange(32), torch.arange(8), indexing="ij")
+    return W2[m, 32 * (s >> 1) + 16 * (s & 1) + 8 * (e >> 2) + 4 * h + (e & 3)]
+
+
+def _w3_image(W3, D):
+    """W3 [1 + D, 32] -> image [NT + 1 t][2 u][2 h][32 m][8 e] <- row 1 + 32 t + m (zero past D; the last tile holds only row 0,
+    at m == 0), column 16 u + 8 (e >> 2) + 4 h + (e & 3)"""
+    nt = (D + 31) // 32
+    t, u, h, m, e = torch.meshgrid(torch.arange(nt + 1), torch.arange(2), torch.arange(2), torch.arange(32), torch.arange(8), indexing="ij")
+    row = torch.where(t < nt, 1 + 32 * t + m, torch.zeros_like(m))
+    live = torch.where(t < nt, 32 * t + m < D, m == 0)
+    v = W3[row.clamp(max=D), 16 * u + 8 * (e >> 2) + 4 * h + (e & 3)]
+    return torch.where(live, v, torch.zeros_like(v))
+
+
+@functools.lru_cache(maxsize=None)
+def _host_map_checked(D):
+    """The two maps above are permutations onto the matrices: unpack a packed random matrix with the inverse written out per source
+    element (row / column -> image slot) and get the matrix back; every other W3 slot is zero."""
+    W2 = torch.randn(32, 256, generator=g(D))
+    W3 = torch.randn(1 + D, 32, generator=g(D + 1))
+    img2, img3 = _w2_image(W2), _w3_image(W3, D)
+    slot = lambda r: (4 * ((r & 15) >> 3) + (r & 3), ((r & 15) >> 2) & 1, r >> 4)      # row r of a 32-block -> (e, h, k-step)
+    back2 = torch.empty_like(W2)
+    for c in range(256):
+        e, h, u = slot(c & 31)
+        back2[:, c] = img2[2 * (c >> 5) + u, h, :, e]
+    back3 = torch.empty_like(W3)
+    for c in range(32):
+        e, h, u = slot(c)
+        back3[0, c] = img3[-1, u, h, 0, e]
+        back3[1:, c] = img3[:-1, u, h, :, e].reshape(-1)[:D]
+    assert torch.equal(back2, W2) and torch.equal(back3, W3)
+    assert int((img3 != 0).sum()) == int((W3 != 0).sum())
+    return True
+
+
+def _u8(t):
+    return t.contiguous().reshape(-1).view(torch.uint8)
+
+
+@pytest.mark.parametrize("D", [90, 384, 768])
+def test_pack_layout_matches_host_fragment_map(dev, D):
+    """wvn_pixel_mlp_pack / wvn_pixel_mlp_exact_pack, byte for byte: bf16 blob = W1 (zero-padded to DX) | W2 image | W3 image |
+    biases; exact blob = W2 hi | W3 hi | W2 lo | W3 lo | biases with lo = bf16(v - float(hi)) -- so the exact blob's hi images and
+    biases are the bf16 blob's."""
+    assert _host_map_checked(D)
+    nt, dx = (D + 31) // 32, (D if D in (384, 768) else 128)
+    sizes = [256 * D, 256, 32 * 256, 32, (1 + D) * 32, 1 + D]
+    flat = torch.randn(sum(sizes), generator=g(100 + D))
+    W1, b1, W2, b2, W3, b3 = flat.split(sizes)
+    W1, W2, W3 = W1.reshape(256, D), W2.reshape(32, 256), W3.reshape(1 + D, 32)
+    img = torch.cat([_w2_image(W2).reshape(-1), _w3_image(W3, D).reshape(-1)])
+    hi = img.to(torch.bfloat16)
+    lo = (img - hi.float()).to(torch.bfloat16)
+    bias = torch.zeros(256 + 32 + 32 * (nt + 1))
+    bias[:256], bias[256:288], bias[288:288 + D], bias[288 + 32 * nt] = b1, b2, b3[1:], b3[0]
+    w1 = torch.zeros(256, dx)
+    w1[:, :D] = W1
+    want_bf16 = torch.cat([_u8(w1.to(torch.bfloat16)), _u8(hi), _u8(bias)])
+    want_exact = torch.cat([_u8(hi), _u8(lo), _u8(bias)])
+
+    h, d, fd = _lib.lib(), _lib.MlpDesc(D, 256, 32, 0), flat.to(dev)
+    for fn, nbytes, want in ((h.wvn_pixel_mlp_pack, h.wvn_pixel_mlp_pack_bytes(C.byref(d)), want_bf16),
+                             (h.wvn_pixel_mlp_exact_pack, h.wvn_pixel_mlp_exact_pack_bytes(C.byref(d)), want_exact)):
+        assert nbytes == want.numel()
+        got = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device=dev)
+        _lib.check(fn(C.byref(d), fd.data_ptr(), got.data_ptr(), _lib.stream()), "pack")
+        assert torch.equal(got.cpu(), want)
 
 
 def test_predict_per_pixel_with_stego_features(dev, golden):

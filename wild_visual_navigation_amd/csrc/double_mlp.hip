@@ -153,8 +153,7 @@ __global__ __launch_bounds__(256) void dmlp_fwd_kernel(DmlpArgs p) {
       if (p.table && row < p.R) {
         const float cm = p.conf_dev ? p.conf_dev[0] : p.mean, cs = p.conf_dev ? p.conf_dev[1] : p.std;
         const float cf = p.conf_dev ? p.conf_dev[2] : p.std_factor;
-        // (a NaN feature row: torch.clip keeps the NaN loss, fminf / fmaxf would drop it)
-        const float conf = isnan(loss) ? NAN : confidence_of(loss, cm, cs, cf);
+        const float conf = confidence_of_nan(loss, cm, cs, cf);
         *(f32x4_t*)(p.table + (size_t)row * 4) = f32x4_t{trav_s[r], conf, loss, 0.f};
       }
     }

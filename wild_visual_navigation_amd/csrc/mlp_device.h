@@ -26,7 +26,10 @@ __device__ inline float confidence_of(float x, float mean, float std, float f) {
   if (isnan(lo) || isnan(hi)) xc = NAN;
   return 1.f - (xc - lo) / (hi - lo);
 }
-
+// the same for a loss that may be NaN (a NaN feature row): torch.clip keeps the NaN, fminf / fmaxf would drop it
+__device__ inline float confidence_of_nan(float x, float mean, float std, float f) {
+  return isnan(x) ? NAN : confidence_of(x, mean, std, f);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // The other ConfidenceGenerator methods (confidence_generator.py:87-151).  Their statistic has a memory: the persistent device
