@@ -126,6 +126,42 @@ def test_linear_form_c_restatement_equals_its_numpy_statement():
         assert np.array_equal(lab_c, lab_n) and np.array_equal(cent_c, cent_n), (G, H, C, K)
 
 
+def test_degenerate_kmeans_fixtures_are_degenerate_and_both_statements_agree_on_them(capsys):
+    """tests/kmeans_edge_cases.py: piecewise-constant integer codes -- exact ties, clusters that end up empty, zero rows.  On every fixture
+    tests/test_gpu_kmeans_edges.py runs: the numpy statement equals its C restatement (the direct oracle on the direct form's fixtures, the
+    linear one -- labels AND centroids -- on the linear form's; the numpy side only up to P K C = 4e7), and the input IS degenerate: these
+    are conditions on the fixture, not measurements -- a fixture that misses one is to be changed, not the condition."""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import kmeans_edge_cases as KE
+    from oracle import build_oracle, kmeans_linear as KL
+
+    build_oracle.build(force=False)
+    assert OI._oracle_lib() is not None
+    for G, H, C, K, nv in sorted(set(KE.DIRECT_FIXTURES + KE.LINEAR_FIXTURES)):
+        code = KE.degenerate_code(G, C, nv, seed=0)
+        assert code.shape == (G * G, C) and not code[0].any() and np.array_equal(code, np.round(code)) and np.abs(code).max() <= 3
+        assert len(np.unique(code, axis=0)) == nv < K
+        d = KE.describe(code, G, H, K)
+        with capsys.disabled():
+            print(f"\n  degenerate fixture G={G} H={H} C={C} K={K}: {d['duplicate_centroids']} duplicate initial centroids, {d['zero_rows']} zero rows, "
+                  f"first-pass tie share {d['tie_share']:.3f}, {d['used_clusters']} of {K} clusters used", end="")
+        assert d["duplicate_centroids"] >= 1 and d["zero_rows"] >= 100 and d["used_clusters"] < K, (G, H, C, K, d)
+        if K == 20:      # the case all five assign forms of the direct kernel run
+            assert d["tie_share"] >= 0.5, d
+        if H * H * K * C > 4e7:
+            continue
+        if (G, H, C, K, nv) in KE.DIRECT_FIXTURES:
+            dense = OI.upsample_bilinear_fixed(code.reshape(G, G, C), H).reshape(H * H, C)
+            assert np.array_equal(OI.kmeans_cosine_labels(dense, K), OI.kmeans_cosine_labels_numpy(dense, K)), (G, H, C, K)
+        if (G, H, C, K, nv) in KE.LINEAR_FIXTURES:
+            lab_c, cent_c = KL.kmeans_pixels_linear(code, G, H, K)
+            lab_n, cent_n = KL.kmeans_pixels_linear(code, G, H, K, force_numpy=True)
+            assert np.array_equal(lab_c, lab_n) and np.array_equal(cent_c, cent_n), (G, H, C, K)
+
+
 def test_linear_and_direct_statements_of_the_pixel_kmeans_agree_within_float_tolerance():
     """The two definitions are the same function in exact arithmetic.  In fp32 every pixel where their maps differ must lie within
     the float tolerance of a decision boundary of the direct statement: its margin there <= 2 (eps_x + eps_c) with eps_x = 0 (the
