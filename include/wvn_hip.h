@@ -363,6 +363,22 @@ typedef struct wvn_label_pool_node {
 int wvn_label_pool_batched(const wvn_label_pool_node* nodes_dev, int n, int C, int H, int W, int Smax, void* scratch_sum,
                            int* scratch_cnt, void* stream);
 
+/* segmentation_type "random" (feature_extractor.py:96-111, 227-235: nr pixels of the frame are the segments) for a batch, csrc/random_pixels.hip.
+ * Frame b draws with the key (seed, frame0 + b), both unsigned 32-bit (the frame index wraps); the key defines a bijection pi of
+ * [0, H*W) -- a four-round balanced Feistel network on the smallest even number of bits that holds H*W, cycle-walked into range;
+ * round keys from splitmix64 of seed << 32 ^ frame, murmur3's 32-bit finaliser as the round function (tests/random_pixels_ref.py
+ * states it in integers) -- and
+ *   idx [B][nr]   int32: idx[b][j] = pi(j), nr distinct pixels (row-major y * W + x), O(nr) work;
+ *   seg [B][H][W] int32: pi^-1(p) where that is < nr, -1 elsewhere (sample j carries id j).
+ * Every thread evaluates pi or pi^-1 for its own element: no sort, no atomics, no host synchronisation, the same values for any
+ * launch geometry.  idx or seg may be NULL (not both).  WVN_ERR_ARG: nr < 1, nr > H*W, H*W > 2^30, B < 1, B > 65535. */
+int wvn_random_pixels(unsigned seed, unsigned frame0, int B, int H, int W, int nr, int* idx, int* seg, void* stream);
+/* feat[b][j][:] (fp32 [B][nr][D]) = the bilinear (align_corners=True) value of tokens[b] ([G*G][D] fp32) at pixel idx[b][j] = y * H + x
+ * of the H x H map: bit-identical to wvn_upsample_bilinear's dense[b][:][y][x] -- the reference's dense.reshape(D, H*H)[:, idx].T --
+ * from four token rows per sample.  idx is arbitrary (duplicates allowed); an index outside [0, H*H) gives a NaN row.  Any D >= 1.
+ * WVN_ERR_ARG: null pointer, B < 1, B > 65535, G < 1, H < 1, H > 32768, D < 1, nr < 1. */
+int wvn_gather_bilinear(const float* tokens, const int* idx, float* feat, int B, int G, int H, int D, int nr, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Supervision masks: ImageProjector.project_and_render (image_projector.py:126-197: pinhole projection +
  * kornia draw_convex_polygon) fused with the torch.fmin merge of traversability_estimator.py:281-286, for n mission nodes in

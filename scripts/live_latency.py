@@ -1,6 +1,7 @@
 """Single-frame latency of the live node's per-frame path (wvn_feature_extractor_node.py:305-363 with prediction_per_pixel):
-8-bit 448x448 frame already on the GPU -> DINO ViT-S/8 (bf16) -> fused per-pixel traversability + confidence maps.
-One JSON line.  (Replaying the same ~115-launch sequence from a HIP graph was measured at every size -- 1.70 vs 1.73 ms at
+8-bit 448x448 frame already on the GPU -> DINO ViT-S/8 (bf16) -> fused per-pixel traversability + confidence maps
+(predict_per_pixel_ms), the segmentation + pooling half (extract_ms, extract_batch_ms), and both from one backbone pass
+(predict_and_extract_ms: wvn_feature_extractor_node.py:305-393).  One JSON line.  (Replaying the same ~115-launch sequence from a HIP graph was measured at every size -- 1.70 vs 1.73 ms at
 448x448, 1.28 vs 1.31 ms at 224x224 with stego features, bit-identical results -- and is not kept: the launches already overlap
 execution, the frame time is the chain of dependent small-grid kernels.)"""
 import json
@@ -29,10 +30,11 @@ def wall(fn, iters):
     return (time.perf_counter() - t0) / iters * 1e3
 
 
-def run(dev, S, ftype, precision="bf16", arch="vit_small"):
+def run(dev, S, ftype, precision="bf16", arch="vit_small", seg=None):
     v2 = ftype == "dinov2"
     sd = synthetic_vit_state_dict(arch, 14 if v2 else 8, depth=12, pretrain_grid=37 if v2 else 28, dinov2=v2)
-    fe = FeatureExtractor(device=dev, segmentation_type="stego" if ftype == "stego" else "grid", feature_type=ftype, patch_size=14 if v2 else 8,
+    seg = seg or ("stego" if ftype == "stego" else "grid")
+    fe = FeatureExtractor(device=dev, segmentation_type=seg, feature_type=ftype, patch_size=14 if v2 else 8,
                           backbone_type=arch, input_size=S, pretrained_weights=sd, precision=precision)
     params = ExperimentParams()
     params.model.simple_mlp_cfg.input_size = fe.feature_dim
@@ -44,7 +46,13 @@ def run(dev, S, ftype, precision="bf16", arch="vit_small"):
     eager = wall(lambda: fe.predict_per_pixel(frame, model, cg), 50)
     # the segmentation + pooling half of the node's frame (extract): k-means / grid segments, pooled rows
     seg_ms = wall(lambda: fe.extract(frame), 30)
-    return {"frame": f"{S}x{S} uint8", "features": ftype, "backbone": arch, "precision": precision, "predict_per_pixel_ms": round(eager, 3), "extract_ms": round(seg_ms, 3)}
+    # the batched form of that half (no graph structure; for random segmentation ops.random_pixels + ops.gather_bilinear instead of extract's
+    # torch.randperm + pooling pass), and the whole frame -- maps and training message -- from one backbone pass
+    batch_ms = wall(lambda: fe.extract_batch(frame), 30)
+    both_ms = wall(lambda: fe.predict_and_extract(frame, model, cg), 50)
+    return {"frame": f"{S}x{S} uint8", "features": ftype, "segmentation": seg, "backbone": arch, "precision": precision,
+            "predict_per_pixel_ms": round(eager, 3), "extract_ms": round(seg_ms, 3), "extract_batch_ms": round(batch_ms, 3),
+            "predict_and_extract_ms": round(both_ms, 3)}
 
 
 def main():
@@ -57,6 +65,7 @@ def main():
             out += [run(dev, 448, "dino", prec, "vit_base"), run(dev, 518, "dinov2", prec, "vit_base")]
             continue
         out += [run(dev, 448, "dino", prec), run(dev, 224, "stego", prec), run(dev, 224, "dino", prec)]
+    out.append(run(dev, 224, "stego", "mixed", seg="random"))   # the node's default frame with segmentation_type "random" (default.yaml:22)
     print(json.dumps(out))
 
 

@@ -25,6 +25,9 @@ class FeatureExtractor:
         self._input_size = input_size
         self._stego_features_already_computed_in_segmentation = False
         self._tokens = None  # patch-resolution features of the frame(s) being processed
+        # extract_batch's random segmentation: image b of a call draws from the key (random_seed, frame index + b) (ops.random_pixels)
+        self._random_seed = int(kwargs.get("random_seed", 0))
+        self._random_frame = 0   # frames drawn so far without an explicit frame_index
         self.segment_extractor = SegmentExtractor().to(self._device)
         precision = kwargs.get("precision", "mixed")   # the <= 1e-3 mode (the reference is fp32 end to end); "fp16" / "bf16" are opt-in speed paths
 
@@ -139,7 +142,11 @@ class FeatureExtractor:
                       **kwargs) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Batched hot path (no graph structure): img [B,3,H,H] -> (feat [B,S,D], seg [B,H,H] int32,
         n_segments [B] int32).  Rows of ids that do not occur in an image are NaN (the reference's empty
-        mean).  Supported segmentations: grid, slic, stego.  SLIC with ``slic_enforce_connectivity=True`` adds one batched
+        mean).  Supported segmentations: grid, slic, stego, random.  Random (``n_random_pixels=100``, ``frame_index=None``): image b
+        draws n_random_pixels distinct pixels from the key (``random_seed`` of the constructor, frame_index + b), so a frame index reproduces
+        its draw whatever the batching; ``frame_index=None`` counts the frames of the calls so far.  seg is -1 off the samples, sample j carries
+        id j, feat[b, j] is the interpolated feature at that pixel (ops.random_pixels, ops.gather_bilinear: no permutation of the frame, no
+        pooling pass, no host synchronisation; the single-frame ``extract`` keeps its torch.randperm draw).  SLIC with ``slic_enforce_connectivity=True`` adds one batched
         connectivity pass over the B maps (ops.slic_enforce_connectivity: fragments below slic_min_size_factor of a superpixel go to a
         neighbour; ids stay cluster ids, emptied ids give NaN rows); the pass has no host synchronisation.  ``backbone_out``: the tokens ``backbone_stage(img)`` returned."""
         img = img.to(self._device)
@@ -172,6 +179,18 @@ class FeatureExtractor:
             n_seg = ops.slic_num_clusters(H, W, self._slic_num_components)
             nseg = torch.full((B,), n_seg, dtype=torch.int32, device=self._device)
             tokens = backbone_out if backbone_out is not None else self._feature_tokens(img)
+        elif self._segmentation_type == "random":
+            if H != W:
+                raise _lib.WvnError(f"extract_batch: square frames only (the feature map is H x H); got H={H}, W={W}")
+            nr = kwargs.get("n_random_pixels", 100)
+            frame = kwargs.get("frame_index")
+            if frame is None:
+                frame = self._random_frame
+                self._random_frame = (frame + B) & 0xFFFFFFFF
+            idx, seg = ops.random_pixels(B, H, W, nr, seed=self._random_seed, frame0=frame, device=self._device)
+            tokens = backbone_out if backbone_out is not None else self.backbone_stage(img)
+            # a one-pixel segment's "mean" is the interpolated feature at that pixel (feature_extractor.py:96-111)
+            return ops.gather_bilinear(tokens, idx, G, H), seg, torch.full((B,), nr, dtype=torch.int32, device=self._device)
         else:
             raise TypeError(f"extract_batch: segmentation_type [{self._segmentation_type}] not supported")
         feat = None
@@ -193,38 +212,73 @@ class FeatureExtractor:
         kernel (fp16 tokens are rounded to bf16 once), fp32 (exact) extractor -> the hi + lo split form (<= 1e-3 of the reference).
         ``model.input_size`` must equal the extractor's ``feature_dim`` (WvnError otherwise).  Like the reference
         (dino_interface.py:87-90) the map is H x H for an H x W frame."""
-        mean, std, f = 0.0, 1.0, 0.5
-        if confidence_generator is not None:
-            mean, std, f = float(confidence_generator.mean), float(confidence_generator.std), float(confidence_generator.std_factor)
-        return self._predict_per_pixel(img.to(self._device), model, mean, std, f, None, want_loss)
+        img = img.to(self._device)
+        self._check_per_pixel_model(model, "predict_per_pixel")
+        rows, _ = self._per_pixel_tokens(img, model)
+        return self._per_pixel_maps(rows, model, img.shape[0], img.shape[2], *self._confidence_scalars(confidence_generator), want_loss)
 
-    def _predict_per_pixel(self, img, model, mean, std, f, conf_state, want_loss):
-        B, H = img.shape[0], img.shape[2]
-        G = self._grid()
-        stego = self._feature_type == "stego"
-        prec = self._extractor._precision
-        exact = prec in ("exact", "fp32", "mixed")
-        if not hasattr(model, "ZX_COLS"):   # refused before the backbone runs
-            raise _lib.WvnError(f"predict_per_pixel: fused per-pixel inference is not implemented for {type(model).__name__} "
+    @torch.no_grad()
+    def predict_and_extract(self, img: torch.Tensor, model, confidence_generator=None, want_loss: bool = False, **kwargs):
+        """The live node's whole image callback with ``prediction_per_pixel`` (wvn_feature_extractor_node.py:305-393) from ONE backbone
+        pass: img [B,3,H,H] -> (trav [B,H,H], conf [B,H,H], loss_reco | None, feat [B,S,D], seg [B,H,H] int32, nseg [B]), the tuple
+        shape of ``predict_per_segment``.  The three maps are ``predict_per_pixel(img, model, confidence_generator, want_loss)``'s and
+        feat / seg / nseg are ``extract_batch(img, **kwargs)``'s (the ImageFeatures training message), bit for bit; the tokens of the one
+        ViT run (for stego features with flip TTA: of the one paired run, and its one STEGO head) feed both.  grid, slic, stego or random
+        segmentation; dino, dinov2 or stego features; every precision.  SimpleMLP only, refused before the backbone runs."""
+        img = img.to(self._device)
+        self._check_per_pixel_model(model, "predict_and_extract")
+        rows, tokens = self._per_pixel_tokens(img, model)
+        trav, conf, loss = self._per_pixel_maps(rows, model, img.shape[0], img.shape[2], *self._confidence_scalars(confidence_generator),
+                                                want_loss)
+        feat, seg, nseg = self.extract_batch(img, backbone_out=tokens, **kwargs)
+        return trav, conf, loss, feat, seg, nseg
+
+    @staticmethod
+    def _confidence_scalars(confidence_generator):
+        if confidence_generator is None:
+            return 0.0, 1.0, 0.5
+        return float(confidence_generator.mean), float(confidence_generator.std), float(confidence_generator.std_factor)
+
+    def _check_per_pixel_model(self, model, who):
+        """What the fused per-pixel kernel cannot serve is refused before the backbone runs."""
+        if not hasattr(model, "ZX_COLS"):
+            raise _lib.WvnError(f"{who}: fused per-pixel inference is not implemented for {type(model).__name__} "
                                 f"(SimpleMLP only); use predict_per_segment")
         if self.feature_dim != model.input_size:
-            raise _lib.WvnError(f"predict_per_pixel: the extractor's feature_dim is {self.feature_dim}, the model's input_size is "
+            raise _lib.WvnError(f"{who}: the extractor's feature_dim is {self.feature_dim}, the model's input_size is "
                                 f"{model.input_size}")
-        if exact:   # fp32 extractor: hi + lo split MFMA operands in the fused kernel
+
+    def _exact(self) -> bool:
+        return self._extractor._precision in ("exact", "fp32", "mixed")
+
+    def _per_pixel_tokens(self, img, model):
+        """First half of the per-pixel prediction: the one backbone pass -> (rows, tokens).  ``rows`` is what ``_per_pixel_maps`` reads:
+        the fp32 tokens themselves for an fp32 extractor, the bf16 zx rows [B*G*G, ZX_COLS] with the features from column X_COL
+        otherwise.  ``tokens`` [B, G*G, D] fp32 is the same pass's ``backbone_stage(img)`` (for ``extract_batch(backbone_out=...)``)."""
+        B, G = img.shape[0], self._grid()
+        if self._exact():   # fp32 extractor: hi + lo split MFMA operands in the fused kernel
             tokens = self.backbone_stage(img)
-            return model.forward_per_pixel_exact(tokens.reshape(B * G * G, -1), B, G, (H, H), mean, std, f, want_loss=want_loss,
-                                                 conf_state=conf_state)
-        if stego:   # 90-d code (the live node's default feature_type), zero-padded to the 128 columns the layer-1 GEMM reads
-            code = self._extractor.code_tokens(img).reshape(B * G * G, -1)
+            return tokens, tokens
+        if self._feature_type == "stego":   # 90-d code (the live node's default feature_type), zero-padded to the 128 columns the layer-1 GEMM reads
+            tokens = self._extractor.code_tokens(img)
+            code = tokens.reshape(B * G * G, -1)
             zx = torch.zeros(B * G * G, model.ZX_COLS, dtype=torch.bfloat16, device=self._device)
             zx[:, model.X_COL: model.X_COL + code.shape[1]] = code
-        else:
-            zx = torch.empty(B * G * G, model.ZX_COLS, dtype=torch.bfloat16, device=self._device)
-            if self._extractor._model.lowp_dtype != torch.bfloat16:   # (fp16) the kernel takes bf16 features: the fp32 tokens rounded once
-                ops.cast_rows_bf16(self._extractor._model.forward_tokens(img).reshape(B * G * G, -1), zx[:, model.X_COL:])
-            else:
-                self._extractor._model.forward_tokens(img, lowp_out=zx[:, model.X_COL:])
-        return model.forward_per_pixel(zx, B, G, (H, H), mean, std, f, want_loss=want_loss, conf_state=conf_state)
+            return zx, tokens
+        zx = torch.empty(B * G * G, model.ZX_COLS, dtype=torch.bfloat16, device=self._device)
+        if self._extractor._model.lowp_dtype != torch.bfloat16:   # (fp16) the kernel takes bf16 features: the fp32 tokens rounded once
+            tokens = self._extractor._model.forward_tokens(img)
+            ops.cast_rows_bf16(tokens.reshape(B * G * G, -1), zx[:, model.X_COL:])
+        else:   # the final LayerNorm writes its result twice: fp32 tokens, and bf16 straight into the zx rows
+            tokens = self._extractor._model.forward_tokens(img, lowp_out=zx[:, model.X_COL:])
+        return zx, tokens
+
+    def _per_pixel_maps(self, rows, model, B, H, mean, std, f, want_loss):
+        """Second half: the fused up-sample + MLP + confidence kernel on ``_per_pixel_tokens``' rows -> (trav, conf, loss_reco | None)."""
+        G = self._grid()
+        if self._exact():
+            return model.forward_per_pixel_exact(rows.reshape(B * G * G, -1), B, G, (H, H), mean, std, f, want_loss=want_loss)
+        return model.forward_per_pixel(rows, B, G, (H, H), mean, std, f, want_loss=want_loss)
 
     @torch.no_grad()
     def predict_per_segment(self, img: torch.Tensor, model, confidence_generator=None, want_loss: bool = False,

@@ -23,6 +23,41 @@ def upsample_bilinear(tokens: torch.Tensor, grid: int, out_size: int) -> torch.T
     return out
 
 
+def random_pixels(batch: int, H: int, W: int, nr: int, seed: int = 0, frame0: int = 0, device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
+    """segmentation_type "random" (feature_extractor.py:227-235) for a batch, without a permutation of the frame: image b draws
+    ``nr`` distinct pixels from the key (seed, frame0 + b) (both taken modulo 2^32) -> (idx [B,nr] int32 row-major pixel indices,
+    seg [B,H,W] int32: j at idx[b, j], -1 elsewhere).  A function of the key and H*W alone (tests/random_pixels_ref.py)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.WvnError(f"random_pixels: device must be a GPU (got {device}); the HIP path has no CPU fallback")
+    if not (1 <= nr <= H * W):
+        raise _lib.WvnError(f"random_pixels: n_random_pixels={nr} must lie in [1, H*W={H * W}]")
+    idx = torch.empty(batch, nr, dtype=torch.int32, device=device)
+    seg = torch.empty(batch, H, W, dtype=torch.int32, device=device)
+    check(lib().wvn_random_pixels(int(seed) & 0xFFFFFFFF, int(frame0) & 0xFFFFFFFF, batch, H, W, nr, ptr(idx), ptr(seg), stream()),
+          "wvn_random_pixels")
+    return idx, seg
+
+
+def gather_bilinear(tokens: torch.Tensor, idx: torch.Tensor, grid: int, out_size: int) -> torch.Tensor:
+    """tokens [B,G*G,D] fp32, idx [B,nr] pixel indices y * H + x of the H x H map (any order, duplicates allowed) -> feat [B,nr,D]:
+    ``upsample_bilinear(tokens, grid, out_size).reshape(B, D, H*H)[b, :, idx[b]].T`` bit for bit, from four token rows per sample
+    (feature_extractor.py:96-111).  An index outside the map gives a NaN row."""
+    require_cuda(tokens, "tokens")
+    require_cuda(idx, "idx")
+    if tokens.dim() != 3 or idx.dim() != 2 or idx.shape[0] != tokens.shape[0] or tokens.shape[1] != grid * grid or out_size < 1:
+        raise _lib.WvnError(f"gather_bilinear: tokens [B,{grid}*{grid},D] and idx [B,nr] expected, got {tuple(tokens.shape)} and {tuple(idx.shape)}")
+    if tokens.dtype != torch.float32:
+        raise _lib.WvnError(f"gather_bilinear: fp32 tokens expected, got {tokens.dtype}")
+    tokens = tokens.contiguous()
+    idx = _i32(idx).contiguous()
+    B, _, D = tokens.shape
+    nr = idx.shape[1]
+    feat = torch.empty(B, nr, D, dtype=torch.float32, device=tokens.device)
+    check(lib().wvn_gather_bilinear(ptr(tokens), ptr(idx), ptr(feat), B, grid, out_size, D, nr, stream()), "wvn_gather_bilinear")
+    return feat
+
+
 def upsample_nearest_labels(labels: torch.Tensor, out_size: int) -> torch.Tensor:
     """labels [B,G,G] int32 -> [B,H,H] int32 (stego_interface.py:108-109)."""
     require_cuda(labels, "labels")
