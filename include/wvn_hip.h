@@ -675,6 +675,40 @@ int wvn_pixel_mlp_infer_exact(const wvn_mlp_desc* d, const float* params, const 
                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Anomaly detection: the forward pass of the LinearRnvp flow (model/linear_rnvp.py:216-296 as get_model builds it: two coupling
+ * layers with separate s and t networks D -> h -> h -> D, each followed by a permutation; csrc/rnvp.hip).  Per coupling layer,
+ * m = mask:  mu = u*m;  s = tanh(S(mu));  t = T(mu);  x = mu + (1-m)*(u*exp(s) + t);  log_det += sum((1-m)*s);  then x = x[:, p].
+ *   score[r] = sum_c(-z[r][c]^2 / 2 - log(sqrt(2 pi))) + log_det[r]      (AnomalyLoss: logprob.sum(1) + log_det, unit normal prior)
+ * Every matrix product is formed from hi + lo bf16 operand pairs (three MFMAs, fp32 accumulation): the fp32 reference to ~2^-16.
+ * D = 384 or 90, 1 <= h <= 256, flows = 2; 0 / WVN_ERR_ARG otherwise.
+ *
+ * params : fp32, per flow and per network (s, then t): W1 [h][D] | b1 [h] | W2 [h][h] | b2 [h] | W3 [D][h] | b3 [D]  (Linear layout)
+ * mask   : [flows][D] fp32 zeros and ones, D/2 ones per flow;  perm: [flows][D] int64, the permutation buffers p
+ * packed : wvn_rnvp_pack_bytes() bytes, 16-byte aligned, rebuilt by wvn_rnvp_pack whenever parameters, masks or permutations change
+ * rows   : x [R][ldx >= D] fp32.  pixels: tokens [batch*grid*grid][ld_tokens >= D] fp32; row (b, y, x) is the align_corners=True
+ *          bilinear blend of its four tokens, formed in fp32 inside the kernel (the dense tensor is never written), R = batch*out_h*out_w
+ *          (2 <= grid <= 4096, out_h, out_w >= 2, R < 2^31)
+ * score  : [R].  log_det: [R] or NULL.  z: [R][ldz >= D] in the reference's column order, or NULL.
+ * conf   : [R] or NULL: confidence(-score) with the interval formula of ConfidenceGenerator; mean / std / std_factor as
+ *          scalars, or conf_state (may be NULL): the same three floats in device memory, read instead.
+ * wvn_rnvp_row_tile(): the rows one workgroup processes at a time (callers need it for nothing; tests place R around it).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct wvn_rnvp_desc {
+  int D;
+  int h;
+  int flows;
+} wvn_rnvp_desc;
+size_t wvn_rnvp_pack_bytes(const wvn_rnvp_desc* d);
+int wvn_rnvp_row_tile(void);
+int wvn_rnvp_pack(const wvn_rnvp_desc* d, const float* params, const float* mask, const long long* perm, void* packed, void* stream);
+int wvn_rnvp_forward_rows(const wvn_rnvp_desc* d, const void* packed, const float* x, int ldx, long long R, float mean, float std,
+                          float std_factor, const float* conf_state, float* score, float* conf, float* log_det, float* z, int ldz,
+                          void* stream);
+int wvn_rnvp_forward_pixels(const wvn_rnvp_desc* d, const void* packed, const float* tokens, int ld_tokens, int batch, int grid,
+                            int out_h, int out_w, float mean, float std, float std_factor, const float* conf_state, float* score,
+                            float* conf, float* log_det, float* z, int ldz, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused per-segment traversability inference: the node's per-frame path with prediction_per_pixel = False
  * (wvn_feature_extractor_node.py:320-366, quick_start.py:184-210):
  *   input_feat = feat[seg.reshape(-1)];  out = SimpleMLP(input_feat)

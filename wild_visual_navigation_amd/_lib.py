@@ -77,6 +77,10 @@ class MlpDesc(C.Structure):
     _fields_ = [("D", C.c_int), ("H1", C.c_int), ("H2", C.c_int), ("reserved", C.c_int)]
 
 
+class RnvpDesc(C.Structure):
+    _fields_ = [("D", C.c_int), ("h", C.c_int), ("flows", C.c_int)]
+
+
 MLP_KIND_DOUBLE = 1   # include/wvn_hip.h: WVN_MLP_KIND_DOUBLE (MlpDesc.reserved)
 
 
@@ -197,6 +201,11 @@ _SIGNATURES = {
     "wvn_pixel_mlp_exact_pack": ([_p, _p, _p, _p], _i),
     "wvn_pixel_mlp_infer_exact": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
     "wvn_pixel_mlp_infer": ([_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p], _i),
+    "wvn_rnvp_pack_bytes": ([_p], _sz),
+    "wvn_rnvp_row_tile": ([], _i),
+    "wvn_rnvp_pack": ([_p, _p, _p, _p, _p, _p], _i),
+    "wvn_rnvp_forward_rows": ([_p, _p, _p, _i, _ll, _f, _f, _f, _p, _p, _p, _p, _p, _i, _p], _i),
+    "wvn_rnvp_forward_pixels": ([_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _i, _p], _i),
     "wvn_segment_predict_workspace_bytes": ([_p, _i, _i], _sz),
     "wvn_segment_predict": ([_p, _p, _p, _i, _ll, _i, _i, _p, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
     "wvn_debug_gemm_bf16_timed": ([_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p], _i),

@@ -65,9 +65,19 @@ class DoubleMlpCfgParams(_Node):
 
 @dataclass
 class OtherModelCfgParams(_Node):
-    """Config slots of the models outside this build (SimpleGCN / LinearRnvp, experiment_params.py:113-139): callers write
-    ``input_size`` into all four unconditionally (quick_start.py:131-134); the models themselves are outside this build."""
+    """Config slot of the model outside this build (SimpleGCN, experiment_params.py:123-129): callers write
+    ``input_size`` into all four slots unconditionally (quick_start.py:131-134); the model itself is outside this build."""
     input_size: int = 384
+
+
+@dataclass
+class LinearRnvpCfgParams(_Node):
+    input_size: int = 384
+    coupling_topology: List[int] = field(default_factory=lambda: [200])
+    mask_type: str = "odds"
+    conditioning_size: int = 0
+    use_permutation: bool = True
+    single_function: bool = False
 
 
 @dataclass
@@ -77,7 +87,7 @@ class ModelParams(_Node):
     simple_mlp_cfg: SimpleMlpCfgParams = field(default_factory=SimpleMlpCfgParams)
     double_mlp_cfg: DoubleMlpCfgParams = field(default_factory=DoubleMlpCfgParams)
     simple_gcn_cfg: OtherModelCfgParams = field(default_factory=OtherModelCfgParams)
-    linear_rnvp_cfg: OtherModelCfgParams = field(default_factory=OtherModelCfgParams)
+    linear_rnvp_cfg: LinearRnvpCfgParams = field(default_factory=LinearRnvpCfgParams)
 
 
 @dataclass

@@ -765,6 +765,43 @@ int wvn_pixel_mlp_infer_exact(const wvn_mlp_desc* d, const float* params, const 
                                           workspace_bytes, (hipStream_t)stream);
 }
 
+// LinearRnvp forward flow (rnvp.hip): every check is host arithmetic, a refused call launches nothing
+size_t wvn_rnvp_pack_bytes(const wvn_rnvp_desc* d) {
+  if (!d || !wvn_rnvp_supported(d->D, d->h, d->flows)) return 0;
+  return wvn_rnvp_pack_bytes_impl(d->D, d->h);
+}
+int wvn_rnvp_row_tile(void) { return wvn_rnvp_row_tile_impl(); }
+int wvn_rnvp_pack(const wvn_rnvp_desc* d, const float* params, const float* mask, const long long* perm, void* packed, void* stream) {
+  if (!d || !wvn_rnvp_supported(d->D, d->h, d->flows) || !params || !mask || !perm || !packed || ((uintptr_t)packed & 15)) return WVN_ERR_ARG;
+  return wvn_rnvp_pack_launch(d->D, d->h, params, mask, perm, packed, (hipStream_t)stream);
+}
+int wvn_rnvp_forward_rows(const wvn_rnvp_desc* d, const void* packed, const float* x, int ldx, long long R, float mean, float std,
+                          float std_factor, const float* conf_state, float* score, float* conf, float* log_det, float* z, int ldz,
+                          void* stream) {
+  if (!d || !wvn_rnvp_supported(d->D, d->h, d->flows) || !packed || ((uintptr_t)packed & 15) || !x || !score) return WVN_ERR_ARG;
+  if (ldx < d->D || R <= 0 || R > 0x7fffffffll || (z && ldz < d->D)) return WVN_ERR_ARG;
+  RnvpCall c{};
+  c.D = d->D; c.h = d->h; c.packed = packed;
+  c.x = x; c.ldx = ldx; c.R = R;
+  c.mean = mean; c.std = std; c.std_factor = std_factor; c.conf_dev = conf_state;
+  c.score = score; c.conf = conf; c.log_det = log_det; c.z = z; c.ldz = ldz;
+  return wvn_rnvp_forward_launch(c, (hipStream_t)stream);
+}
+int wvn_rnvp_forward_pixels(const wvn_rnvp_desc* d, const void* packed, const float* tokens, int ld_tokens, int batch, int grid,
+                            int out_h, int out_w, float mean, float std, float std_factor, const float* conf_state, float* score,
+                            float* conf, float* log_det, float* z, int ldz, void* stream) {
+  if (!d || !wvn_rnvp_supported(d->D, d->h, d->flows) || !packed || ((uintptr_t)packed & 15) || !tokens || !score) return WVN_ERR_ARG;
+  if (ld_tokens < d->D || batch <= 0 || grid < 2 || grid > 4096 || out_h < 2 || out_w < 2 || (z && ldz < d->D)) return WVN_ERR_ARG;
+  const long long R = (long long)batch * out_h * out_w;
+  if (R > 0x7fffffffll) return WVN_ERR_ARG;
+  RnvpCall c{};
+  c.D = d->D; c.h = d->h; c.packed = packed;
+  c.tokens = tokens; c.ldt = ld_tokens; c.B = batch; c.G = grid; c.Ho = out_h; c.Wo = out_w; c.R = R;
+  c.mean = mean; c.std = std; c.std_factor = std_factor; c.conf_dev = conf_state;
+  c.score = score; c.conf = conf; c.log_det = log_det; c.z = z; c.ldz = ldz;
+  return wvn_rnvp_forward_launch(c, (hipStream_t)stream);
+}
+
 // fused per-segment inference (segment_predict.hip)
 size_t wvn_segment_predict_workspace_bytes(const wvn_mlp_desc* d, int B, int S) {
   if (!d || B <= 0 || S <= 0) return 0;

@@ -343,6 +343,21 @@ int wvn_pixel_mlp_infer_exact_launch(int D, int h1, int h2, const float* params,
                                      const float* conf_state, float* trav, float* conf, float* loss, void* workspace,
                                      size_t workspace_bytes, hipStream_t st);
 
+// ---- LinearRnvp forward flow (rnvp.hip) -------------------------------------------------------------------------------------
+struct RnvpCall {
+  int D, h;
+  const void* packed;
+  const float* x; int ldx; long long R;                    // rows source (x != nullptr) ...
+  const float* tokens; int ldt, B, G, Ho, Wo;              // ... or pixels source
+  float mean, std, std_factor; const float* conf_dev;
+  float* score; float* conf; float* log_det; float* z; int ldz;
+};
+bool wvn_rnvp_supported(int D, int h, int flows);
+size_t wvn_rnvp_pack_bytes_impl(int D, int h);
+int wvn_rnvp_row_tile_impl();
+int wvn_rnvp_pack_launch(int D, int h, const float* params, const float* mask, const long long* perm, void* packed, hipStream_t st);
+int wvn_rnvp_forward_launch(const RnvpCall& c, hipStream_t st);
+
 // ---- fused per-segment traversability inference (segment_predict.hip) --------------------------------------------------
 bool wvn_segment_predict_supported(int D, int h1, int h2);
 size_t wvn_segment_predict_workspace_bytes_impl(int B, int S);

@@ -224,7 +224,8 @@ class FeatureExtractor:
         shape of ``predict_per_segment``.  The three maps are ``predict_per_pixel(img, model, confidence_generator, want_loss)``'s and
         feat / seg / nseg are ``extract_batch(img, **kwargs)``'s (the ImageFeatures training message), bit for bit; the tokens of the one
         ViT run (for stego features with flip TTA: of the one paired run, and its one STEGO head) feed both.  grid, slic, stego or random
-        segmentation; dino, dinov2 or stego features; every precision.  SimpleMLP only, refused before the backbone runs."""
+        segmentation; dino, dinov2 or stego features; every precision.  SimpleMLP or LinearRnvp (trav = conf = confidence(-score), third map
+        -score), anything else is refused before the backbone runs."""
         img = img.to(self._device)
         self._check_per_pixel_model(model, "predict_and_extract")
         rows, tokens = self._per_pixel_tokens(img, model)
@@ -241,9 +242,9 @@ class FeatureExtractor:
 
     def _check_per_pixel_model(self, model, who):
         """What the fused per-pixel kernel cannot serve is refused before the backbone runs."""
-        if not hasattr(model, "ZX_COLS"):
+        if not hasattr(model, "ZX_COLS") and not self._flow_model(model):
             raise _lib.WvnError(f"{who}: fused per-pixel inference is not implemented for {type(model).__name__} "
-                                f"(SimpleMLP only); use predict_per_segment")
+                                f"(SimpleMLP and LinearRnvp only); use predict_per_segment")
         if self.feature_dim != model.input_size:
             raise _lib.WvnError(f"{who}: the extractor's feature_dim is {self.feature_dim}, the model's input_size is "
                                 f"{model.input_size}")
@@ -251,12 +252,18 @@ class FeatureExtractor:
     def _exact(self) -> bool:
         return self._extractor._precision in ("exact", "fp32", "mixed")
 
+    @staticmethod
+    def _flow_model(model) -> bool:
+        """LinearRnvp (anomaly detection): its per-pixel kernel (csrc/rnvp.hip) reads the fp32 tokens whatever the extractor's
+        precision; trav = conf = confidence(-score), the third map is -score."""
+        return getattr(model, "PER_PIXEL_FP32_TOKENS", False)
+
     def _per_pixel_tokens(self, img, model):
         """First half of the per-pixel prediction: the one backbone pass -> (rows, tokens).  ``rows`` is what ``_per_pixel_maps`` reads:
         the fp32 tokens themselves for an fp32 extractor, the bf16 zx rows [B*G*G, ZX_COLS] with the features from column X_COL
         otherwise.  ``tokens`` [B, G*G, D] fp32 is the same pass's ``backbone_stage(img)`` (for ``extract_batch(backbone_out=...)``)."""
         B, G = img.shape[0], self._grid()
-        if self._exact():   # fp32 extractor: hi + lo split MFMA operands in the fused kernel
+        if self._exact() or self._flow_model(model):   # fp32 extractor: hi + lo split MFMA operands in the fused kernel
             tokens = self.backbone_stage(img)
             return tokens, tokens
         if self._feature_type == "stego":   # 90-d code (the live node's default feature_type), zero-padded to the 128 columns the layer-1 GEMM reads
@@ -276,7 +283,7 @@ class FeatureExtractor:
     def _per_pixel_maps(self, rows, model, B, H, mean, std, f, want_loss):
         """Second half: the fused up-sample + MLP + confidence kernel on ``_per_pixel_tokens``' rows -> (trav, conf, loss_reco | None)."""
         G = self._grid()
-        if self._exact():
+        if self._exact() or self._flow_model(model):
             return model.forward_per_pixel_exact(rows.reshape(B * G * G, -1), B, G, (H, H), mean, std, f, want_loss=want_loss)
         return model.forward_per_pixel(rows, B, G, (H, H), mean, std, f, want_loss=want_loss)
 

@@ -1,11 +1,13 @@
-"""get_model -- wild_visual_navigation/model/network_register.py:44-55 (class-name registry; SimpleMLP and DoubleMLP are on
+"""get_model -- wild_visual_navigation/model/network_register.py:44-55 (class-name registry; SimpleMLP, DoubleMLP and LinearRnvp are on
 the MI355X path)."""
 import inspect
 
 from .double_mlp import DoubleMLP
+from .linear_rnvp import LinearRnvp
 from .simple_mlp import SimpleMLP
 
-_REGISTER = {"SimpleMLP": (SimpleMLP, "simple_mlp_cfg"), "DoubleMLP": (DoubleMLP, "double_mlp_cfg")}
+_REGISTER = {"SimpleMLP": (SimpleMLP, "simple_mlp_cfg"), "DoubleMLP": (DoubleMLP, "double_mlp_cfg"),
+             "LinearRnvp": (LinearRnvp, "linear_rnvp_cfg")}
 
 
 def _get(cfg, key):
@@ -18,7 +20,11 @@ def get_model(model_cfg):
         raise KeyError(f"model '{name}' is not part of the MI355X hot path (available: {list(_REGISTER)})")
     cls, key = _REGISTER[name]
     sub = _get(model_cfg, key)
-    args = [a for a in inspect.signature(cls.__init__).parameters if a != "self"]   # (DoubleMLP has no ``reconstruction``)
-    kw = dict(sub) if isinstance(sub, dict) else {k: getattr(sub, k) for k in args}
-    kw["hidden_sizes"] = list(kw["hidden_sizes"])
+    # the constructor arguments the cfg node carries (DoubleMLP has no ``reconstruction``; LinearRnvp's cfg leaves flow_n,
+    # batch_norm and **kwargs to the constructor's defaults, as upstream's LinearRnvp(**cfg) does)
+    args = [a for a in inspect.signature(cls.__init__).parameters if a not in ("self", "kwargs")]
+    kw = dict(sub) if isinstance(sub, dict) else {k: getattr(sub, k) for k in args if hasattr(sub, k)}
+    for k in ("hidden_sizes", "coupling_topology"):
+        if kw.get(k) is not None:
+            kw[k] = list(kw[k])
     return cls(**kw)

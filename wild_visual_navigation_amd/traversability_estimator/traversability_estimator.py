@@ -6,6 +6,10 @@ constructor (10 reference arguments), ``train() -> dict``, ``make_batch``, ``add
 (``_model``, ``_traversability_loss._confidence_generator``, ``_mission_graph``, ``_step``, ``_visualizer``).  Forward, loss, backward and Adam run in the fused HIP phases
 (trainer.py); with torch.distributed initialised every rank trains on its own frames and the two
 small all-reduces keep the replicas identical.
+
+``anomaly_detection=True`` (LinearRnvp + AnomalyLoss, traversability_estimator.py:83-96): the model's forward flow is a HIP kernel
+at inference; a training step is at most 8 nodes x 100 labelled segment rows and runs on autograd over the model's torch
+statement with ``torch.optim.Adam``, on one rank.
 """
 import os
 from threading import Lock
@@ -14,7 +18,7 @@ import torch
 
 from ..distributed import all_ranks_ready
 from ..model import get_model
-from ..utils import Batch, TraversabilityLoss
+from ..utils import AnomalyLoss, Batch, TraversabilityLoss
 from .. import ops
 from .graphs import BaseGraph, DistanceWindowGraph, MaxElementsGraph
 from .nodes import MissionNode, SupervisionNode
@@ -30,8 +34,6 @@ class TraversabilityEstimator:
                  supervision_distance_thr: float = None, min_samples_for_training: int = 10,
                  vis_node_index: int = 10, mode=False, extraction_store_folder=None,
                  anomaly_detection: bool = False):
-        if anomaly_detection:
-            raise ValueError("anomaly_detection (LinearRnvp / AnomalyLoss) is outside the MI355X hot path")
         self._device = torch.device(device)
         self._mode = mode
         self._extraction_store_folder = extraction_store_folder
@@ -58,6 +60,17 @@ class TraversabilityEstimator:
         self._model = get_model(_get(params, "model")).to(self._device)
         self._model.train()
         loss_cfg, gen = _get(params, "loss"), _get(params, "general")
+        self._loss = torch.tensor([torch.inf])
+        self._step = 0
+        if anomaly_detection:
+            if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                raise ValueError("anomaly_detection=True trains on one rank (the autograd step has no gradient all-reduce)")
+            la = _get(params, "loss_anomaly")
+            self._traversability_loss = AnomalyLoss(
+                **{k: _get(la, k) for k in la}, log_enabled=_get(gen, "log_confidence"),
+                log_folder=_get(gen, "model_path") or "/tmp").to(self._device)
+            self._optimizer = torch.optim.Adam(self._model.parameters(), lr=_get(_get(params, "optimizer"), "lr"))
+            return
         self._traversability_loss = TraversabilityLoss(
             w_trav=_get(loss_cfg, "w_trav"), w_reco=_get(loss_cfg, "w_reco"), w_temp=_get(loss_cfg, "w_temp"),
             anomaly_balanced=_get(loss_cfg, "anomaly_balanced"), model=self._model, method=_get(loss_cfg, "method"),
@@ -69,8 +82,6 @@ class TraversabilityEstimator:
                                      w_trav=_get(loss_cfg, "w_trav"), w_reco=_get(loss_cfg, "w_reco"),
                                      method=_get(loss_cfg, "method"), anomaly_balanced=_get(loss_cfg, "anomaly_balanced"))
         self._cg_version = None   # the ConfidenceGenerator state version the trainer's device state was last loaded from
-        self._loss = torch.tensor([torch.inf])
-        self._step = 0
 
     # ------------------------------------------------------------------------------------------------
     @property
@@ -207,7 +218,7 @@ class TraversabilityEstimator:
 
     def make_batch(self, batch_size: int = 8):
         nodes = self._mission_graph.get_n_random_valid_nodes(n=batch_size)
-        return Batch.from_data_list([n.as_pyg_data() for n in nodes])
+        return Batch.from_data_list([n.as_pyg_data(anomaly_detection=self._anomaly_detection) for n in nodes])
 
     def train(self):
         """traversability_estimator.py:449-497: one optimisation step; returns the reference's dict."""
@@ -223,6 +234,8 @@ class TraversabilityEstimator:
         # every rank steps iff ALL ranks have a batch (a rank that skipped alone would leave the others hanging in RCCL).
         if all_ranks_ready(graph is not None, self._device):
             if graph is not None:
+                if self._anomaly_detection:
+                    return self._train_anomaly(graph, return_dict)
                 with self._learning_lock:
                     losses = self.train_on_batch(graph.x, graph.y, graph.y_valid)
                 log_step = (self._step % 20) == 0
@@ -233,6 +246,26 @@ class TraversabilityEstimator:
                 return_dict["loss_total"], return_dict["loss_trav"], return_dict["loss_reco"] = vals[0], vals[1], vals[2]
                 return return_dict
         return_dict["loss_total"] = -1
+        return return_dict
+
+    def _train_anomaly(self, graph, return_dict):
+        """traversability_estimator.py:464-495 in the anomaly-detection mode: forward (the model's torch statement), AnomalyLoss,
+        backward, ``torch.optim.Adam`` step."""
+        log_step = (self._step % 20) == 0
+        with self._learning_lock:
+            graph.x = graph.x.to(self._device)
+            res = self._model(graph)
+            self._loss, loss_aux, _ = self._traversability_loss(graph, res, step=self._step, log_step=log_step)
+            self._optimizer.zero_grad()
+            self._loss.backward()
+            self._optimizer.step()
+        total = self._loss.item()
+        if log_step:
+            print(f"step: {self._step} | loss: {total:5f} | loss_trav: {loss_aux['loss_trav'].item():5f} | "
+                  f"loss_reco: {loss_aux['loss_reco'].item():5f}")
+        self._step += 1
+        return_dict["loss_total"] = total
+        return_dict["loss_trav"], return_dict["loss_reco"] = loss_aux["loss_trav"].item(), loss_aux["loss_reco"].item()
         return return_dict
 
     def train_on_batch(self, x: torch.Tensor, y: torch.Tensor, y_valid: torch.Tensor) -> torch.Tensor:
@@ -262,7 +295,8 @@ class TraversabilityEstimator:
             torch.save({
                 "step": self._step,
                 "model_state_dict": self._model.state_dict(),
-                "optimizer_state_dict": self._optimizer.optimizer_state_dict(),
+                "optimizer_state_dict": (self._optimizer.state_dict() if self._anomaly_detection
+                                         else self._optimizer.optimizer_state_dict()),
                 "traversability_loss_state_dict": self._traversability_loss.state_dict(),
                 "loss": self.loss,
             }, checkpoint_file)
@@ -274,7 +308,10 @@ class TraversabilityEstimator:
             self._pause_training = True
             ck = torch.load(checkpoint_path, map_location=self._device, weights_only=False)
             self._model.load_state_dict(ck["model_state_dict"])
-            self._optimizer.load_optimizer_state_dict(ck["optimizer_state_dict"])
+            if self._anomaly_detection:
+                self._optimizer.load_state_dict(ck["optimizer_state_dict"])
+            else:
+                self._optimizer.load_optimizer_state_dict(ck["optimizer_state_dict"])
             self._traversability_loss.load_state_dict(ck["traversability_loss_state_dict"])
             self._step = ck["step"]
             self._loss = torch.tensor([ck["loss"]])

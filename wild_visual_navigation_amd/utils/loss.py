@@ -1,4 +1,4 @@
-"""TraversabilityLoss -- wild_visual_navigation/utils/loss.py:57-164.
+"""TraversabilityLoss and AnomalyLoss -- wild_visual_navigation/utils/loss.py:57-164, 16-54.
 
 ``forward`` keeps the reference signature and return triple.  The optimisation step of
 ``TraversabilityEstimator.train`` does not go through this module's autograd graph: loss, gradient and
@@ -78,10 +78,25 @@ class TraversabilityLoss(torch.nn.Module):
 
 
 class AnomalyLoss(torch.nn.Module):
-    """wild_visual_navigation/utils/loss.py:16-54 belongs to the LinearRnvp anomaly-detection ablation (non-default model,
-    SURVEY.md section 2: out of scope).  The name exists because callers import it unconditionally (quick_start.py:12,
-    wvn_feature_extractor_node.py:12); constructing it is refused."""
+    """wild_visual_navigation/utils/loss.py:16-54: the loss of the anomaly-detection mode.  ``res`` is LinearRnvp's forward dict;
+    the loss is the mean negative log-likelihood, the confidence statistic is fed with -(logprob.sum(1) + log_det) of every row
+    (all rows of a batch are positives in this mode)."""
 
-    def __init__(self, *args, **kwargs):
+    def __init__(self, confidence_std_factor: float, method: str, log_enabled: bool = False, log_folder: str = "/tmp"):
         super().__init__()
-        raise ValueError("AnomalyLoss (LinearRnvp anomaly detection) is outside the MI355X hot path")
+        self._confidence_generator = ConfidenceGenerator(std_factor=confidence_std_factor, method=method,
+                                                         log_enabled=log_enabled, log_folder=log_folder)
+
+    def forward(self, graph: Optional[Data], res: dict, update_generator: bool = True, step: int = 0, log_step: bool = False):
+        losses = res["logprob"].sum(1) + res["log_det"]
+        x = -losses.clone().detach()
+        if update_generator:
+            confidence = self._confidence_generator.update(x=x, x_positive=x, step=step)
+        else:
+            # (the reference leaves ``confidence`` unbound here and raises; the statistic is read without being moved instead)
+            confidence = self._confidence_generator.inference_without_update(x)
+        loss_aux = {"loss_trav": torch.tensor([0.0]), "loss_reco": torch.tensor([0.0]), "confidence": confidence}
+        return -torch.mean(losses), loss_aux, confidence
+
+    def update_node_confidence(self, node):
+        node.confidence = 0
