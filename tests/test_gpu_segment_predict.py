@@ -89,6 +89,43 @@ def test_one_segment_per_pixel(dev, D, B):
     assert (conf.cpu().double() - c0).abs().max().item() <= 1e-4
 
 
+@pytest.mark.parametrize("D,B,S", [(91, 2, 17), (257, 1, 5)])
+def test_layer_corners_match_fp64_oracle(dev, D, B, S):
+    """The corners of the tile layers (csrc/mlp_tile_device.h) the cases above do not reach on the table path.  D = 91: layer 1
+    takes its odd-D tail, and 34 rows leave two real rows in the last tile of 16.  D = 257: 258 output columns, so the second
+    column pass of layer 3 has two live threads, the first of them on column 256 (first of its pass, but not column 0).
+    Every id occurs in the 8 x 8 map."""
+    H = W = 8
+    model, sd = _model(dev, D)
+    feat = _features(B, S, D, seed=D + S)
+    seg = (torch.arange(B * H * W, dtype=torch.int32) % S).reshape(B, H, W)
+    trav, conf, loss = model.forward_per_segment(feat.to(dev), seg.to(dev), MEAN, STD, FAC, want_loss=True)
+    t0, l0, c0 = (_paint(r, seg) for r in _oracle_rows(sd, feat))
+    assert (trav.cpu().double() - t0).abs().max().item() <= 1e-5
+    assert ((loss.cpu().double() - l0).abs() / l0).max().item() <= 1e-5
+    assert (conf.cpu().double() - c0).abs().max().item() <= 1e-4
+
+
+def test_referenced_nan_row_stays_nan(dev):
+    """A NaN feature row that the map references paints NaN trav and loss (torch.relu keeps NaN: the table path's ReLU form), and
+    changes no bit of any other pixel.  (The confidence of the NaN row is not asserted here.)"""
+    S, D, H, W = 20, 90, 8, 8
+    model, _ = _model(dev, D)
+    feat = _features(1, S, D, seed=9)
+    seg = (torch.arange(H * W, dtype=torch.int32) % S).reshape(1, H, W)
+    zeroed = feat.clone()
+    zeroed[0, 3] = 0.0
+    feat[0, 3] = float("nan")
+    got = [o.cpu() for o in model.forward_per_segment(feat.to(dev), seg.to(dev), MEAN, STD, FAC, want_loss=True)]
+    ref = [o.cpu() for o in model.forward_per_segment(zeroed.to(dev), seg.to(dev), MEAN, STD, FAC, want_loss=True)]
+    hit = seg == 3
+    assert hit.any()
+    assert torch.isnan(got[0][hit]).all() and torch.isnan(got[2][hit]).all()
+    for o, r in zip(got, ref):
+        assert torch.isfinite(o[~hit]).all()
+        assert torch.equal(o[~hit], r[~hit])
+
+
 @pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
 def test_id_rule(dev, dtype):
     """torch indexing: ids in [-S, 0) select row S + id; ids >= S or < -S give NaN in all three outputs; NaN rows nobody references

@@ -7,9 +7,10 @@
 //                         out, the per-row reconstruction loss and, for the fused step, the statistic {n_lab, sum, sum^2, R}: the last
 //                         tile to arrive folds the per-tile partials in tile order (mlp_train_device.h: stat_publish_fold, shared
 //                         with mlp_train.hip).  The same kernel fills the per-segment table {trav, conf, loss, 0} of
-//                         segment_predict.hip's paint kernel.
-//     dmlp_bwd_kernel   : gradient seed (mlp_device.h: grad_seed), dL/dh2 and dL/dh1 of both networks (ReLU masks), per-tile
-//                         loss sums (mlp_train_device.h)
+//                         segment_predict.hip's paint kernel; the x-tile load, the row sum of the loss partials and the table
+//                         write are the text of that file's table kernel (mlp_tile_device.h).  The pair layers are this file's.
+//     dmlp_bwd_kernel   : gradient seed (mlp_train_device.h: seed_tile, shared with mlp_train.hip), dL/dh2 and dL/dh1 of both
+//                         networks (ReLU masks), per-tile loss sums (mlp_train_device.h)
 //     weight gradients  : mlp_train.hip's table-driven kernel (wvn_train_wgrad_launch) on the six matrices of the pair; this
 //                         file only fills the table
 // With Adam (mlp.hip) the fused step is FOUR launches, as the fused SimpleMLP step.  The general path (any h1, h2 <= 256, any row
@@ -27,9 +28,6 @@ constexpr int TR = 16;       // rows per workgroup
 constexpr int HMAX = 256, DMAX = 1024;
 constexpr int FUSED_H1 = 64, FUSED_H2 = 32, FUSED_RMAX = 2048;
 
-// torch.relu: NaN stays NaN (a NaN feature row of the per-segment table must not turn into a finite prediction)
-__device__ inline float relu_nan(float v) { return v < 0.f ? 0.f : v; }
-
 size_t fwd_lds(const DmlpGeom& g) {
   return ((size_t)TR * x_pitch(g.D) + (size_t)TR * 2 * g.H1 + (size_t)TR * 2 * g.H2 + (size_t)TR * 256 + 2 * TR) * sizeof(float);
 }
@@ -41,7 +39,8 @@ size_t bwd_lds_max() { return bwd_lds(wvn_dmlp_geom(DMAX, HMAX, HMAX)); }
 // forward
 // ---------------------------------------------------------------------------------------------------------------------------
 // one layer of the pair on the tile: out[r][c] = relu(b[c] + sum_k in[r][net(c) * in_off + k] * W_net(c)[c'][k]) for the 2 * N columns
-// of both networks.  A work item is (column, row half): 8 accumulators, one ascending FMA chain each.
+// of both networks.  A work item is (column, row half): 8 accumulators, one ascending FMA chain each.  relu_nan: a NaN feature row
+// of the per-segment table must not turn into a finite prediction.
 __device__ inline void pair_layer(const float* __restrict__ P, size_t oWa, size_t oWb, size_t oba, size_t obb, int N, int K,
                                   const float* __restrict__ in, int in_pitch, int in_off, float* __restrict__ outs, int tid) {
   const int N2 = 2 * N;
@@ -78,15 +77,7 @@ __global__ __launch_bounds__(256) void dmlp_fwd_kernel(DmlpArgs p) {
   const int tid = threadIdx.x, row0 = blockIdx.x * TR;
   const int Rr = real_rows(p);
   // ---- x tile (rows past R / past the device-side count: zeros) ----
-  for (int i = tid; i < TR * D; i += 256) {
-    const int r = i / D, k = i - r * D, gr = row0 + r;
-    float v = 0.f;
-    if (gr < Rr) {
-      const int b = gr / p.S, s = gr - b * p.S;
-      v = p.x[b * p.ld_frame + (long long)s * p.ld_row + k];
-    }
-    xs[r * DP + k] = v;
-  }
+  load_x_tile<TR, true>(xs, p.x, p.ld_row, p.ld_frame, p.S, D, row0, Rr);
   __syncthreads();
   pair_layer(p.P, g.W1[0], g.W1[1], g.b1[0], g.b1[1], H1, D, xs, DP, 0, h1s, tid);
   __syncthreads();
@@ -138,24 +129,16 @@ __global__ __launch_bounds__(256) void dmlp_fwd_kernel(DmlpArgs p) {
     for (int r = 0; r < TR; ++r) part[r * 256 + tid] = s[r];
   }
   __syncthreads();
-  // ---- per-row sum of the 256 partials: 16 lanes per row, lane q adds partials q, q + 16, ... in order, then a butterfly ----
   {
     const int r = tid >> 4, q = tid & 15, row = row0 + r;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += part[r * 256 + q + 16 * i];
-    s += __shfl_xor(s, 8, 64); s += __shfl_xor(s, 4, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 1, 64);
-    const float loss = s / (float)D;
+    const float loss = row_sum_256(part) / (float)D;
     if (q == 0) {
       const float lr = row < Rr ? loss : 0.f;
       lr_s[r] = lr;
       if (p.lr && row < p.R) p.lr[row] = lr;
-      if (p.table && row < p.R) {
-        const float cm = p.conf_dev ? p.conf_dev[0] : p.mean, cs = p.conf_dev ? p.conf_dev[1] : p.std;
-        const float cf = p.conf_dev ? p.conf_dev[2] : p.std_factor;
-        const float conf = confidence_of_nan(loss, cm, cs, cf);
-        *(f32x4_t*)(p.table + (size_t)row * 4) = f32x4_t{trav_s[r], conf, loss, 0.f};
-      }
+      // confidence_of_nan: a NaN loss keeps a NaN confidence (seg_table_kernel writes confidence_of)
+      if (p.table && row < p.R)
+        table_row_write<confidence_of_nan>(p.table + (size_t)row * 4, trav_s[r], loss, p.conf_dev, p.mean, p.std, p.std_factor);
     }
   }
   if (!p.part) return;   // (uniform) no statistic asked for: inference, the table, the general training path
@@ -181,22 +164,7 @@ __global__ __launch_bounds__(256) void dmlp_bwd_kernel(DmlpArgs p) {
       gos[i] = row0 + r < p.R ? p.g_out[(size_t)row0 * O + i] : 0.f;
     }
   } else {
-    // ---- gradient seed (mlp_device.h): 16 threads per row ----
-    const int r = tid >> 4, q = tid & 15, row = row0 + r;
-    const bool real = row < Rr;
-    const Seed sd = real ? grad_seed(loss_step(p, D), p.lr[row], p.out[(size_t)row * O], p.y[row], p.valid[row] != 0) : Seed{};
-    if (q == 0) {
-      tw[r] = sd.raw * sd.wrow;
-      tw[TR + r] = sd.raw;
-      if (p.conf_out && row < p.R) p.conf_out[row] = sd.conf;
-      gos[r * O] = sd.g0;
-      if (row < p.R) p.g_out[(size_t)row * O] = sd.g0;
-    }
-    for (int d = q; d < D; d += 16) {
-      const float gv = real ? seed_elem(sd, p.out[(size_t)row * O + 1 + d], p.x[(size_t)row * p.ld_row + d]) : 0.f;
-      gos[r * O + 1 + d] = gv;
-      if (row < p.R) p.g_out[(size_t)row * O + 1 + d] = gv;
-    }
+    seed_tile<256 / TR>(p, D, row0, Rr, gos, tw);   // 16 lanes per row
   }
   __syncthreads();
   if (!p.seed_given && tid < 64) loss_sums_partial<TR>(p, tw);

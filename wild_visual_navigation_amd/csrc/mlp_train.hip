@@ -14,16 +14,17 @@
 // A workgroup owns 32 consecutive rows through all layers; weights stream from L2 (478 KB for D = 384), activations of the
 // tile live in LDS.
 // Shared with the DoubleMLP step (double_mlp.hip): the argument block (wvn_internal.h: TrainArgs), the statistic's publish / fold
-// and the loss-sum partial (mlp_train_device.h), the gradient seed (mlp_device.h), and the weight-gradient kernel, which lives here
-// and takes its matrices from a table (wvn_train_wgrad_launch).  The layer arithmetic below is SimpleMLP's own.
+// the gradient-seed block and the loss-sum partial (mlp_train_device.h), and the weight-gradient kernel, which lives here and takes
+// its matrices from a table (wvn_train_wgrad_launch).  The forward's x-tile load and its three layers are the text the per-segment
+// table kernel (segment_predict.hip) runs too: mlp_tile_device.h.  Tile height, ReLU form, what is stored and the loss reduction
+// are this kernel's.
 #include "common.h"
 #include "mlp_train_device.h"
 
 namespace {
 
-constexpr int TR = 32;     // rows per workgroup
-constexpr int H1 = 256, H2 = 32;
-constexpr int H1P = H1 + 4;  // LDS pitch of the h1 tile (bank spread for the 8 rows a wave reads at once)
+using namespace simple_mlp;   // H1, H2, H1P
+constexpr int TR = 32;        // rows per workgroup
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // fwd
@@ -37,87 +38,30 @@ __global__ __launch_bounds__(256) void mlp_train_fwd_kernel(MlpTrainArgs p) {
   float* outs = h2s + TR * H2;          // [TR][O]
   const int tid = threadIdx.x, row0 = blockIdx.x * TR;
   const int Rr = real_rows(p);
-  // ---- x tile (rows past R / past the device-side count: zeros) ----
-  for (int i = tid; i < TR * D; i += 256) {
-    const int r = i / D, k = i - r * D;
-    xs[r * DP + k] = (row0 + r < Rr) ? p.x[(size_t)(row0 + r) * p.ld_row + k] : 0.f;
-  }
+  // ---- x tile (rows past R / past the device-side count: zeros); a flat [R][D] matrix ----
+  load_x_tile<TR, false>(xs, p.x, p.ld_row, 0, p.R, D, row0, Rr);
   __syncthreads();
-  // ---- layer 1: h1 = relu(x W1^T + b1).  thread -> columns n0, n0 + 1, rows 16 rh .. + 15 (a wave shares rh: x reads broadcast) ----
-  {
-    const int n0 = (tid & 127) * 2, rh = tid >> 7;
-    const float* w0 = p.P + p.o.W1 + (size_t)n0 * D;
-    const float* w1 = w0 + D;
-    float a0[16], a1[16];
-    const float b0 = p.P[p.o.b1 + n0], b1 = p.P[p.o.b1 + n0 + 1];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { a0[r] = b0; a1[r] = b1; }
-    const float* xr = xs + (16 * rh) * DP;
-    for (int k = 0; k + 1 < D; k += 2) {
-      const float wa0 = w0[k], wa1 = w0[k + 1], wb0 = w1[k], wb1 = w1[k + 1];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float x0 = xr[r * DP + k], x1 = xr[r * DP + k + 1];
-        a0[r] = fmaf(x1, wa1, fmaf(x0, wa0, a0[r]));
-        a1[r] = fmaf(x1, wb1, fmaf(x0, wb0, a1[r]));
-      }
-    }
-    if (D & 1) {
-      const int k = D - 1;
-      const float wa0 = w0[k], wb0 = w1[k];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { a0[r] = fmaf(xr[r * DP + k], wa0, a0[r]); a1[r] = fmaf(xr[r * DP + k], wb0, a1[r]); }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float v0 = fmaxf(a0[r], 0.f), v1 = fmaxf(a1[r], 0.f);
-      h1s[(16 * rh + r) * H1P + n0] = v0;
-      h1s[(16 * rh + r) * H1P + n0 + 1] = v1;
-      if (row0 + 16 * rh + r < p.R) *(float2*)(p.h1 + (size_t)(row0 + 16 * rh + r) * H1 + n0) = float2{v0, v1};
-    }
-  }
+  // ---- layers 1 and 2, 16 and 4 rows per thread; the activations also go to HBM for the backward pass.
+  //      relu_fmax: a NaN activation becomes 0 here (the table kernels keep it with relu_nan) ----
+  float* const h1g = p.h1, * const h2g = p.h2, * const outg = p.out;
+  const int R = p.R;
+  smlp_layer1<TR / 2, relu_fmax>(p.P, p.o.W1, p.o.b1, D, xs, [=](int r, int n0, float v0, float v1) {
+    h1s[r * H1P + n0] = v0;
+    h1s[r * H1P + n0 + 1] = v1;
+    if (row0 + r < R) *(float2*)(h1g + (size_t)(row0 + r) * H1 + n0) = float2{v0, v1};
+  });
   __syncthreads();
-  // ---- layer 2: h2 = relu(h1 W2^T + b2).  thread -> column j, rows 4 rg .. + 3 ----
-  {
-    const int j = tid & 31, rg = tid >> 5;
-    const float* w = p.P + p.o.W2 + (size_t)j * H1;
-    float a[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) a[r] = p.P[p.o.b2 + j];
-    for (int k = 0; k < H1; k += 4) {
-      const f32x4_t w4 = *(const f32x4_t*)(w + k);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const f32x4_t h4 = *(const f32x4_t*)(h1s + (4 * rg + r) * H1P + k);
-        a[r] = fmaf(h4[3], w4[3], fmaf(h4[2], w4[2], fmaf(h4[1], w4[1], fmaf(h4[0], w4[0], a[r]))));
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float v = fmaxf(a[r], 0.f);
-      h2s[(4 * rg + r) * H2 + j] = v;
-      if (row0 + 4 * rg + r < p.R) p.h2[(size_t)(row0 + 4 * rg + r) * H2 + j] = v;
-    }
-  }
+  smlp_layer2<TR / 8, relu_fmax>(p.P, p.o.W2, p.o.b2, h1s, [=](int r, int j, float v) {
+    h2s[r * H2 + j] = v;
+    if (row0 + r < R) h2g[(size_t)(row0 + r) * H2 + j] = v;
+  });
   __syncthreads();
-  // ---- layer 3: out = h2 W3^T + b3, sigmoid on column 0.  thread -> columns n = tid, tid + 256 ----
-  for (int n = tid; n < O; n += 256) {
-    float w[H2];
-#pragma unroll
-    for (int j = 0; j < H2; j += 4) {
-      const f32x4_t w4 = *(const f32x4_t*)(p.P + p.o.W3 + (size_t)n * H2 + j);
-      w[j] = w4[0]; w[j + 1] = w4[1]; w[j + 2] = w4[2]; w[j + 3] = w4[3];
-    }
-    const float b = p.P[p.o.b3 + n];
-    for (int r = 0; r < TR; ++r) {
-      float a = b;
-#pragma unroll
-      for (int j = 0; j < H2; ++j) a = fmaf(h2s[r * H2 + j], w[j], a);
-      if (n == 0) a = sigmoid_f(a);
-      outs[r * O + n] = a;
-      if (row0 + r < p.R) p.out[(size_t)(row0 + r) * O + n] = a;
-    }
-  }
+  // ---- layer 3, sigmoid on column 0 ----
+  smlp_layer3<TR, false>(p.P, p.o.W3, p.o.b3, D, h2s, [=](int r, int n, float a) {
+    if (n == 0) a = sigmoid_f(a);
+    outs[r * O + n] = a;
+    if (row0 + r < R) outg[(size_t)(row0 + r) * O + n] = a;
+  });
   __syncthreads();
   // ---- per-row reconstruction loss: 8 threads per row, fixed order ----
   {
@@ -147,24 +91,7 @@ __global__ __launch_bounds__(256) void mlp_train_bwd_kernel(MlpTrainArgs p) {
   float* tw = gh2s + TR * H2;          // [TR] trav_w, [TR] trav_raw
   const int tid = threadIdx.x, row0 = blockIdx.x * TR;
   const int Rr = real_rows(p);
-  // ---- gradient seed (mlp_device.h): 8 threads per row ----
-  {
-    const int r = tid >> 3, q = tid & 7, row = row0 + r;
-    const bool real = row < Rr;
-    const Seed sd = real ? grad_seed(loss_step(p, D), p.lr[row], p.out[(size_t)row * O], p.y[row], p.valid[row] != 0) : Seed{};
-    if (q == 0) {
-      tw[r] = sd.raw * sd.wrow;
-      tw[TR + r] = sd.raw;
-      if (p.conf_out && row < p.R) p.conf_out[row] = sd.conf;
-      gos[r * O] = sd.g0;
-      if (row < p.R) p.g_out[(size_t)row * O] = sd.g0;
-    }
-    for (int d = q; d < D; d += 8) {
-      const float g = real ? seed_elem(sd, p.out[(size_t)row * O + 1 + d], p.x[(size_t)row * p.ld_row + d]) : 0.f;
-      gos[r * O + 1 + d] = g;
-      if (row < p.R) p.g_out[(size_t)row * O + 1 + d] = g;
-    }
-  }
+  seed_tile<256 / TR>(p, D, row0, Rr, gos, tw);   // 8 lanes per row
   __syncthreads();
   if (tid < 64) loss_sums_partial<TR>(p, tw);
   // ---- g_h2 = (g_out W3) masked by h2 > 0.  thread -> row r, columns j0 .. j0 + 3; W3 [O][32] ----

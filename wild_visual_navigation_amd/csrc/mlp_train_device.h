@@ -1,13 +1,13 @@
 // Device code the two four-launch training steps share (mlp_train.hip: SimpleMLP, row tiles of 32; double_mlp.hip: DoubleMLP,
-// row tiles of 16): the row count, the x-tile pitch, the fixed-order tile sums, the statistic a forward launch publishes and its
-// last tile folds -- the one piece of inter-workgroup synchronisation in the training path -- and the loss-sum partial of a
-// backward launch.  The layer arithmetic of the two models is theirs.
+// row tiles of 16): the row count, the fixed-order tile sums, the statistic a forward launch publishes and its last tile folds --
+// the one piece of inter-workgroup synchronisation in the training path --, the gradient-seed block of a backward tile and the
+// loss-sum partial of a backward launch.  The pieces of a tile forward (x-tile load and pitch, the SimpleMLP layers, which the
+// per-segment table kernel runs too) are in mlp_tile_device.h; DoubleMLP's pair layers are its own.
 #pragma once
-#include "mlp_device.h"
+#include "mlp_tile_device.h"
 #include "wvn_internal.h"
 
 __device__ inline int real_rows(const TrainArgs& p) { return p.rows_dev ? min(p.R, *p.rows_dev) : p.R; }
-__host__ __device__ inline int x_pitch(int D) { return (D + 3) / 4 * 4 + 4; }   // LDS pitch of the x tile: 16-byte rows
 __device__ inline LossStep loss_step(const TrainArgs& p, int D) {
   return LossStep{p.stats, p.cstate, p.minmax, p.method, p.balanced, p.std_factor, p.w_trav, p.w_reco, D};
 }
@@ -63,6 +63,28 @@ template <int TR> __device__ inline void stat_publish_fold(const TrainArgs& p, c
     p.minmax[0] = hi; p.minmax[1] = -lo;
   }
   __hip_atomic_store(p.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next step
+}
+
+// Start of a backward launch: the gradient seed of the tile (mlp_device.h: grad_seed), LPR lanes per row, 256 / LPR rows.  Fills
+// gos [TR][1 + D] and tw ([TR] trav_w, [TR] trav_raw) in LDS, g_out and, if asked for, conf_out for the rows below p.R.
+template <int LPR> __device__ __forceinline__ void seed_tile(const TrainArgs& p, int D, int row0, int Rr, float* gos, float* tw) {
+  constexpr int TR = 256 / LPR;
+  const int O = D + 1, tid = threadIdx.x;
+  const int r = tid / LPR, q = tid % LPR, row = row0 + r;
+  const bool real = row < Rr;
+  const Seed sd = real ? grad_seed(loss_step(p, D), p.lr[row], p.out[(size_t)row * O], p.y[row], p.valid[row] != 0) : Seed{};
+  if (q == 0) {
+    tw[r] = sd.raw * sd.wrow;
+    tw[TR + r] = sd.raw;
+    if (p.conf_out && row < p.R) p.conf_out[row] = sd.conf;
+    gos[r * O] = sd.g0;
+    if (row < p.R) p.g_out[(size_t)row * O] = sd.g0;
+  }
+  for (int d = q; d < D; d += LPR) {
+    const float g = real ? seed_elem(sd, p.out[(size_t)row * O + 1 + d], p.x[(size_t)row * p.ld_row + d]) : 0.f;
+    gos[r * O + 1 + d] = g;
+    if (row < p.R) p.g_out[(size_t)row * O + 1 + d] = g;
+  }
 }
 
 // Backward launch, first wave (tid < 64) behind a barrier; tw: [TR] trav_w, [TR] trav_raw of the tile in LDS.  The tile's partial

@@ -7,7 +7,9 @@
 //
 // Every pixel row is a copy of one of S segment rows, so the MLP runs once per segment and the results are painted:
 //   seg_table_kernel : one row per segment -> a [B*S][4] table {trav, conf, loss, 0} in the workspace (nothing else reaches HBM).
-//                      TR rows per workgroup staged in LDS, weights streamed from L2 (the form of mlp_train_fwd_kernel).  Every
+//                      TR rows per workgroup staged in LDS, weights streamed from L2.  The x-tile load, the three layers, the
+//                      row sum and the table write are the text mlp_train_fwd_kernel and dmlp_fwd_kernel run too
+//                      (mlp_tile_device.h); the tile height, the ReLU form and the loss reduction are this kernel's.  Every
 //                      dot product of a row is ONE fixed-order fp32 FMA chain and every reduction a fixed tree, the same for every
 //                      row wherever it sits: a row's results depend on its features and the parameters only, never on B, S, the
 //                      row's position or its workgroup neighbours (tests/test_gpu_segment_predict.py pins this bit for bit).
@@ -16,25 +18,20 @@
 // Id rule (torch indexing of feat[seg]): ids in [0, S) select their row, ids in [-S, 0) select row S + id (extract() with
 // segmentation_type="random" leaves -1 ids that the reference's gather wraps to the last row), any other id gives NaN outputs.
 #include "common.h"
-#include "mlp_device.h"
+#include "mlp_tile_device.h"
 #include "wvn_internal.h"
 
 namespace {
 
+using namespace simple_mlp;       // H1, H2, H1P
 constexpr int TR = 16;            // rows per table workgroup
-constexpr int H1 = 256, H2 = 32;
-constexpr int H1P = H1 + 4;       // LDS pitch of the h1 tile
 constexpr int DMAX = 1024;
 constexpr int TCOLS = 4;          // table row: trav, conf, loss, (pad) -- one 16-byte read per pixel
 constexpr int PAINT_THREADS = 256;
 constexpr int PAINT_QUADS = 4;    // quads (4 pixels) per thread and workgroup pass: 4096 pixels per workgroup
 constexpr int PAINT_LDS_ROWS = 2048;   // tables up to 32 KB are staged in LDS
 
-__host__ __device__ inline int x_pitch(int D) { return (D + 3) / 4 * 4 + 4; }
 size_t table_lds_bytes(int D) { return ((size_t)TR * x_pitch(D) + (size_t)TR * H1P + (size_t)TR * H2 + TR) * sizeof(float); }
-
-// torch.relu: NaN stays NaN (fmaxf would turn a NaN row into a finite prediction)
-__device__ inline float relu_nan(float v) { return v < 0.f ? 0.f : v; }
 
 struct TableParams {
   const float* P;                 // flat parameters: W1 [256][D], b1, W2 [32][256], b2, W3 [1+D][32], b3
@@ -55,110 +52,40 @@ __global__ __launch_bounds__(256) void seg_table_kernel(TableParams p) {
   const int tid = threadIdx.x, row0 = blockIdx.x * TR;
   const size_t oW1 = 0, ob1 = (size_t)H1 * D, oW2 = ob1 + H1, ob2 = oW2 + (size_t)H2 * H1, oW3 = ob2 + H2, ob3 = oW3 + (size_t)(D + 1) * H2;
   // ---- x tile (rows past R: zeros, never written out) ----
-  for (int i = tid; i < TR * D; i += 256) {
-    const int r = i / D, k = i - r * D, g = row0 + r;
-    float v = 0.f;
-    if (g < R) {
-      const int b = g / p.S, s = g - b * p.S;
-      v = p.feat[b * p.ld_frame + (long long)s * p.ld_row + k];
-    }
-    xs[r * DP + k] = v;
-  }
+  load_x_tile<TR, true>(xs, p.feat, p.ld_row, p.ld_frame, p.S, D, row0, R);
   __syncthreads();
-  // ---- layer 1: h1 = relu(W1 x + b1).  thread -> columns n0, n0 + 1, rows 8 rh .. + 7 (a wave shares rh: x reads broadcast) ----
-  {
-    const int n0 = (tid & 127) * 2, rh = tid >> 7;
-    const float* w0 = p.P + oW1 + (size_t)n0 * D;
-    const float* w1 = w0 + D;
-    float a0[8], a1[8];
-    const float b0 = p.P[ob1 + n0], b1 = p.P[ob1 + n0 + 1];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) { a0[r] = b0; a1[r] = b1; }
-    const float* xr = xs + (8 * rh) * DP;
-    for (int k = 0; k + 1 < D; k += 2) {
-      const float wa0 = w0[k], wa1 = w0[k + 1], wb0 = w1[k], wb1 = w1[k + 1];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        const float x0 = xr[r * DP + k], x1 = xr[r * DP + k + 1];
-        a0[r] = fmaf(x1, wa1, fmaf(x0, wa0, a0[r]));
-        a1[r] = fmaf(x1, wb1, fmaf(x0, wb0, a1[r]));
-      }
-    }
-    if (D & 1) {
-      const int k = D - 1;
-      const float wa0 = w0[k], wb0 = w1[k];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) { a0[r] = fmaf(xr[r * DP + k], wa0, a0[r]); a1[r] = fmaf(xr[r * DP + k], wb0, a1[r]); }
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      h1s[(8 * rh + r) * H1P + n0] = relu_nan(a0[r]);
-      h1s[(8 * rh + r) * H1P + n0 + 1] = relu_nan(a1[r]);
-    }
-  }
+  // ---- layers 1 and 2, 8 and 2 rows per thread.  relu_nan: a NaN feature row stays NaN (the training forward clamps with fmaxf) ----
+  smlp_layer1<TR / 2, relu_nan>(p.P, oW1, ob1, D, xs, [=](int r, int n0, float v0, float v1) {
+    h1s[r * H1P + n0] = v0;
+    h1s[r * H1P + n0 + 1] = v1;
+  });
   __syncthreads();
-  // ---- layer 2: h2 = relu(W2 h1 + b2).  thread -> column j, rows 2 rg, 2 rg + 1 ----
-  {
-    const int j = tid & 31, rg = tid >> 5;
-    const float* w = p.P + oW2 + (size_t)j * H1;
-    float a[2];
-    a[0] = a[1] = p.P[ob2 + j];
-    for (int k = 0; k < H1; k += 4) {
-      const f32x4_t w4 = *(const f32x4_t*)(w + k);
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const f32x4_t h4 = *(const f32x4_t*)(h1s + (2 * rg + r) * H1P + k);
-        a[r] = fmaf(h4[3], w4[3], fmaf(h4[2], w4[2], fmaf(h4[1], w4[1], fmaf(h4[0], w4[0], a[r]))));
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) h2s[(2 * rg + r) * H2 + j] = relu_nan(a[r]);
-  }
+  smlp_layer2<TR / 8, relu_nan>(p.P, oW2, ob2, h1s, [=](int r, int j, float v) { h2s[r * H2 + j] = v; });
   __syncthreads();
-  // ---- layer 3 + reconstruction error: out = W3 h2 + b3.  thread -> columns n = tid, tid + 256, ... (ascending) ----
+  // ---- layer 3 + reconstruction error: column 0 is the traversability, the others fold into per-thread partials ----
   float* part = h1s;                   // [TR][256] per-thread squared-error partials (h1 is dead)
   {
     float s[TR];
 #pragma unroll
     for (int r = 0; r < TR; ++r) s[r] = 0.f;
-    for (int n = tid; n <= D; n += 256) {
-      float w[H2];
-#pragma unroll
-      for (int j = 0; j < H2; j += 4) {
-        const f32x4_t w4 = *(const f32x4_t*)(p.P + oW3 + (size_t)n * H2 + j);
-        w[j] = w4[0]; w[j + 1] = w4[1]; w[j + 2] = w4[2]; w[j + 3] = w4[3];
+    smlp_layer3<TR, true>(p.P, oW3, ob3, D, h2s, [&](int r, int n, float a) {
+      if (n == 0) {
+        trav_s[r] = sigmoid_f(a);
+      } else {
+        const float e = a - xs[r * DP + n - 1];
+        s[r] = fmaf(e, e, s[r]);
       }
-      const float b = p.P[ob3 + n];
-#pragma unroll
-      for (int r = 0; r < TR; ++r) {
-        float a = b;
-#pragma unroll
-        for (int j = 0; j < H2; ++j) a = fmaf(h2s[r * H2 + j], w[j], a);
-        if (n == 0) {
-          trav_s[r] = sigmoid_f(a);
-        } else {
-          const float e = a - xs[r * DP + n - 1];
-          s[r] = fmaf(e, e, s[r]);
-        }
-      }
-    }
+    });
 #pragma unroll
     for (int r = 0; r < TR; ++r) part[r * 256 + tid] = s[r];
   }
   __syncthreads();
-  // ---- per-row sum of the 256 partials: 16 lanes per row, lane q adds partials q, q + 16, ... in order, then a butterfly ----
   {
     const int r = tid >> 4, q = tid & 15;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += part[r * 256 + q + 16 * i];
-    s += __shfl_xor(s, 8, 64); s += __shfl_xor(s, 4, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 1, 64);
-    if (q == 0 && row0 + r < R) {
-      const float loss = s / (float)D;
-      const float cm = p.conf_dev ? p.conf_dev[0] : p.mean, cs = p.conf_dev ? p.conf_dev[1] : p.std;
-      const float cf = p.conf_dev ? p.conf_dev[2] : p.std_factor;
-      *(f32x4_t*)(p.table + (size_t)(row0 + r) * TCOLS) = f32x4_t{trav_s[r], confidence_of(loss, cm, cs, cf), loss, 0.f};
-    }
+    const float s = row_sum_256(part);
+    // confidence_of: a NaN loss gets a finite confidence here (dmlp_fwd_kernel writes confidence_of_nan)
+    if (q == 0 && row0 + r < R)
+      table_row_write<confidence_of>(p.table + (size_t)(row0 + r) * TCOLS, trav_s[r], s / (float)D, p.conf_dev, p.mean, p.std, p.std_factor);
   }
 }
 
