@@ -42,7 +42,7 @@ extern "C" {
                            error) on the fp16-operand kernel of WVN_PREC_F16, fed fp16 q / k / v^T by the QKV epilogue and writing  \
                            its output as hi + lo planes from its fp32 accumulators.  Weights as for WVN_PREC_X3 */
 
-int wvn_version(void);
+int wvn_version(void); /* 101 (100 -> 101: wvn_flip_average gained ld_src; wvn_vit_forward_frames_head, wvn_stego_head added) */
 
 /* ---------------------------------------------------------------------------------------------
  * DINO ViT backbone  (replaces stego.backbones.backbone.get_backbone(cfg)(img), called from
@@ -180,6 +180,32 @@ int wvn_vit_forward_frames(const wvn_vit_model* m, const void* frames, int frame
 int wvn_vit_forward_frames_pair(const wvn_vit_model* m, const void* frames, int frames_u8, int src_h, int src_w, const int* rows,
                                 const int* cols, const int* cols_mirror, int batch, float* tokens_f32, void* tokens_lowp, int ld_lowp,
                                 void* workspace, size_t workspace_bytes, void* stream);
+/* The STEGO segmentation head (code = tok W_lin^T + b_lin + ReLU(tok W_hid^T + b_hid) W_nl^T + b_nl) as wvn_vit_forward_frames_head
+ * takes it.  It travels in a struct of its own: wvn_vit_model keeps its size.  All pointers are device pointers, 16-byte aligned.
+ *   w_cat  hi / lo bf16 planes [2][512][384]: rows 0 .. 383 W_hid, rows 384 .. 384 + code_dim - 1 W_lin, the rest zero
+ *   b_cat  [512] fp32: b_hid, b_lin, zeros
+ *   w_nl   hi / lo bf16 planes [2][code_dim][384];  b_nl [code_dim] fp32
+ *   code   OUT fp32 [rows][ld_code], rows = frames * G * G patch rows; ld_code % 4 == 0, >= 128: columns 0 .. code_dim - 1 hold the
+ *          code, columns up to 127 zeros (the padded stride keeps every row 16-byte aligned; narrow with wvn_flip_average) */
+typedef struct wvn_stego_head {
+  const void* w_cat;
+  const float* b_cat;
+  const void* w_nl;
+  const float* b_nl;
+  float* code;
+  int code_dim; /* <= 128 */
+  int ld_code;
+} wvn_stego_head;
+/* wvn_vit_forward_frames (cols_mirror == NULL: `batch` frames) or wvn_vit_forward_frames_pair (2 * batch frames, the mirrors behind the
+ * frames) with the STEGO head run off the residual rows: a statistics pass leaves {mean, rstd} of the final LayerNorm, ONE
+ * A-stationary launch forms LayerNorm(x) as it loads the rows and writes the hidden planes (into the workspace) and the linear
+ * branch's code rows, a third product adds the non-linear branch.  No token tensor is written; the code is bit-identical to
+ * wvn_vit_forward_frames(_pair) + wvn_split_planes + three wvn_gemm_x3.  WVN_PREC_X3 / WVN_PREC_MIX, D = 384,
+ * from 8192 token rows on (the route of the split-operand block kernels); everywhere else it
+ * returns WVN_ERR_ARG BEFORE launching anything and the caller runs wvn_vit_forward_frames(_pair) and the head's three products. */
+int wvn_vit_forward_frames_head(const wvn_vit_model* m, const void* frames, int frames_u8, int src_h, int src_w, const int* rows,
+                                const int* cols, const int* cols_mirror, int batch, const wvn_stego_head* head, void* workspace,
+                                size_t workspace_bytes, void* stream);
 /* The same gather as an image op (ImageProjector.resize_image, image_projector.py:199-200, whose result the callers also
  * display): out [planes, out_h, out_w] = in [planes, src_h, src_w][.., rows[y], cols[x]]; elem_bytes 1 (uint8) or 4 (fp32, int32). */
 int wvn_resize_nearest_crop(const void* in, void* out, long long planes, int src_h, int src_w, const int* rows, const int* cols,
@@ -497,8 +523,10 @@ int wvn_table_bilerp_argmax(const float* table, int* labels, int B, int G, int H
 int wvn_table_bilerp_argmax_ac(const float* table, int* labels, int B, int G, int H, int K, int align_corners, void* stream);
 /* out = 0.5 * (a + flip_x(mirrored)) on [B, G, G, C] fp32 patch maps: the code of a frame averaged with the flipped-back code of
  * its mirror image (the second pass of the upstream Stego.get_code; the mirror pass itself is wvn_vit_forward_frames with a
- * reversed column table).  out may alias a. */
-int wvn_flip_average(const float* a, const float* mirrored, float* out, int B, int G, int C, void* stream);
+ * reversed column table).  ld_src: row stride (floats, >= C) of a and mirrored -- C for contiguous maps, 128 for the padded code
+ * rows of wvn_vit_forward_frames_head; out is [B, G, G, C] contiguous and may alias a where ld_src == C.  mirrored == NULL: out = a
+ * (the padded rows narrowed: the single-pass form). */
+int wvn_flip_average(const float* a, const float* mirrored, float* out, int B, int G, int C, int ld_src, void* stream);
 int wvn_kmeans_cosine(const float* xn, int* labels, int* nseg, void* scratch, int B, int P, int C, int K, int iters,
                       int relabel, void* stream);
 
@@ -796,6 +824,11 @@ int wvn_debug_mlp_mx(const float* x, int ldx, const float* ln_stats, const float
  * the layouts of wvn_attention_f16 (Wp = backbone.pack_a384_mx(qkv.weight)). */
 int wvn_debug_qkv_mx(const float* x, int ldx, const float* ln_stats, const float* ln_g, const float* ln_b, const void* Wp, const float* bias, void* q,
                      void* q_lo, void* k, void* vt, int heads, int npad, int ntok_s, float q_scale, int M, long long* dbg, void* stream);
+/* The first launch of wvn_vit_forward_frames_head's head alone (gemm_a384_x3.hip, X_HEAD): x [frames * ntok_s][ldx] fp32 residual rows (patch p of
+ * frame f is row f * ntok_s + 1 + p; the other rows are never read), stats[row] = {mean, rstd}; w_cat / b_cat as in wvn_stego_head; hid / hid_lo: the hi / lo
+ * bf16 planes [frames * npatch][384] of ReLU(LayerNorm(x) W_hid^T + b_hid); code [frames * npatch][ld_code] fp32: columns 0 .. 127 = LayerNorm(x) W_lin^T + b_lin. */
+int wvn_debug_stego_head_fused(const float* x, int ldx, const float* stats, const float* ln_g, const float* ln_b, const void* w_cat, const float* b_cat,
+                               void* hid, void* hid_lo, float* code, int ld_code, int frames, int npatch, int ntok_s, void* stream);
 /* subsequent wvn_attention_bf16 launches write dbg[(workgroup * 4 + wave) * 5 + {0 wait, 1 QK^T, 2 softmax, 3 PV,
  * 4 total}]; NULL switches the instrumented build off again. */
 /* (test hook) out_f16[i] = fp16(in[i]) as the kernels convert: finite values beyond the fp16 range saturate to +-65504 (MODE.FP16_OVFL) */

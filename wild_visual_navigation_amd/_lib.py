@@ -46,6 +46,9 @@ class WvnError(RuntimeError):
     pass
 
 
+ERR_ARG = 1001   # WVN_ERR_ARG: bad argument, or "this route is not eligible" -- returned before anything is launched
+
+
 # ConfidenceGenerator methods of the training step (include/wvn_hip.h: WVN_CONF_*, wvn_conf_desc)
 CONF_METHODS = {"latest_measurement": 0, "running_mean": 1, "kalman_filter": 2, "moving_average": 3}
 CONF_WINDOW = 5
@@ -73,6 +76,12 @@ class VitModel(C.Structure):
     ]
 
 
+class StegoHead(C.Structure):
+    """include/wvn_hip.h: wvn_stego_head (the head of wvn_vit_forward_frames_head)."""
+    _fields_ = [("w_cat", C.c_void_p), ("b_cat", C.c_void_p), ("w_nl", C.c_void_p), ("b_nl", C.c_void_p), ("code", C.c_void_p),
+                ("code_dim", C.c_int), ("ld_code", C.c_int)]
+
+
 class MlpDesc(C.Structure):
     _fields_ = [("D", C.c_int), ("H1", C.c_int), ("H2", C.c_int), ("reserved", C.c_int)]
 
@@ -95,6 +104,8 @@ _SIGNATURES = {
     "wvn_vit_forward_u8": ([_p, _p, _i, _p, _p, _i, _p, _sz, _p], _i),
     "wvn_vit_forward_frames": ([_p, _p, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _sz, _p], _i),
     "wvn_vit_forward_frames_pair": ([_p, _p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _i, _p, _sz, _p], _i),
+    "wvn_vit_forward_frames_head": ([_p, _p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _sz, _p], _i),
+    "wvn_debug_stego_head_fused": ([_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "wvn_resize_nearest_crop": ([_p, _p, _ll, _i, _i, _p, _p, _i, _i, _i, _p], _i),
     "wvn_prof_enable": ([_i], _i),
     "wvn_prof_collect": ([_p, _p], _i),
@@ -166,7 +177,7 @@ _SIGNATURES = {
     "wvn_kmeans_scratch_bytes": ([_i, _i, _i, _i], _sz),
     "wvn_kmeans_pixels_scratch_bytes": ([_i, _i, _i, _i, _i], _sz),
     "wvn_kmeans_cosine_pixels": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
-    "wvn_flip_average": ([_p, _p, _p, _i, _i, _i, _p], _i),
+    "wvn_flip_average": ([_p, _p, _p, _i, _i, _i, _i, _p], _i),
     "wvn_kmeans_pixels_linear_supported_shape": ([_i, _i, _i, _i], _i),
     "wvn_kmeans_pixels_linear_scratch_bytes": ([_i, _i, _i, _i, _i], _sz),
     "wvn_kmeans_cosine_pixels_linear": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),

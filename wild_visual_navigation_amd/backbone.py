@@ -235,6 +235,37 @@ def _debug_bits() -> int:
     return v
 
 
+class StegoHead:
+    """The STEGO segmentation head as ``VitBackbone.forward_tokens(_pair)(head=...)`` takes it (precisions "exact" / "mixed", D = 384):
+    code = tok W_lin^T + b_lin + ReLU(tok W_hid^T + b_hid) W_nl^T + b_nl, every product hi*hi + hi*lo + lo*hi on bf16 planes.  Packed once at
+    model load from the fp32 weights on the device: ``w_cat`` / ``b_cat`` are the weight and bias of the launch that reads the residual rows
+    (ops.pack_stego_head), the plane stacks [2, N, 384] serve the third product and the separate products where the library declines the
+    fused route."""
+    LD = 128   # row stride (floats) of the code rows: ops.STEGO_HEAD_LD
+
+    def __init__(self, w_hid: torch.Tensor, b_hid: torch.Tensor, w_lin: torch.Tensor, b_lin: torch.Tensor, w_nl: torch.Tensor, b_nl: torch.Tensor):
+        from . import ops
+
+        self.w_hid, self.w_lin, self.w_nl = split_planes(w_hid.float()), split_planes(w_lin.float()), split_planes(w_nl.float())   # bf16 planes [2, N, 384]
+        self.b_hid, self.b_lin, self.b_nl = b_hid.float().contiguous(), b_lin.float().contiguous(), b_nl.float().contiguous()
+        self.code_dim = w_lin.shape[0]
+        self.w_cat, self.b_cat = ops.pack_stego_head(w_hid, self.b_hid, w_lin, self.b_lin)
+
+    def desc(self, code: torch.Tensor) -> "_lib.StegoHead":
+        """The C descriptor with ``code`` ([rows, LD] fp32, contiguous) as the output."""
+        return _lib.StegoHead(self.w_cat.data_ptr(), self.b_cat.data_ptr(), self.w_nl.data_ptr(), self.b_nl.data_ptr(), code.data_ptr(), self.code_dim, self.LD)
+
+    def apply(self, tok: torch.Tensor, code: torch.Tensor) -> None:
+        """The head as three separate products on final-LayerNorm tokens [R, 384] fp32 -> code [R, LD] (the padded rows of the fused route)."""
+        from . import ops
+
+        planes = ops.split_planes(tok)
+        hid = ops.gemm_x3(planes, self.w_hid, self.b_hid, _lib.EPI_RELU_BF16)
+        dst = code[:, :self.code_dim]
+        ops.gemm_x3(planes, self.w_lin, self.b_lin, _lib.EPI_F32, out=dst)
+        ops.gemm_x3(hid, self.w_nl, self.b_nl, _lib.EPI_RESID_F32, out=dst)
+
+
 class VitBackbone:
     """Device-resident DINO / DINOv2 ViT.  ``precision``: "bf16" (MFMA fast path), "fp16" (the same kernels with fp16 operands:
     same speed, 8x less operand rounding -- csrc/operand.h), "mixed" (the <= 1e-3 parity mode sized by the error budget: the linears as
@@ -427,8 +458,14 @@ class VitBackbone:
         return {_lib.PREC_BF16: torch.bfloat16, _lib.PREC_FP8: torch.bfloat16, _lib.PREC_F16: torch.float16,
                 _lib.PREC_F32: torch.float32}.get(self.precision)
 
+    def _head_check(self, head, out, lowp_out):
+        if self.precision not in (_lib.PREC_X3, _lib.PREC_MIX) or self.dim != 384:
+            raise _lib.WvnError("head= needs precision 'exact' or 'mixed' and a 384-d backbone")
+        if out is not None or lowp_out is not None:
+            raise _lib.WvnError("head= returns the code INSTEAD of the tokens: a caller that needs both runs the head on the tokens itself")
+
     def forward_tokens(self, img: torch.Tensor, out: Optional[torch.Tensor] = None,
-                       lowp_out: Optional[torch.Tensor] = None, flip: bool = False) -> torch.Tensor:
+                       lowp_out: Optional[torch.Tensor] = None, flip: bool = False, head: Optional[StegoHead] = None) -> torch.Tensor:
         """img [B,3,H,W]: fp32 in [0,1] or raw uint8 frames (x/255 is then fused into the patch gather, bit-identical to passing
         ``img.float() / 255``), at the network size or at ANY camera size -- the NEAREST resize + centre crop of
         dino_interface.py:52-59 is then fused into the same gather through index tables (``transforms.ingest_tables``;
@@ -436,18 +473,23 @@ class VitBackbone:
         column table, no copy).  -> final-LN patch tokens [B, G*G, D] fp32 (fresh tensor unless ``out`` is given).
         ``lowp_out`` (optional, [B*G*G, ld] in the model precision) receives the same values for a following MFMA GEMM
         (STEGO head).  Frames are pushed through in chunks of ``max_chunk`` so a chunk's activations stay resident in the
-        256 MB Infinity Cache."""
+        256 MB Infinity Cache.
+        ``head`` (a ``StegoHead``; "exact" / "mixed"): the STEGO code INSTEAD of the tokens, [B, G*G, StegoHead.LD] fp32 rows whose first
+        ``head.code_dim`` columns hold the code -- run off the residual rows (``wvn_vit_forward_frames_head``: no token tensor is written)
+        where the library takes that route, chunk by chunk; a chunk it declines gets its tokens and the head's three separate products."""
         _lib.require_cuda(img, "img")
         B, Cc, Hs, Ws = img.shape
         if Cc != 3:
             raise _lib.WvnError(f"expected [B,3,H,W], got {tuple(img.shape)}")
         if lowp_out is not None and self.precision in (_lib.PREC_X3, _lib.PREC_MIX):
             raise _lib.WvnError("precisions 'exact' / 'mixed' return fp32 tokens only (split them with ops.split_planes)")
+        if head is not None:
+            self._head_check(head, out, lowp_out)
         if img.dtype != torch.uint8:
             img = img.float()
         img = img.contiguous()
         u8 = img.dtype == torch.uint8
-        direct = Hs == self.img_size and Ws == self.img_size and not flip
+        direct = Hs == self.img_size and Ws == self.img_size and not flip and head is None   # (the head's entry point takes the index tables)
         tab = None
         if not direct:
             from .feature_extractor.transforms import ingest_tables
@@ -456,13 +498,29 @@ class VitBackbone:
             img = img.float() / 255   # wvn_vit_forward_u8 covers the 16-bit-operand precisions at patch 8; others take fp32 here
             u8 = False
         P = self.grid * self.grid
-        if out is None:
-            out = torch.empty(B, P, self.dim, dtype=torch.float32, device=self.device)
         chunk = min(self.max_chunk, B)
         ws = self._workspace(chunk)
         st = _lib.stream()
         esz = 2 if self._lowp16 is not None else 4
         frame_bytes = 3 * Hs * Ws * img.element_size()
+        if head is not None:
+            code = torch.empty(B, P, head.LD, dtype=torch.float32, device=self.device)
+            for b0 in range(0, B, chunk):
+                nb = min(chunk, B - b0)
+                src = img.data_ptr() + b0 * frame_bytes
+                rc = self.lib.wvn_vit_forward_frames_head(C.byref(self.model), src, int(u8), Hs, Ws, tab.rows.data_ptr(), tab.cols.data_ptr(), None, nb,
+                                                          C.byref(head.desc(code[b0:])), ws.data_ptr(), ws.numel(), st)
+                if rc == _lib.ERR_ARG:   # declined before any launch (too few rows for the A-stationary route): tokens, then the three products
+                    tok = torch.empty(nb, P, self.dim, dtype=torch.float32, device=self.device)
+                    rc = self.lib.wvn_vit_forward_frames(C.byref(self.model), src, int(u8), Hs, Ws, tab.rows.data_ptr(), tab.cols.data_ptr(), nb,
+                                                         tok.data_ptr(), 0, 0, ws.data_ptr(), ws.numel(), st)
+                    _lib.check(rc, "wvn_vit_forward_frames")
+                    head.apply(tok.reshape(nb * P, self.dim), code[b0:b0 + nb].reshape(nb * P, head.LD))
+                else:
+                    _lib.check(rc, "wvn_vit_forward_frames_head")
+            return code
+        if out is None:
+            out = torch.empty(B, P, self.dim, dtype=torch.float32, device=self.device)
         for b0 in range(0, B, chunk):
             nb = min(chunk, B - b0)
             lp, ld = 0, 0
@@ -482,17 +540,20 @@ class VitBackbone:
                            "wvn_vit_forward")
         return out
 
-    def forward_tokens_pair(self, img: torch.Tensor, lowp_out: Optional[torch.Tensor] = None):
+    def forward_tokens_pair(self, img: torch.Tensor, lowp_out: Optional[torch.Tensor] = None, head: Optional[StegoHead] = None):
         """The frames AND their horizontal mirror images through the network in one launch sequence per chunk
         (``wvn_vit_forward_frames_pair``: twice the rows per launch; bit-identical to ``forward_tokens(img)`` and
         ``forward_tokens(img, flip=True)``).  Returns (tokens [2B, G*G, D] fp32, chunk): rows are laid out chunk by chunk,
-        [chunk's frames | chunk's mirrors]; ``lowp_out`` ([2B*G*G, ld]) likewise."""
+        [chunk's frames | chunk's mirrors]; ``lowp_out`` ([2B*G*G, ld]) likewise.  ``head``: as in ``forward_tokens`` -- the first
+        return value is then the code [2B, G*G, StegoHead.LD] in the same row layout."""
         _lib.require_cuda(img, "img")
         B, Cc, Hs, Ws = img.shape
         if Cc != 3:
             raise _lib.WvnError(f"expected [B,3,H,W], got {tuple(img.shape)}")
         if lowp_out is not None and self.precision in (_lib.PREC_X3, _lib.PREC_MIX):
             raise _lib.WvnError("precisions 'exact' / 'mixed' return fp32 tokens only (split them with ops.split_planes)")
+        if head is not None:
+            self._head_check(head, None, lowp_out)
         if img.dtype != torch.uint8:
             img = img.float()
         img = img.contiguous()
@@ -500,12 +561,29 @@ class VitBackbone:
         tab = ingest_tables(Hs, Ws, self.img_size, self.device, flip=False)
         tabm = ingest_tables(Hs, Ws, self.img_size, self.device, flip=True)
         P = self.grid * self.grid
-        out = torch.empty(2 * B, P, self.dim, dtype=torch.float32, device=self.device)
         chunk = min(self.max_chunk, B)
         ws = self._workspace(2 * chunk)
         st = _lib.stream()
         esz = 2 if self._lowp16 is not None else 4
         frame_bytes = 3 * Hs * Ws * img.element_size()
+        u8 = int(img.dtype == torch.uint8)
+        if head is not None:
+            code = torch.empty(2 * B, P, head.LD, dtype=torch.float32, device=self.device)
+            for b0 in range(0, B, chunk):
+                nb = min(chunk, B - b0)
+                src = img.data_ptr() + b0 * frame_bytes
+                rc = self.lib.wvn_vit_forward_frames_head(C.byref(self.model), src, u8, Hs, Ws, tab.rows.data_ptr(), tab.cols.data_ptr(), tabm.cols.data_ptr(),
+                                                          nb, C.byref(head.desc(code[2 * b0:])), ws.data_ptr(), ws.numel(), st)
+                if rc == _lib.ERR_ARG:   # declined before any launch: tokens, then the three products
+                    tok = torch.empty(2 * nb, P, self.dim, dtype=torch.float32, device=self.device)
+                    rc = self.lib.wvn_vit_forward_frames_pair(C.byref(self.model), src, u8, Hs, Ws, tab.rows.data_ptr(), tab.cols.data_ptr(),
+                                                              tabm.cols.data_ptr(), nb, tok.data_ptr(), 0, 0, ws.data_ptr(), ws.numel(), st)
+                    _lib.check(rc, "wvn_vit_forward_frames_pair")
+                    head.apply(tok.reshape(2 * nb * P, self.dim), code[2 * b0:2 * b0 + 2 * nb].reshape(2 * nb * P, head.LD))
+                else:
+                    _lib.check(rc, "wvn_vit_forward_frames_head")
+            return code, chunk
+        out = torch.empty(2 * B, P, self.dim, dtype=torch.float32, device=self.device)
         for b0 in range(0, B, chunk):
             nb = min(chunk, B - b0)
             lp, ld = 0, 0

@@ -16,7 +16,7 @@
 
 extern "C" {
 
-int wvn_version(void) { return 100; }
+int wvn_version(void) { return 101; }   // 101: wvn_flip_average takes the source row stride; wvn_vit_forward_frames_head
 
 size_t wvn_vit_workspace_bytes(const wvn_vit_model* m, int batch) {
   if (!m || batch <= 0) return 0;
@@ -49,6 +49,21 @@ int wvn_vit_forward_frames_pair(const wvn_vit_model* m, const void* frames, int 
   const WvnIngest ing{rows, cols, src_h, src_w};
   return wvn_vit_forward_impl(m, frames, frames_u8 != 0, &ing, batch, tokens_f32, tokens_lowp, ld_lowp, workspace, workspace_bytes, stream,
                               cols_mirror);
+}
+
+int wvn_vit_forward_frames_head(const wvn_vit_model* m, const void* frames, int frames_u8, int src_h, int src_w, const int* rows,
+                                const int* cols, const int* cols_mirror, int batch, const wvn_stego_head* head, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  if (!rows || !cols || !head || src_h <= 0 || src_w <= 0) return WVN_ERR_ARG;
+  const WvnIngest ing{rows, cols, src_h, src_w};
+  return wvn_vit_forward_impl(m, frames, frames_u8 != 0, &ing, batch, nullptr, nullptr, 0, workspace, workspace_bytes, stream, cols_mirror, head);
+}
+
+int wvn_debug_stego_head_fused(const float* x, int ldx, const float* stats, const float* ln_g, const float* ln_b, const void* w_cat, const float* b_cat,
+                               void* hid, void* hid_lo, float* code, int ld_code, int frames, int npatch, int ntok_s, void* stream) {
+  if (!w_cat) return WVN_ERR_ARG;
+  return wvn_gemm_a384_head_launch(x, ldx, stats, ln_g, ln_b, (const bf16_t*)w_cat, (const bf16_t*)w_cat + (size_t)512 * 384, b_cat, (bf16_t*)hid,
+                                   (bf16_t*)hid_lo, code, ld_code, frames, npatch, ntok_s, (hipStream_t)stream);
 }
 
 int wvn_resize_nearest_crop(const void* in, void* out, long long planes, int src_h, int src_w, const int* rows, const int* cols,
@@ -427,8 +442,8 @@ int wvn_table_bilerp_argmax(const float* table, int* labels, int B, int G, int H
   return wvn_table_bilerp_argmax_launch(table, labels, B, G, H, K, (hipStream_t)stream);
 }
 int wvn_debug_kmeans_linear_rows(int rc) { wvn_kmeans_pixels_linear_set_rows(rc); return WVN_OK; }
-int wvn_flip_average(const float* a, const float* mirrored, float* out, int B, int G, int C, void* stream) {
-  return wvn_flip_average_launch(a, mirrored, out, B, G, C, (hipStream_t)stream);
+int wvn_flip_average(const float* a, const float* mirrored, float* out, int B, int G, int C, int ld_src, void* stream) {
+  return wvn_flip_average_launch(a, mirrored, out, B, G, C, ld_src, (hipStream_t)stream);
 }
 int wvn_kmeans_cosine(const float* xn, int* labels, int* nseg, void* scratch, int B, int P, int C, int K, int iters,
                       int relabel, void* stream) {

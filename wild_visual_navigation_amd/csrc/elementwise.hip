@@ -208,6 +208,40 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   }
 }
 
+// The statistics of layernorm_kernel<float, 6> alone, for the patch rows of the residual stream (row frame * ntok_s + 1 + patch): stats[row] = {mean, rstd}
+// with EXACTLY its arithmetic -- the same columns per lane, the same summation order, the same two passes -- so that a consumer that forms
+// ((x - mean) * rstd) * gamma + beta on load (gemm_a384_x3.hip, X_HEAD) holds the tokens that kernel would have written, bit for bit.
+__global__ __launch_bounds__(256) void layernorm_patch_stats_kernel(const float* __restrict__ x, float* __restrict__ stats, int rows_out, float eps, int npatch,
+                                                                    int ntok_s) {
+  constexpr int VPT = 6, D = 384;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= rows_out) return;
+  const int b = row / npatch, pp = row - b * npatch;
+  const size_t in_row = (size_t)b * ntok_s + 1 + pp;
+  const float* xr = x + in_row * D;
+  float v[VPT];
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPT; ++i) {
+    v[i] = xr[lane + 64 * i];
+    s += v[i];
+  }
+  const float mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPT; ++i) {
+    float d = v[i] - mean;
+    q += d * d;
+  }
+  const float var = wave_sum(q) / (float)D;
+  const float rstd = 1.0f / sqrtf(var + eps);
+  if (lane == 0) {
+    stats[2 * in_row] = mean;
+    stats[2 * in_row + 1] = rstd;
+  }
+}
+
 // D = 384 with bf16 output (LN1 / LN2 of every ViT-S block: 24 launches per forward, HBM-bound at 1536 B read + 768 B
 // written per row).  16 lanes per row, each lane owns 3 groups of 8 consecutive columns: every access is a 16-byte load or
 // store, a wave handles 4 rows per pass and LN_RPW rows in all (gamma / beta stay in registers).  Same two-pass fp32
@@ -494,6 +528,14 @@ int wvn_pad_zero_launch(void* base, long long nrows, long long row_stride_bytes,
 
 int wvn_cls_rows_launch(const float* cls_pos, float* x, int B, int ntok, int D, hipStream_t st) {  // ntok = rows per frame
   hipLaunchKernelGGL(cls_rows_kernel, dim3(ceil_div(B * D, 256)), dim3(256), 0, st, cls_pos, x, B, ntok, D);
+  WVN_LAUNCH_CHECK();
+  return WVN_OK;
+}
+
+int wvn_layernorm_patch_stats_launch(const float* x, float* stats, int frames, int npatch, int ntok_s, float eps, hipStream_t st) {
+  if (!x || !stats || frames <= 0 || npatch <= 0 || ntok_s <= npatch) return WVN_ERR_ARG;
+  const int rows = frames * npatch;
+  hipLaunchKernelGGL(layernorm_patch_stats_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, st, x, stats, rows, eps, npatch, ntok_s);
   WVN_LAUNCH_CHECK();
   return WVN_OK;
 }

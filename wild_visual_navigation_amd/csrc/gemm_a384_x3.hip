@@ -48,9 +48,13 @@ constexpr int BM = 128;
 constexpr int PIECES = SLICE_BYTES / 1024 / 4;  // 1 KB DMA pieces per wave and slice (8)
 static_assert(PIECES == 8, "one DMA piece per k-step of a slice");
 
-enum { X_GELU = 0, X_RESID = 1, X_QK = 2, X_V = 3, X_PLANES = 4, X_GELU_FRAG = 5, X_QK_F16 = 6, X_V_F16 = 7, X_QKV = 8, X_QKV_F16 = 9 };   // _F16: one fp16 plane per tensor
+enum { X_GELU = 0, X_RESID = 1, X_QK = 2, X_V = 3, X_PLANES = 4, X_GELU_FRAG = 5, X_QK_F16 = 6, X_V_F16 = 7, X_QKV = 8, X_QKV_F16 = 9, X_HEAD = 10 };   // _F16: one fp16 plane per tensor
 // X_QKV / X_QKV_F16: q | k | v^T in ONE launch -- the column tiles of q and k run in the TR orientation, those of v^T in the other; a row
 // block's two planes (192 registers) are loaded once instead of twice (617 MB per launch at 128 frames) and there is one prologue / tail
+// X_HEAD (LayerNorm on load only; tokens in the fp32 LayerNorm kernel's operation order, accumulators from zero and the bias behind them: bit-identical to that kernel + the tiled gemm_x3): the two products of the STEGO head that read the final-LayerNorm tokens, in ONE launch over the residual rows.  W = [W_hid (384 rows);
+// W_lin (zero-padded to 128 rows)], N = 512: column tiles 0 - 5 leave ReLU(.) as row-major hi / lo planes (the X_PLANES store), tiles 6 - 7 fp32 rows of a code buffer with a
+// padded row stride (the X_RESID image without the read of C).  The kernel's rows are PATCH rows r; only the load maps them to residual rows (r / npatch) * ntok_s + 1 + r % npatch
+// (past the CLS row and the padding rows of each frame).  The tile kind is the tag the other instantiations use for the orientation: every tile here is TR.
 
 struct X384Params {
   const bf16_t* A; const bf16_t* A_lo; int lda;
@@ -70,6 +74,8 @@ struct X384Params {
   // LNA: A = LayerNorm(ln_x) formed while the row block is loaded: ln_x fp32 [M][ln_ldx], ln_stats[m] = {mean, rstd} (left by the kernel
   // that wrote the rows: gemm_n384_x3.hip), gamma / beta [384]
   const float* ln_x; int ln_ldx; const float* ln_stats; const float* ln_g; const float* ln_b;
+  // X_HEAD: patch rows per frame (rows of ln_x per frame: ntok_s), the fp32 code rows [M][ld_code] of column tiles 6 - 7
+  int npatch; float* code; int ld_code;
 };
 
 __device__ inline void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
@@ -104,6 +110,8 @@ constexpr int X384_LDS_MAX = 160 * 1024;
 template <int EPI, bool TIMING = false, bool LNA = false, bool MX = false, bool BURST = false>
 __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
   static_assert(!MX || (LNA && (EPI == X_GELU_FRAG || EPI == X_QKV_F16)), "the MX form exists for the LayerNorm-on-load fc1 / QKV instantiations");
+  static_assert(EPI != X_HEAD || (LNA && !MX), "the STEGO head reads the residual rows: LayerNorm on load, split bf16 operands");
+  constexpr bool HEAD = EPI == X_HEAD;
   wvn_fp16_saturate();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -203,9 +211,11 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
       // their producer left, scaled, shifted and split on the way into the operand registers: ~5 VALU per value once per row block
       // (18 - 24 column tiles of three slice periods each), instead of a kernel that reads the rows and writes the planes
       const int row = min(m0w + l31, p.M - 1);
-      const wvn_f32x2_t st = *(const wvn_f32x2_t*)(p.ln_stats + 2 * (size_t)row);
+      int xrow = row;
+      if constexpr (HEAD) xrow += (row / p.npatch) * (p.ntok_s - p.npatch) + 1;   // patch row -> residual row: frame * ntok_s + 1 + patch (outputs stay indexed by the patch row)
+      const wvn_f32x2_t st = *(const wvn_f32x2_t*)(p.ln_stats + 2 * (size_t)xrow);
       const float a1 = st[1], a0 = -st[0] * st[1];
-      const float* xr = p.ln_x + (size_t)row * p.ln_ldx + hi * 8;
+      const float* xr = p.ln_x + (size_t)xrow * p.ln_ldx + hi * 8;
       // twelve k-steps = 24 row pieces = 96 registers at a time: two memory round trips per row block, for a wave that has nothing to hide
       // them behind (four k-steps at a time: six round trips, +4.7 ms per step; all 48 pieces at once: ~180 spilled registers).  The
       // scheduling barriers keep each group's requests in front of its arithmetic, the empty asm keeps the arithmetic of a k-step in
@@ -228,8 +238,13 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
           float y[8];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            y[e] = fmaf(fmaf(u[2 * i][e], a1, a0), g0[e], b0[e]);
-            y[4 + e] = fmaf(fmaf(u[2 * i + 1][e], a1, a0), g1[e], b1[e]);
+            if constexpr (HEAD) {   // the fp32 LayerNorm kernel's own operation order: the tokens it would have written, bit for bit
+              y[e] = fmaf(__fmul_rn(__fsub_rn(u[2 * i][e], st[0]), a1), g0[e], b0[e]);
+              y[4 + e] = fmaf(__fmul_rn(__fsub_rn(u[2 * i + 1][e], st[0]), a1), g1[e], b1[e]);
+            } else {
+              y[e] = fmaf(fmaf(u[2 * i][e], a1, a0), g0[e], b0[e]);
+              y[4 + e] = fmaf(fmaf(u[2 * i + 1][e], a1, a0), g1[e], b1[e]);
+            }
           }
           uint32_t h[4], l[4];
 #pragma unroll
@@ -293,6 +308,13 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
   } else if constexpr (!IS_QKV) {
     voff[0] = (unsigned)(((lane >> 3) * p.ldc + (lane & 7) * 8) * 2);
     stg_rd = (lane >> 3) * 144 + (lane & 7) * 16;
+  }
+  // X_HEAD, code tiles: fp32 rows of the code buffer through a descriptor of their own (four rows of 16 lanes per store)
+  const __amdgpu_buffer_rsrc_t rs_code = __builtin_amdgcn_make_buffer_rsrc(HEAD ? (void*)p.code : p.C, 0, HEAD ? (unsigned)((size_t)p.M * p.ld_code * 4) : 0u, 0x00020000);
+  unsigned stg_rd_code = 0;
+  if constexpr (HEAD) {
+    voff[1] = (unsigned)(((lane >> 4) * p.ld_code + (lane & 15) * 4) * 4);
+    stg_rd_code = (lane >> 4) * 272 + (lane & 15) * 16;
   }
 
   // ---- one k-step (16 of the slice's 128) of one ring slice: the (W hi, W lo) fragment pairs of the two column halves -> six MFMAs,
@@ -381,7 +403,8 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
   // TR tiles : images [32 rows m][64 cols n] (bf16 rows of 144 B: hi image at 0, lo image at IMG_BF16; fp32 rows of 272 B)
   // !TR tiles: images [64 rows n][32 cols m] (rows of 80 B; hi at 0, lo at 64 * 80)       -- V^T
   auto epi_chunk = [&](int part, int jp, int s, auto tr_tag) __attribute__((always_inline)) {
-    constexpr bool TR = decltype(tr_tag)::value;
+    constexpr bool TR = HEAD || decltype(tr_tag)::value;
+    constexpr bool CODE = HEAD && !decltype(tr_tag)::value;   // X_HEAD: the tag is the tile's KIND -- true: hidden planes (ReLU), false: fp32 code rows
     const int n0 = jp * BNT;
     if constexpr (EPI == X_RESID) {
       if (part == 1 && s >= 6)   // the first two residual row groups of part 2
@@ -428,7 +451,15 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
           }
           return;
         }
-        if constexpr (EPI == X_RESID) {
+        if constexpr (HEAD) {   // bias BEHIND the accumulation (the accumulators start at zero): the summation order of the tiled gemm_x3 kernel, whose results these are bit for bit
+          const wvn_f32x2_t b2 = *(const wvn_f32x2_t*)(bias_l + n0 + c);
+          v0 += b2[0]; v1 += b2[1];
+        }
+        if constexpr (HEAD && !CODE) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
+        if constexpr (CODE) {
+          const wvn_f32x2_t o = {v0, v1};
+          *(wvn_f32x2_t*)(stg + l31 * 272 + c * 4) = o;
+        } else if constexpr (EPI == X_RESID) {
           if (p.ls) { v0 *= p.ls[n0 + c]; v1 *= p.ls[n0 + c + 1]; }
           const wvn_f32x2_t o = {v0, v1};
           *(wvn_f32x2_t*)(stg + l31 * 272 + c * 4) = o;
@@ -461,7 +492,13 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
       return;
     }
     // part 2: wave-private image(s) -> global, 16 bytes per lane
-    if constexpr (EPI == X_RESID) {
+    if constexpr (CODE) {   // four fp32 rows of 64 columns per chunk, onto code columns n0 - 384 ..; rows past M are dropped
+      const int it = s;
+      const unsigned so = __builtin_amdgcn_readfirstlane(((m0w + 4 * it) * p.ld_code + (n0 - KD)) * 4);
+      const u32x4_t o = *(const u32x4_t*)(stg + stg_rd_code + it * 4 * 272);
+      const unsigned vo = m0w + 4 * it + (lane >> 4) < p.M ? voff[1] : OOB;
+      wvn_store_b128_guarded(o, rs_code, vo, so);
+    } else if constexpr (EPI == X_RESID) {
       const int it = s;
       const unsigned so = __builtin_amdgcn_readfirstlane(((m0w + 4 * it) * p.ldc + n0) * 4);
       f32x4_t v = *(const f32x4_t*)(stg + stg_rd + it * 4 * 272);
@@ -512,7 +549,12 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
   auto init_acc = [&](int j, auto tr_tag) __attribute__((always_inline)) {
     constexpr bool TR = decltype(tr_tag)::value;
     const int n0 = j * BNT;
-    if constexpr (TR) {
+    if constexpr (HEAD) {   // (the bias is added in the epilogue: see epi_chunk)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    } else if constexpr (TR) {
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -651,6 +693,25 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
         else tile(j, j - j0, j1, F{}, F{}, F{});
       }
       if (j1 - 1 < nqk) {
+#pragma unroll
+        for (int part = 0; part < 3; ++part)
+#pragma unroll
+          for (int c = 0; c < 8; ++c) epi_chunk(part, j1 - 1, c, T{});
+      } else {
+#pragma unroll
+        for (int part = 0; part < 3; ++part)
+#pragma unroll
+          for (int c = 0; c < 8; ++c) epi_chunk(part, j1 - 1, c, F{});
+      }
+    } else if constexpr (HEAD) {
+      using T = std::true_type; using F = std::false_type;
+      constexpr int NPL = KD / BNT;   // column tiles 0 .. 5: hidden planes; 6, 7: code rows.  The epilogue riding in tile j is tile j - 1's
+      init_acc(j0, T{});
+      for (int j = j0; j < j1; ++j) {
+        if (j <= NPL) tile(j, j - j0, j1, T{}, T{}, T{});
+        else tile(j, j - j0, j1, T{}, F{}, T{});
+      }
+      if (j1 - 1 < NPL) {
 #pragma unroll
         for (int part = 0; part < 3; ++part)
 #pragma unroll
@@ -1204,6 +1265,35 @@ int wvn_gemm_a384_x3_launch(const GemmBf16Params& g, int epi, hipStream_t st) {
     }
     default: return WVN_ERR_ARG;
   }
+}
+
+// The STEGO head's two products on the final-LayerNorm tokens, formed on load from the residual rows (X_HEAD): x [frames * ntok_s][ldx] fp32 residual rows with
+// stats[row] = {mean, rstd}; W / W_lo [512][384] = [W_hid; W_lin zero-padded to 128 rows], bias [512]; hid / hid_lo [M][384] bf16 planes of ReLU(tok W_hid^T + b),
+// code [M][ld_code] fp32 rows whose columns 0 .. 127 receive tok W_lin^T + b (M = frames * npatch patch rows).  WVN_ERR_ARG before any launch where not eligible.
+int wvn_gemm_a384_head_launch(const float* x, int ldx, const float* stats, const float* g, const float* b, const bf16_t* W, const bf16_t* W_lo, const float* bias,
+                              bf16_t* hid, bf16_t* hid_lo, float* code, int ld_code, int frames, int npatch, int ntok_s, hipStream_t st) {
+  constexpr int N = KD + 2 * BNT;
+  if (!x || !stats || !g || !b || !W || !W_lo || !bias || !hid || !hid_lo || !code) return WVN_ERR_ARG;
+  if (frames <= 0 || npatch <= 0 || ntok_s <= npatch || (ldx % 4) || ldx < KD || (ld_code % 4) || ld_code < 2 * BNT) return WVN_ERR_ARG;
+  if (((uintptr_t)x | (uintptr_t)W | (uintptr_t)W_lo | (uintptr_t)hid | (uintptr_t)hid_lo | (uintptr_t)code) & 15) return WVN_ERR_ARG;
+  if ((uintptr_t)stats & 7) return WVN_ERR_ARG;
+  if (W_lo <= W || (size_t)(W_lo - W) + (size_t)N * KD >= (1ull << 30)) return WVN_ERR_ARG;   // one descriptor over both planes
+  const long long M = (long long)frames * npatch;
+  if (M * KD * 2 >= (1ll << 31) || M * ld_code * 4 >= (1ll << 31)) return WVN_ERR_ARG;
+  X384Params p{};
+  p.lda = KD; p.W = W; p.w_plane = (size_t)(W_lo - W); p.bias = bias;
+  p.C = hid; p.C_lo = hid_lo; p.ldc = KD; p.M = (int)M; p.N = N; p.q_scale = 1.f;
+  p.ntok_s = ntok_s; p.npatch = npatch; p.code = code; p.ld_code = ld_code;
+  p.ln_x = x; p.ln_ldx = ldx; p.ln_stats = stats; p.ln_g = g; p.ln_b = b;
+  const int lds = BIAS_OFF + N * 4 + 2 * KD * 4;
+  static_assert(BIAS_OFF + N * 4 + 2 * KD * 4 <= X384_LDS_MAX, "ring + staging + bias / gamma / beta tables");
+  static LdsOptIn lds_opt_in;
+  if (const int rc = lds_opt_in(X384_LDS_MAX, (const void*)gemm_a384_x3_kernel<X_HEAD, false, true>)) return rc;
+  const long long units = (long long)ceil_div(p.M, BM) * (N / BNT);
+  const int grid = (int)(units < x384_num_cus() ? units : x384_num_cus());
+  hipLaunchKernelGGL((gemm_a384_x3_kernel<X_HEAD, false, true>), dim3(grid), dim3(256), lds, st, p);
+  WVN_LAUNCH_CHECK();
+  return WVN_OK;
 }
 
 void wvn_gemm_a384_mx_set_form(int form) { g_a384_mx_form = form == 1 || form == 2 ? form : 0; }

@@ -1160,16 +1160,17 @@ int run_kmeans_pixels(const float* code, int* labels, int* nseg, float* scratch,
 }
 
 // out[b][gy][gx][:] = 0.5 * (a[b][gy][gx][:] + m[b][gy][G-1-gx][:]): the code averaged with the flipped-back code of the mirrored
-// frame (the flip pass of the upstream get_code)
-__global__ void flip_average_kernel(const float* __restrict__ a, const float* __restrict__ m, float* __restrict__ out, long long n,
-                                    int G, int C) {
+// frame (the flip pass of the upstream get_code).  a and m have a row stride of ld floats (the padded code rows of the fused STEGO head; ld == C: contiguous), out is
+// contiguous; m == nullptr: out = a, the rows narrowed (one pass, no mirror)
+__global__ void flip_average_kernel(const float* a, const float* m, float* out, long long n, int G, int C, int ld) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int c = (int)(i % C);
   const long long r = i / C;
   const int gx = (int)(r % G);
   const long long row = r / G;
-  out[i] = __fmul_rn(__fadd_rn(a[i], m[(row * G + (G - 1 - gx)) * C + c]), 0.5f);
+  const float v = a[r * ld + c];
+  out[i] = m ? __fmul_rn(__fadd_rn(v, m[(row * G + (G - 1 - gx)) * ld + c]), 0.5f) : v;
 }
 
 // out[r] = argmax_c x[r][c], lowest index wins ties (torch.argmax semantics on finite rows): the label maps of the STEGO
@@ -1262,10 +1263,11 @@ int wvn_kmeans_pixels_screen_stats(unsigned long long* out, int reset) {
   return e == hipSuccess ? WVN_OK : (int)e;
 }
 
-int wvn_flip_average_launch(const float* a, const float* mirrored, float* out, int B, int G, int C, hipStream_t st) {
-  if (!a || !mirrored || !out || B <= 0 || G <= 0 || C <= 0) return WVN_ERR_ARG;
+int wvn_flip_average_launch(const float* a, const float* mirrored, float* out, int B, int G, int C, int ld_src, hipStream_t st) {
+  if (!a || !out || B <= 0 || G <= 0 || C <= 0 || ld_src < C) return WVN_ERR_ARG;
+  if (ld_src != C && out == a) return WVN_ERR_ARG;   // in place only on contiguous rows
   const long long n = (long long)B * G * G * C;
-  hipLaunchKernelGGL(flip_average_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, mirrored, out, n, G, C);
+  hipLaunchKernelGGL(flip_average_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, mirrored, out, n, G, C, ld_src);
   WVN_LAUNCH_CHECK();
   return WVN_OK;
 }

@@ -586,8 +586,9 @@ size_t wvn_vit_workspace_bytes_impl(const wvn_vit_model* m, int batch) { return 
 // batch + i is frame i gathered through the second column table (its mirror image: the flip pass of the upstream Stego.get_code).
 // Twice the rows per launch: the persistent block kernels end on a thinner partial round (6.2 -> 12.3 rounds of row blocks).
 int wvn_vit_forward_impl(const wvn_vit_model* m, const void* img, int img_u8, const WvnIngest* ing, int batch, float* tokens_f32, void* tokens_lowp,
-                         int ld_lowp, void* workspace, size_t workspace_bytes, void* stream, const int* cols_mirror) {
+                         int ld_lowp, void* workspace, size_t workspace_bytes, void* stream, const int* cols_mirror, const wvn_stego_head* head) {
   if (!m || !img || !workspace || batch <= 0 || (cols_mirror && !ing)) return WVN_ERR_ARG;
+  if (head && (tokens_f32 || tokens_lowp)) return WVN_ERR_ARG;   // the code INSTEAD of the tokens: a caller that needs both runs the head itself
   const int frames_in = batch;
   if (cols_mirror) batch *= 2;
   if (m->dim != m->heads * 64 || m->depth <= 0 || m->depth > WVN_MAX_DEPTH || m->img_size % m->patch) return WVN_ERR_ARG;
@@ -601,6 +602,18 @@ int wvn_vit_forward_impl(const wvn_vit_model* m, const void* img, int img_u8, co
   const bool split = r.family == FAM_SPLIT, f32 = r.family == FAM_F32;
   if (split && tokens_lowp) return WVN_ERR_ARG;  // exact mode hands out fp32 tokens only (callers split with wvn_split_planes)
   const int Mp = (int)d.Mp;
+  bf16_t* head_hid = (bf16_t*)w.hid;   // the head's hidden planes [2][Mp][384]: the hidden-activation region is free once the last fc2 has run
+  if (head) {
+    // Eligible on the route of the split-operand block kernels with the statistics buffer (D = 384, r.ln_fuse, from kRowsSplitKernels rows on) where the head
+    // launch takes the shapes; decided here, before anything is launched
+    if (!split || d.D != 384 || !r.ln_fuse) return WVN_ERR_ARG;
+    if (!head->w_cat || !head->b_cat || !head->w_nl || !head->b_nl || !head->code || head->code_dim <= 0 || head->code_dim > 128 || head->ld_code < 128 ||
+        (head->ld_code % 4))
+      return WVN_ERR_ARG;
+    if ((((uintptr_t)head->w_cat | (uintptr_t)head->w_nl | (uintptr_t)head->code) & 15) || (size_t)d.Mp * 384 * 2 >= (1ull << 31) ||
+        (size_t)d.Mp * head->ld_code * 4 >= (1ull << 31) || (size_t)2 * d.Mp * 384 > d.pl_frag * 2)
+      return WVN_ERR_ARG;
+  }
 
   {
     Span s(0, st);
@@ -658,6 +671,19 @@ int wvn_vit_forward_impl(const wvn_vit_model* m, const void* img, int img_u8, co
       case FAM_SPLIT: RET_IF(block_split(f, L, lr, last, carry)); break;
       case FAM_F32: RET_IF(block_f32(f, L)); break;
     }
+  }
+  if (head) {
+    // the STEGO head off the residual rows: LayerNorm on load + [W_hid; W_lin] in one A-stationary launch, then code += hid W_nl^T + b_nl on the tiled kernel
+    // The final LayerNorm's {mean, rstd} come from a statistics pass with the LayerNorm kernel's own arithmetic, not from the last fc2's one-pass sums: the
+    // tokens formed on load are then the ones that kernel writes, and the code is the separate launches' bit for bit
+    RET_IF(wvn_layernorm_patch_stats_launch(w.x, w.ln_stats, d.B, d.npatch, d.ntok_s, kLnEps, st));
+    bf16_t* hid_lo = head_hid + (size_t)Mp * 384;
+    RET_IF(wvn_gemm_a384_head_launch(w.x, d.D, w.ln_stats, m->norm_g, m->norm_b, (const bf16_t*)head->w_cat, (const bf16_t*)head->w_cat + (size_t)512 * 384, head->b_cat,
+                                     head_hid, hid_lo, head->code, head->ld_code, d.B, d.npatch, d.ntok_s, st));
+    GemmBf16Params p{};
+    p.A = head_hid; p.A_lo = hid_lo; p.lda = 384; p.W = (const bf16_t*)head->w_nl; p.W_lo = (const bf16_t*)head->w_nl + (size_t)head->code_dim * 384; p.ldw = 384;
+    p.bias = head->b_nl; p.C = head->code; p.ldc = head->ld_code; p.M = Mp; p.N = head->code_dim; p.K = 384;
+    return wvn_gemm_x3_launch(p, EPI_RESID_F32, st);
   }
   Span s(2, st);
   return wvn_layernorm_launch(w.x, m->norm_g, m->norm_b, tokens_lowp, split || f32 ? 0 : r.opk->fmt, ld_lowp, tokens_f32, d.D, Mp, d.D, kLnEps, 1, d.ntok,

@@ -99,6 +99,9 @@ int wvn_gemm_n384_x3_frag_launch(const GemmBf16Params& p, int epi, hipStream_t s
 int wvn_gemm_n384_mx_launch(const GemmBf16Params& p, int epi, hipStream_t st);
 // the MX form of the A-stationary kernel (LayerNorm on load; EPI_GELU_FRAG -> MX fragment planes, EPI_QKV -> fp16 q | k | v^T); W packed by backbone.pack_a384_mx
 int wvn_gemm_a384_mx_launch(const GemmBf16Params& p, int epi, hipStream_t st);
+// the STEGO head's two products on LayerNorm(x), formed on load from the residual rows (gemm_a384_x3.hip, X_HEAD): hidden planes + padded code rows
+int wvn_gemm_a384_head_launch(const float* x, int ldx, const float* stats, const float* g, const float* b, const bf16_t* W, const bf16_t* W_lo, const float* bias,
+                              bf16_t* hid, bf16_t* hid_lo, float* code, int ld_code, int frames, int npatch, int ntok_s, hipStream_t st);
 
 // Descriptor builders of the split-operand / MX block kernels (vit_forward.hip): one per kernel, used by the forward and by the
 // stand-alone wvn_debug_* entries, which pass the planes the forward does not (dbg, A_h8, C_h8).
@@ -190,14 +193,18 @@ int wvn_pad_zero_launch(void* base, long long nrows, long long row_stride_bytes,
 int wvn_layernorm_launch(const float* x, const float* gamma, const float* beta, void* y, int y_fmt, int ldy,
                          float* y2, int ldy2, int rows_out, int D, float eps, int drop_cls, int ntok,
                          int ntok_s, hipStream_t st, void* y_lo = nullptr);  // y_lo: exact mode, lo plane of the bf16 output
+// {mean, rstd} of the patch rows of x [frames * ntok_s][384] with the arithmetic of the fp32 LayerNorm kernel, into stats[2 * (frame * ntok_s + 1 + patch)]
+int wvn_layernorm_patch_stats_launch(const float* x, float* stats, int frames, int npatch, int ntok_s, float eps, hipStream_t st);
 int wvn_cast_f32_bf16_launch(const float* src, int lds_, bf16_t* dst, int ldd, int rows, int cols, hipStream_t st, int f16 = 0);
 
 // ---- the ViT forward (vit_forward.hip) behind wvn_vit_forward* / wvn_vit_workspace_bytes (api.hip) -------------------
 struct wvn_vit_model;
+struct wvn_stego_head;
 size_t wvn_vit_workspace_bytes_impl(const wvn_vit_model* m, int batch);
 // img_u8: raw uint8 pixels; ing: optional NEAREST resize + crop tables; cols_mirror: see vit_forward.hip
 int wvn_vit_forward_impl(const wvn_vit_model* m, const void* img, int img_u8, const WvnIngest* ing, int batch, float* tokens_f32, void* tokens_lowp,
-                         int ld_lowp, void* workspace, size_t workspace_bytes, void* stream, const int* cols_mirror = nullptr);
+                         int ld_lowp, void* workspace, size_t workspace_bytes, void* stream, const int* cols_mirror = nullptr,
+                         const wvn_stego_head* head = nullptr);   // head: the STEGO code instead of tokens (WVN_ERR_ARG before any launch where not eligible)
 
 // ---- attention (attention_bf16.hip / attention_f32.hip) ---------------------------------------
 int wvn_attention_f32_launch(const float* q, const float* k, const float* v, float* out, int B, int heads, int ntok,
@@ -243,7 +250,7 @@ int wvn_table_slots(int K);
 int wvn_table_bilerp_argmax_launch(const float* table, int* labels, int B, int G, int H, int K, hipStream_t st, int align_corners = 1);
 void wvn_kmeans_pixels_set_assign_form(int form);
 int wvn_kmeans_pixels_screen_stats(unsigned long long* out, int reset);   // -1 default (MFMA where eligible), 0 the VALU form always
-int wvn_flip_average_launch(const float* a, const float* mirrored, float* out, int B, int G, int C, hipStream_t st);
+int wvn_flip_average_launch(const float* a, const float* mirrored, float* out, int B, int G, int C, int ld_src, hipStream_t st);   // mirrored == nullptr: out = a, narrowed
 int wvn_kmeans_launch(const float* xn, int* labels, int* nseg, float* scratch, int B, int P, int C, int K, int iters,
                       int relabel, hipStream_t st);
 // ConfidenceGenerator method of a training step (include/wvn_hip.h, wvn_conf_desc).  The default -- state == nullptr -- is the

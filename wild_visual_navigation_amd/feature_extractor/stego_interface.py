@@ -34,7 +34,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from .. import _lib, ops
-from ..backbone import ARCH, VitBackbone, split_planes
+from ..backbone import ARCH, StegoHead, VitBackbone, split_planes
 from .dino_interface import _Cfg, _load_state_dict
 
 STEGO_CODE_DIM = 90
@@ -130,6 +130,8 @@ class StegoInterface:
         code_align_corners: bool = True,   # how postprocess() up-samples the code BEFORE clustering / probing (the absent package's choice, stego_interface.py:94-100):
         #                                    True = the align_corners=True taps of WVN's own later up-sample (:107); False = the half-pixel taps of the public STEGO
         #                                    evaluation code.  `features` (stego_interface.py:107) and the pooling are WVN's own code: always align_corners=True
+        fuse_head: Optional[bool] = None,  # "exact" / "mixed", D = 384: run the head off the backbone's residual rows (final LayerNorm on load, no token tensor;
+        #                                    VitBackbone.forward_tokens(head=)).  None: on unless the environment variable WVN_NO_HEAD_FUSE is set -- read HERE, once
     ):
         if cfg is None or len(cfg) == 0:
             self._cfg = _Cfg(model_path=model_path, input_size=input_size, run_crf=run_crf,
@@ -202,6 +204,7 @@ class StegoInterface:
         dev = self._device
         self._D = D
         self._C = head["cluster1.0.weight"].shape[0]
+        self._head = None   # the pack of the fused route (fuse_head)
         self._b_hid = head["cluster2.0.bias"].float().to(dev).contiguous()
         self._b_code = (head["cluster1.0.bias"] + head["cluster2.2.bias"]).float().to(dev).contiguous()
         self._b_lin = head["cluster1.0.bias"].float().to(dev).contiguous()
@@ -214,6 +217,13 @@ class StegoInterface:
             self._w_hid = split_planes(head["cluster2.0.weight"].float().to(dev))
             self._w_lin = split_planes(head["cluster1.0.weight"].float().to(dev))
             self._w_nl = split_planes(head["cluster2.2.weight"].float().to(dev))
+            if fuse_head is None:
+                import os
+
+                fuse_head = os.environ.get("WVN_NO_HEAD_FUSE", "0") in ("", "0")
+            if fuse_head and D == 384 and self._C <= 128:   # (D = 768 keeps the separate products)
+                self._head = StegoHead(head["cluster2.0.weight"].float().to(dev), self._b_hid, head["cluster1.0.weight"].float().to(dev), self._b_lin,
+                                       head["cluster2.2.weight"].float().to(dev), self._b_nl)
         else:
             self._w_hid = head["cluster2.0.weight"].float().to(dev).contiguous()
             self._w_lin = head["cluster1.0.weight"].float().to(dev).contiguous()
@@ -248,12 +258,20 @@ class StegoInterface:
             t = getattr(self, name, None)
             if t is not None:
                 setattr(self, name, t.to(device))
+        if self._head is not None:
+            hs = {k: v.float().to(device) for k, v in self._head_sd.items()}
+            self._head = StegoHead(hs["cluster2.0.weight"], hs["cluster2.0.bias"], hs["cluster1.0.weight"], hs["cluster1.0.bias"], hs["cluster2.2.weight"],
+                                   hs["cluster2.2.bias"])
         self._device = device
 
     # ---- code (STEGO head) at patch resolution --------------------------------------------------------
     def _code_once(self, img: torch.Tensor, flip: bool = False) -> torch.Tensor:
         B = img.shape[0]
         P, D = self._bb.grid ** 2, self._D
+        if self._head is not None:   # the head off the residual rows; the padded code rows narrowed by the flip-average kernel's no-mirror form
+            wide = self._bb.forward_tokens(img, flip=flip, head=self._head)
+            out = torch.empty(B, P, self._C, dtype=torch.float32, device=self._device)
+            return ops.flip_average(wide[:, :, :self._C], None, self._bb.grid, out=out)
         if self._precision in ("bf16", "fp8", "fp16"):
             cat = torch.empty(B * P, 2 * D, dtype=self._bb.lowp_dtype, device=self._device)  # [tok | hid]
             self._bb.forward_tokens(img, lowp_out=cat, flip=flip)
@@ -273,9 +291,12 @@ class StegoInterface:
 
     def _code_pair(self, img: torch.Tensor):
         """``_code_once`` for the frames and their mirrors together: (code [2B, P, C], chunk) in the layout of
-        ``VitBackbone.forward_tokens_pair``."""
+        ``VitBackbone.forward_tokens_pair``.  With the fused head the rows have the padded stride ``StegoHead.LD`` (a view)."""
         B = img.shape[0]
         P, D = self._bb.grid ** 2, self._D
+        if self._head is not None:
+            wide, chunk = self._bb.forward_tokens_pair(img, head=self._head)
+            return wide[:, :, :self._C], chunk
         if self._precision in ("bf16", "fp8", "fp16"):
             cat = torch.empty(2 * B * P, 2 * D, dtype=self._bb.lowp_dtype, device=self._device)  # [tok | hid]
             _, chunk = self._bb.forward_tokens_pair(img, lowp_out=cat)

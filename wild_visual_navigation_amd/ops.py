@@ -426,16 +426,25 @@ def table_bilerp_argmax(table: torch.Tensor, G: int, H: int, align_corners: bool
     return labels
 
 
-def flip_average(code: torch.Tensor, mirrored: torch.Tensor, G: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """0.5 * (code + flip_x(mirrored)) on [B, G*G, C] fp32 patch maps (in place on ``code`` unless ``out`` is given)."""
+def flip_average(code: torch.Tensor, mirrored: Optional[torch.Tensor], G: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """0.5 * (code + flip_x(mirrored)) on [B, G*G, C] fp32 patch maps (in place on ``code`` unless ``out`` is given).  The inputs may be
+    views of rows with a padded stride (``buf[..., :C]`` of the [.., 128] code rows the fused STEGO head writes); ``out`` is then required
+    and contiguous.  ``mirrored=None``: ``out = code`` (the padded rows narrowed, no mirror pass)."""
     require_cuda(code, "code")
     B, P, Cc = code.shape
-    if not (code.is_contiguous() and mirrored.is_contiguous()) or mirrored.shape != code.shape or P != G * G:
-        raise _lib.WvnError("flip_average: contiguous [B, G*G, C] fp32 pairs expected")
+    ld = code.stride(1)
+
+    def rows_ok(t):
+        return t.dtype == torch.float32 and t.stride(2) == 1 and t.stride(1) == ld and (t.shape[0] == 1 or t.stride(0) == P * ld)
+
+    if P != G * G or ld < Cc or not rows_ok(code) or (mirrored is not None and (mirrored.shape != code.shape or not rows_ok(mirrored))):
+        raise _lib.WvnError("flip_average: [B, G*G, C] fp32 pairs expected, contiguous or with one common padded row stride")
+    if out is None and (ld != Cc or mirrored is None):
+        raise _lib.WvnError("flip_average: padded rows / the no-mirror form need out=")
     dst = code if out is None else out
     if out is not None and (not out.is_contiguous() or out.shape != code.shape or out.dtype != torch.float32):
         raise _lib.WvnError("flip_average: out must be a contiguous fp32 tensor of the inputs' shape")
-    check(lib().wvn_flip_average(ptr(code), ptr(mirrored), ptr(dst), B, G, Cc, stream()), "wvn_flip_average")
+    check(lib().wvn_flip_average(ptr(code), ptr(mirrored), ptr(dst), B, G, Cc, ld, stream()), "wvn_flip_average")
     return dst
 
 
@@ -707,6 +716,46 @@ def gemm_x3(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], epi:
     check(lib().wvn_gemm_x3(ptr(a[0]), ptr(a[1]), a.stride(1), ptr(w[0]), ptr(w[1]), w.stride(1), ptr(bias), ptr(c), ptr(c_lo),
                             ldc, M, N, K, epi, stream()), "wvn_gemm_x3")
     return out
+
+
+STEGO_HEAD_LD = 128   # row stride (floats) of the code rows the fused STEGO head writes: 16-byte aligned rows for any code dimension <= 128
+
+
+def pack_stego_head(w_hid: torch.Tensor, b_hid: torch.Tensor, w_lin: torch.Tensor, b_lin: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The weight of the fused STEGO-head launch (include/wvn_hip.h: wvn_stego_head.w_cat / b_cat): hi / lo bf16 planes [2, 512, 384] of
+    [W_hid (384 rows); W_lin (C <= 128 rows); zeros] and the fp32 bias [512] = [b_hid; b_lin; zeros].  fp32 device tensors in."""
+    from .backbone import split_planes as _split
+
+    D, Cc = w_hid.shape[1], w_lin.shape[0]
+    if w_hid.shape != (384, 384) or w_lin.shape[1] != 384 or Cc > 128:
+        raise _lib.WvnError(f"pack_stego_head: D = 384 and a code dimension <= 128 expected, got {tuple(w_hid.shape)} / {tuple(w_lin.shape)}")
+    w = torch.zeros(512, D, dtype=torch.float32, device=w_hid.device)
+    w[:384], w[384:384 + Cc] = w_hid.float(), w_lin.float()
+    b = torch.zeros(512, dtype=torch.float32, device=w_hid.device)
+    b[:384], b[384:384 + Cc] = b_hid.float(), b_lin.float()
+    return _split(w), b.contiguous()
+
+
+def stego_head_fused(x: torch.Tensor, stats: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, w_cat: torch.Tensor, b_cat: torch.Tensor,
+                     frames: int, npatch: int, ntok_s: int, hid: Optional[torch.Tensor] = None,
+                     code: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The first launch of the fused STEGO head alone (csrc/gemm_a384_x3.hip, X_HEAD): x [frames * ntok_s, 384] fp32 residual rows, stats
+    [frames * ntok_s, 2] = {mean, rstd} -> (hid bf16 planes [2, M, 384] = ReLU(LN(x) W_hid^T + b_hid), code fp32 [M, 128] whose columns
+    hold LN(x) W_lin^T + b_lin), M = frames * npatch patch rows; patch p of frame f is read at row f * ntok_s + 1 + p.  ``hid`` /
+    ``code`` may be given with MORE rows than M: the rows past M are not written."""
+    require_cuda(x, "x")
+    M = frames * npatch
+    if hid is None:
+        hid = torch.empty(2, M, 384, dtype=torch.bfloat16, device=x.device)
+    if code is None:
+        code = torch.empty(M, STEGO_HEAD_LD, dtype=torch.float32, device=x.device)
+    if x.shape != (frames * ntok_s, 384) or not x.is_contiguous() or stats.shape != (frames * ntok_s, 2) or not stats.is_contiguous():
+        raise _lib.WvnError("stego_head_fused: x [frames * ntok_s, 384] and stats [frames * ntok_s, 2], contiguous fp32, expected")
+    if hid.dim() != 3 or hid.shape[0] != 2 or hid.shape[1] < M or hid.shape[2] != 384 or not hid.is_contiguous() or code.shape[0] < M or not code.is_contiguous():
+        raise _lib.WvnError("stego_head_fused: hid [2, >= M, 384] bf16 and code [>= M, ld] fp32, contiguous, expected")
+    check(lib().wvn_debug_stego_head_fused(ptr(x), x.stride(0), ptr(stats), ptr(ln_g), ptr(ln_b), ptr(w_cat), ptr(b_cat), ptr(hid[0]), ptr(hid[1]), ptr(code),
+                                           code.stride(0), frames, npatch, ntok_s, stream()), "wvn_debug_stego_head_fused")
+    return hid, code
 
 
 def qkv_fused(x: torch.Tensor, ln: Tuple[torch.Tensor, torch.Tensor, float], w: torch.Tensor, bias: Optional[torch.Tensor],
