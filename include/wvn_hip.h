@@ -737,6 +737,36 @@ int wvn_rnvp_forward_pixels(const wvn_rnvp_desc* d, const void* packed, const fl
                             float* conf, float* log_det, float* z, int ldz, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Anomaly detection: one optimisation step of the flow (AnomalyLoss: loss = -mean(score) over ALL ranks' rows, torch.optim.Adam
+ * defaults; csrc/rnvp_train.hip), in the three phases of the traversability MLPs' step with the same two exchanges:
+ *   phase_a : forward on this rank's rows x [R][ldx >= D] -> score [R], the backward pass's activations -> workspace, and the
+ *             LOCAL statistic stats[4] = {n, sum x, sum x^2, n} of x = -score (fp64)            -> all-reduce(sum) of stats
+ *   phase_b : grads [param_count] fp32 in params order from the workspace phase_a filled and the GLOBAL stats (seed -1/n);
+ *             parameters the masks disconnect get exact zeros                                   -> all-reduce(sum) of grads
+ *   phase_c : Adam step `step` (>= 1) on params with moments adam_m / adam_v; losses[3] = {loss, mean, std}; the confidence
+ *             statistic of `method` (WVN_CONF_*) is committed to conf_state [WVN_CONF_STATE_DOUBLES] from the global stats (every
+ *             row is a positive); packed and train_packed are rebuilt from the new params.
+ * R = 0 is legal in phase_a / phase_b (an empty shard contributes zeros); R <= 65536.  One fixed summation order, no atomics:
+ * bitwise reproducible.  No host synchronisation; the launch count does not depend on R.
+ * train_packed : wvn_rnvp_train_pack_bytes() bytes, 16-byte aligned: the transposed weight images, built by wvn_rnvp_train_pack
+ *                from params and the forward blob `packed` (whose column tables it reads).
+ * workspace    : wvn_rnvp_train_workspace_bytes(d, R) bytes, 16-byte aligned, the same memory in phase_a and phase_b.
+ * Sizes are 0 and calls return WVN_ERR_ARG, before any launch, for NULL pointers, R < 0, an unsupported (D, h) or a workspace
+ * that is too small.
+ * ------------------------------------------------------------------------------------------- */
+size_t wvn_rnvp_train_param_count(const wvn_rnvp_desc* d);
+size_t wvn_rnvp_train_workspace_bytes(const wvn_rnvp_desc* d, long long R);
+size_t wvn_rnvp_train_pack_bytes(const wvn_rnvp_desc* d);
+int wvn_rnvp_train_pack(const wvn_rnvp_desc* d, const float* params, const void* packed, void* train_packed, void* stream);
+int wvn_rnvp_train_phase_a(const wvn_rnvp_desc* d, const void* packed, const float* x, int ldx, long long R, float* score,
+                           double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int wvn_rnvp_train_phase_b(const wvn_rnvp_desc* d, const void* packed, const void* train_packed, long long R, const double* stats,
+                           float* grads, void* workspace, size_t workspace_bytes, void* stream);
+int wvn_rnvp_train_phase_c(const wvn_rnvp_desc* d, float* params, const float* grads, float* adam_m, float* adam_v, int step, float lr,
+                           const double* stats, int method, double* conf_state, float* losses, const float* mask,
+                           const long long* perm, void* packed, void* train_packed, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused per-segment traversability inference: the node's per-frame path with prediction_per_pixel = False
  * (wvn_feature_extractor_node.py:320-366, quick_start.py:184-210):
  *   input_feat = feat[seg.reshape(-1)];  out = SimpleMLP(input_feat)

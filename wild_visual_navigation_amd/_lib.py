@@ -217,6 +217,13 @@ _SIGNATURES = {
     "wvn_rnvp_pack": ([_p, _p, _p, _p, _p, _p], _i),
     "wvn_rnvp_forward_rows": ([_p, _p, _p, _i, _ll, _f, _f, _f, _p, _p, _p, _p, _p, _i, _p], _i),
     "wvn_rnvp_forward_pixels": ([_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _i, _p], _i),
+    "wvn_rnvp_train_param_count": ([_p], _sz),
+    "wvn_rnvp_train_workspace_bytes": ([_p, _ll], _sz),
+    "wvn_rnvp_train_pack_bytes": ([_p], _sz),
+    "wvn_rnvp_train_pack": ([_p, _p, _p, _p, _p], _i),
+    "wvn_rnvp_train_phase_a": ([_p, _p, _p, _i, _ll, _p, _p, _p, _sz, _p], _i),
+    "wvn_rnvp_train_phase_b": ([_p, _p, _p, _ll, _p, _p, _p, _sz, _p], _i),
+    "wvn_rnvp_train_phase_c": ([_p, _p, _p, _p, _p, _i, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p], _i),
     "wvn_segment_predict_workspace_bytes": ([_p, _i, _i], _sz),
     "wvn_segment_predict": ([_p, _p, _p, _i, _ll, _i, _i, _p, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
     "wvn_debug_gemm_bf16_timed": ([_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p], _i),

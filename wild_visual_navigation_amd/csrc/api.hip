@@ -817,6 +817,52 @@ int wvn_rnvp_forward_pixels(const wvn_rnvp_desc* d, const void* packed, const fl
   return wvn_rnvp_forward_launch(c, (hipStream_t)stream);
 }
 
+// LinearRnvp training step (rnvp_train.hip): every check is host arithmetic, a refused call launches nothing
+static bool rnvp_ok(const wvn_rnvp_desc* d) { return d && wvn_rnvp_supported(d->D, d->h, d->flows); }
+static const long long RNVP_TRAIN_MAX_ROWS = 1ll << 16;   // the weight gradients walk the row tiles un-split
+size_t wvn_rnvp_train_param_count(const wvn_rnvp_desc* d) { return rnvp_ok(d) ? wvn_rnvp_train_param_count_impl(d->D, d->h) : 0; }
+size_t wvn_rnvp_train_workspace_bytes(const wvn_rnvp_desc* d, long long R) {
+  if (!rnvp_ok(d) || R < 0 || R > RNVP_TRAIN_MAX_ROWS) return 0;
+  return wvn_rnvp_train_workspace_bytes_impl(d->D, d->h, R);
+}
+size_t wvn_rnvp_train_pack_bytes(const wvn_rnvp_desc* d) { return rnvp_ok(d) ? wvn_rnvp_train_pack_bytes_impl(d->D, d->h) : 0; }
+int wvn_rnvp_train_pack(const wvn_rnvp_desc* d, const float* params, const void* packed, void* train_packed, void* stream) {
+  if (!rnvp_ok(d) || !params || !packed || !train_packed || (((uintptr_t)packed | (uintptr_t)train_packed) & 15)) return WVN_ERR_ARG;
+  return wvn_rnvp_train_pack_launch(d->D, d->h, params, packed, train_packed, (hipStream_t)stream);
+}
+int wvn_rnvp_train_phase_a(const wvn_rnvp_desc* d, const void* packed, const float* x, int ldx, long long R, float* score,
+                           double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!rnvp_ok(d) || !packed || ((uintptr_t)packed & 15) || !stats || !workspace || ((uintptr_t)workspace & 15)) return WVN_ERR_ARG;
+  if (R < 0 || R > RNVP_TRAIN_MAX_ROWS || (R > 0 && (!x || !score || ldx < d->D))) return WVN_ERR_ARG;
+  if (workspace_bytes < wvn_rnvp_train_workspace_bytes_impl(d->D, d->h, R)) return WVN_ERR_ARG;
+  RnvpCall c{};
+  c.D = d->D; c.h = d->h; c.packed = packed;
+  c.x = x; c.ldx = ldx; c.R = R; c.score = score;
+  return wvn_rnvp_train_phase_a_launch(c, stats, workspace, (hipStream_t)stream);
+}
+int wvn_rnvp_train_phase_b(const wvn_rnvp_desc* d, const void* packed, const void* train_packed, long long R, const double* stats,
+                           float* grads, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!rnvp_ok(d) || !packed || !train_packed || (((uintptr_t)packed | (uintptr_t)train_packed) & 15) || !stats || !grads ||
+      !workspace || ((uintptr_t)workspace & 15))
+    return WVN_ERR_ARG;
+  if (R < 0 || R > RNVP_TRAIN_MAX_ROWS || workspace_bytes < wvn_rnvp_train_workspace_bytes_impl(d->D, d->h, R)) return WVN_ERR_ARG;
+  return wvn_rnvp_train_phase_b_launch(d->D, d->h, packed, train_packed, R, stats, grads, workspace, (hipStream_t)stream);
+}
+int wvn_rnvp_train_phase_c(const wvn_rnvp_desc* d, float* params, const float* grads, float* adam_m, float* adam_v, int step, float lr,
+                           const double* stats, int method, double* conf_state, float* losses, const float* mask,
+                           const long long* perm, void* packed, void* train_packed, void* stream) {
+  if (!rnvp_ok(d) || !params || !grads || !adam_m || !adam_v || step <= 0 || !stats || !conf_state || !losses || !mask || !perm ||
+      !packed || !train_packed || (((uintptr_t)packed | (uintptr_t)train_packed) & 15))
+    return WVN_ERR_ARG;
+  if (method < WVN_CONF_LATEST_MEASUREMENT || method > WVN_CONF_MOVING_AVERAGE) return WVN_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = wvn_rnvp_train_param_count_impl(d->D, d->h);
+  RET_IF(wvn_adam_launch(params, grads, adam_m, adam_v, (int)n, step, lr, 0.9f, 0.999f, 1e-8f, st, nullptr, nullptr, 0.f, 0.f, nullptr));
+  RET_IF(wvn_rnvp_train_commit_launch(stats, method, conf_state, losses, st));
+  RET_IF(wvn_rnvp_pack_launch(d->D, d->h, params, mask, perm, packed, st));
+  return wvn_rnvp_train_pack_launch(d->D, d->h, params, packed, train_packed, st);
+}
+
 // fused per-segment inference (segment_predict.hip)
 size_t wvn_segment_predict_workspace_bytes(const wvn_mlp_desc* d, int B, int S) {
   if (!d || B <= 0 || S <= 0) return 0;

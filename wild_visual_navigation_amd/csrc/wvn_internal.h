@@ -364,6 +364,15 @@ size_t wvn_rnvp_pack_bytes_impl(int D, int h);
 int wvn_rnvp_row_tile_impl();
 int wvn_rnvp_pack_launch(int D, int h, const float* params, const float* mask, const long long* perm, void* packed, hipStream_t st);
 int wvn_rnvp_forward_launch(const RnvpCall& c, hipStream_t st);
+// the training step (rnvp_train.hip); phase A takes the rows source of RnvpCall (x, ldx, R, score)
+size_t wvn_rnvp_train_param_count_impl(int D, int h);
+size_t wvn_rnvp_train_workspace_bytes_impl(int D, int h, long long R);
+size_t wvn_rnvp_train_pack_bytes_impl(int D, int h);
+int wvn_rnvp_train_pack_launch(int D, int h, const float* params, const void* packed, void* tpacked, hipStream_t st);
+int wvn_rnvp_train_phase_a_launch(const RnvpCall& c, double* stats, void* ws, hipStream_t st);
+int wvn_rnvp_train_phase_b_launch(int D, int h, const void* packed, const void* tpacked, long long R, const double* stats, float* grads,
+                                  void* ws, hipStream_t st);
+int wvn_rnvp_train_commit_launch(const double* stats, int method, double* cstate, float* losses, hipStream_t st);
 
 // ---- fused per-segment traversability inference (segment_predict.hip) --------------------------------------------------
 bool wvn_segment_predict_supported(int D, int h1, int h2);

@@ -5,7 +5,8 @@ Same constructor and ``state_dict`` keys as upstream (``prior_mean``, ``prior_va
 ``flows.{0,2}.{s,t}.{0,2,4}.{weight,bias}``, ``flows.{1,3}.{p,invp}``), so its checkpoints load with ``strict=True``, and the
 parameters are created in upstream's order, so a seed gives upstream's initial values.  ``forward(Data)`` returns
 ``{"z", "log_det", "logprob"}``: through the kernel when no gradient is asked for (``eval()`` or ``torch.no_grad()``), through
-the torch statement of the same flow (``flow_torch``) when one is -- training runs on autograd.
+the torch statement of the same flow (``flow_torch``) when one is.  ``TraversabilityEstimator`` trains it on a GPU device with
+``RnvpTrainer`` (csrc/rnvp_train.hip), which works on ``flat_params()`` and never calls ``forward``; on the CPU it trains on autograd.
 
 Built: two coupling layers with separate s and t networks D -> h -> h -> D, each followed by a permutation -- what ``get_model``
 builds from ``linear_rnvp_cfg`` -- for D = 384 or 90 and h <= 256, any 0/1 mask with D/2 ones.  Refused by name: ``batch_norm``,
@@ -90,6 +91,7 @@ class LinearRnvp(torch.nn.Module):
         self.desc = _lib.RnvpDesc(input_size, self.hidden, flow_n)
         self._packed: Optional[torch.Tensor] = None
         self._packed_key = None
+        self._flat: Optional[torch.Tensor] = None
 
     # ---- the torch statement of the flow (autograd) ----------------------------------------------------
     def flow_torch(self, x: torch.Tensor):
@@ -108,14 +110,42 @@ class LinearRnvp(torch.nn.Module):
             out += [p for net in (c.s, c.t) for k in (0, 2, 4) for p in (net[k].weight, net[k].bias)]
         return out
 
-    def pack(self) -> torch.Tensor:
-        """The kernel's weight images, rebuilt when a parameter, mask, permutation or the device has changed since the last
-        call (in-place updates -- optimizer steps, ``load_state_dict`` -- move a tensor's version counter)."""
+    _params_in_order = _state_tensors   # ``model.parameters()`` order: the layout of the flat buffer, gradient and Adam moments
+
+    def flat_params(self) -> torch.Tensor:
+        """One flat fp32 buffer that the 24 parameters alias (RnvpTrainer's Adam kernel and gradient all-reduce work on it);
+        re-established when ``.to()`` or a load has broken the aliasing."""
+        ps = self._state_tensors()
+        ok = self._flat is not None and self._flat.device == ps[0].device
+        if ok:
+            off = 0
+            for p in ps:
+                if p.data_ptr() != self._flat.data_ptr() + 4 * off or not p.is_contiguous():
+                    ok = False
+                    break
+                off += p.numel()
+        if not ok:
+            flat = torch.cat([p.detach().reshape(-1).float() for p in ps]).contiguous()
+            off = 0
+            for p in ps:
+                p.data = flat[off: off + p.numel()].view_as(p)
+                off += p.numel()
+            self._flat = flat
+        return self._flat
+
+    def _pack_key(self):
         params = self._state_tensors()
         others = [self.flows[0].mask, self.flows[2].mask, self.flows[1].p, self.flows[3].p, self.prior_mean, self.prior_var]
-        key = tuple((t.data_ptr(), t._version) for t in params + others)
+        return tuple((t.data_ptr(), t._version) for t in params + others)
+
+    def pack(self) -> torch.Tensor:
+        """The kernel's weight images, rebuilt when a parameter, mask, permutation or the device has changed since the last
+        call (in-place updates -- optimizer steps, ``load_state_dict`` -- move a tensor's version counter; RnvpTrainer's kernels
+        do not, and re-pack the images themselves)."""
+        key = self._pack_key()
         if self._packed is not None and key == self._packed_key:
             return self._packed
+        params = self._state_tensors()
         dev = params[0].device
         _lib.require_cuda(params[0], "parameters")
         masks = torch.stack([self.flows[0].mask, self.flows[2].mask]).float().contiguous()

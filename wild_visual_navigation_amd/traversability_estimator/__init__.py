@@ -2,8 +2,9 @@ from .nodes import BaseNode, MissionNode, SupervisionNode, TwistNode, run_base_s
 from .graphs import (BaseGraph, DistanceWindowGraph, MaxElementsGraph, MissionGraph, TemporalWindowGraph, run_base_graph,
                      run_temporal_window_graph)
 from .trainer import MlpTrainer
+from .rnvp_trainer import RnvpTrainer
 from .traversability_estimator import TraversabilityEstimator
 
 __all__ = ["BaseNode", "MissionNode", "SupervisionNode", "BaseGraph", "DistanceWindowGraph", "MaxElementsGraph",
-           "TemporalWindowGraph", "MissionGraph", "MlpTrainer", "TraversabilityEstimator", "TwistNode", "run_base_state",
+           "TemporalWindowGraph", "MissionGraph", "MlpTrainer", "RnvpTrainer", "TraversabilityEstimator", "TwistNode", "run_base_state",
            "run_base_graph", "run_temporal_window_graph"]

@@ -26,46 +26,11 @@ from ..distributed import allreduce_max_, allreduce_sum_
 from ..model.simple_mlp import SimpleMLP
 
 
-
-
-class MlpTrainer:
-    def __init__(self, model: SimpleMLP, lr: float = 1e-3, std_factor: float = 0.5, w_trav: float = 0.03,
-                 w_reco: float = 0.5, process_group=None, fused: bool = True, method: str = "latest_measurement",
-                 anomaly_balanced: bool = True):
-        if method not in _lib.CONF_METHODS:
-            raise ValueError(f"Unknown ConfidenceGenerator method {method!r} (one of {', '.join(_lib.CONF_METHODS)})")
-        self.model = model
-        self.method, self.anomaly_balanced = method, bool(anomaly_balanced)
-        # the *_conf entry points (device state) for anything but the original configuration, which keeps its entry points
-        self._conf = method != "latest_measurement" or not self.anomaly_balanced
-        self.lr, self.std_factor, self.w_trav, self.w_reco = lr, std_factor, w_trav, w_reco
-        self.group = process_group
-        self.step = 0
-        self._state_dev = None
-        self.last_confidence: Optional[torch.Tensor] = None
-        self.comm_events = None   # set to [] to collect (start, end) CUDA-event pairs around the two all-reduces of every step
-        # True: the four-launch step of csrc/mlp_train.hip where its geometry applies (256 / 32 hidden units, <= 2048 rows);
-        # False: the general path (one kernel per stage, 17-20 launches).  Same arithmetic, other summation orders.
-        self.fused = fused
-
-    def _state(self, dev):
-        if self._state_dev != dev:
-            n = self.model.flat_params().numel()
-            self.grads = torch.zeros(n + 2, dtype=torch.float32, device=dev)
-            if self._state_dev is not None:   # change_device in the middle of a mission: the Adam moments move with the model
-                self.m, self.v = self.m.to(dev), self.v.to(dev)
-            else:
-                self.m = torch.zeros(n, dtype=torch.float32, device=dev)
-                self.v = torch.zeros(n, dtype=torch.float32, device=dev)
-            if self._state_dev is not None:   # (the confidence statistic's memory moves too)
-                self.conf_state = self.conf_state.to(dev)
-            else:
-                self.conf_state = self._initial_conf_state(dev)
-            self.minmax = torch.zeros(2, dtype=torch.float32, device=dev)
-            self.stats = torch.zeros(4, dtype=torch.float64, device=dev)
-            self.losses = torch.zeros(5, dtype=torch.float32, device=dev)
-            self.sync_word = torch.zeros(1, dtype=torch.int32, device=dev)   # arrival counter of the fused forward (zero between steps)
-            self._state_dev = dev
+class TrainerState:
+    """What the fused trainers (MlpTrainer, RnvpTrainer) keep alike: the confidence statistic's device state and its exchange with a
+    ConfidenceGenerator, the Adam moments in ``torch.optim.Adam.state_dict()`` shape, the timed all-reduce.  A subclass provides
+    ``model`` (``flat_params()``, ``_params_in_order()``), ``_state(dev)`` (which creates ``m``, ``v``, ``conf_state``), ``step``,
+    ``lr``, ``group``, ``comm_events`` and ``_state_dev``."""
 
     @staticmethod
     def _initial_conf_state(dev) -> torch.Tensor:
@@ -150,6 +115,46 @@ class MlpTrainer:
         allreduce_sum_(t, self.group)   # RCCL runs on its own stream; the current stream waits for it, so b brackets it
         b.record()
         self.comm_events.append((a, b))
+
+
+class MlpTrainer(TrainerState):
+    def __init__(self, model: SimpleMLP, lr: float = 1e-3, std_factor: float = 0.5, w_trav: float = 0.03,
+                 w_reco: float = 0.5, process_group=None, fused: bool = True, method: str = "latest_measurement",
+                 anomaly_balanced: bool = True):
+        if method not in _lib.CONF_METHODS:
+            raise ValueError(f"Unknown ConfidenceGenerator method {method!r} (one of {', '.join(_lib.CONF_METHODS)})")
+        self.model = model
+        self.method, self.anomaly_balanced = method, bool(anomaly_balanced)
+        # the *_conf entry points (device state) for anything but the original configuration, which keeps its entry points
+        self._conf = method != "latest_measurement" or not self.anomaly_balanced
+        self.lr, self.std_factor, self.w_trav, self.w_reco = lr, std_factor, w_trav, w_reco
+        self.group = process_group
+        self.step = 0
+        self._state_dev = None
+        self.last_confidence: Optional[torch.Tensor] = None
+        self.comm_events = None   # set to [] to collect (start, end) CUDA-event pairs around the two all-reduces of every step
+        # True: the four-launch step of csrc/mlp_train.hip where its geometry applies (256 / 32 hidden units, <= 2048 rows);
+        # False: the general path (one kernel per stage, 17-20 launches).  Same arithmetic, other summation orders.
+        self.fused = fused
+
+    def _state(self, dev):
+        if self._state_dev != dev:
+            n = self.model.flat_params().numel()
+            self.grads = torch.zeros(n + 2, dtype=torch.float32, device=dev)
+            if self._state_dev is not None:   # change_device in the middle of a mission: the Adam moments move with the model
+                self.m, self.v = self.m.to(dev), self.v.to(dev)
+            else:
+                self.m = torch.zeros(n, dtype=torch.float32, device=dev)
+                self.v = torch.zeros(n, dtype=torch.float32, device=dev)
+            if self._state_dev is not None:   # (the confidence statistic's memory moves too)
+                self.conf_state = self.conf_state.to(dev)
+            else:
+                self.conf_state = self._initial_conf_state(dev)
+            self.minmax = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.stats = torch.zeros(4, dtype=torch.float64, device=dev)
+            self.losses = torch.zeros(5, dtype=torch.float32, device=dev)
+            self.sync_word = torch.zeros(1, dtype=torch.int32, device=dev)   # arrival counter of the fused forward (zero between steps)
+            self._state_dev = dev
 
     @torch.no_grad()
     def train_step(self, x: torch.Tensor, y: torch.Tensor, y_valid: torch.Tensor,

@@ -8,8 +8,9 @@ constructor (10 reference arguments), ``train() -> dict``, ``make_batch``, ``add
 small all-reduces keep the replicas identical.
 
 ``anomaly_detection=True`` (LinearRnvp + AnomalyLoss, traversability_estimator.py:83-96): the model's forward flow is a HIP kernel
-at inference; a training step is at most 8 nodes x 100 labelled segment rows and runs on autograd over the model's torch
-statement with ``torch.optim.Adam``, on one rank.
+at inference, and on a GPU device a training step (at most 8 nodes x 100 labelled segment rows) runs in the fused HIP phases of
+rnvp_trainer.py, data-parallel like the MLP step.  On ``device="cpu"`` it runs on autograd over the model's torch statement with
+``torch.optim.Adam``, on one rank.
 """
 import os
 from threading import Lock
@@ -22,6 +23,7 @@ from ..utils import AnomalyLoss, Batch, TraversabilityLoss
 from .. import ops
 from .graphs import BaseGraph, DistanceWindowGraph, MaxElementsGraph
 from .nodes import MissionNode, SupervisionNode
+from .rnvp_trainer import RnvpTrainer
 from .trainer import MlpTrainer
 
 
@@ -63,13 +65,20 @@ class TraversabilityEstimator:
         self._loss = torch.tensor([torch.inf])
         self._step = 0
         if anomaly_detection:
-            if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-                raise ValueError("anomaly_detection=True trains on one rank (the autograd step has no gradient all-reduce)")
+            # a GPU device trains on the fused HIP step (RnvpTrainer: data-parallel like MlpTrainer); the CPU keeps autograd
+            fused = self._device.type == "cuda"
+            if not fused and torch.distributed.is_available() and torch.distributed.is_initialized() \
+                    and torch.distributed.get_world_size() > 1:
+                raise ValueError("anomaly_detection=True on the CPU trains on one rank (the autograd step has no gradient all-reduce)")
             la = _get(params, "loss_anomaly")
             self._traversability_loss = AnomalyLoss(
                 **{k: _get(la, k) for k in la}, log_enabled=_get(gen, "log_confidence"),
                 log_folder=_get(gen, "model_path") or "/tmp").to(self._device)
-            self._optimizer = torch.optim.Adam(self._model.parameters(), lr=_get(_get(params, "optimizer"), "lr"))
+            self._cg_version = None
+            if fused:
+                self._optimizer = RnvpTrainer(self._model, lr=_get(_get(params, "optimizer"), "lr"), method=_get(la, "method"))
+            else:
+                self._optimizer = torch.optim.Adam(self._model.parameters(), lr=_get(_get(params, "optimizer"), "lr"))
             return
         self._traversability_loss = TraversabilityLoss(
             w_trav=_get(loss_cfg, "w_trav"), w_reco=_get(loss_cfg, "w_reco"), w_temp=_get(loss_cfg, "w_temp"),
@@ -107,6 +116,8 @@ class TraversabilityEstimator:
         self._mission_graph.change_device(device)
         self._model = self._model.to(device)
         self._traversability_loss = self._traversability_loss.to(device)
+        if isinstance(self._optimizer, RnvpTrainer):
+            self._optimizer.to(self._device)
 
     def update_visualization_node(self):
         """traversability_estimator.py:153-163."""
@@ -252,6 +263,8 @@ class TraversabilityEstimator:
         """traversability_estimator.py:464-495 in the anomaly-detection mode: forward (the model's torch statement), AnomalyLoss,
         backward, ``torch.optim.Adam`` step."""
         log_step = (self._step % 20) == 0
+        if isinstance(self._optimizer, RnvpTrainer):
+            return self._train_anomaly_fused(graph, return_dict, log_step)
         with self._learning_lock:
             graph.x = graph.x.to(self._device)
             res = self._model(graph)
@@ -266,6 +279,25 @@ class TraversabilityEstimator:
         self._step += 1
         return_dict["loss_total"] = total
         return_dict["loss_trav"], return_dict["loss_reco"] = loss_aux["loss_trav"].item(), loss_aux["loss_reco"].item()
+        return return_dict
+
+    def _train_anomaly_fused(self, graph, return_dict, log_step):
+        """The same step on the HIP phases (RnvpTrainer): loss, gradient, Adam and the confidence statistic on the device; the
+        AnomalyLoss module's ConfidenceGenerator is refreshed from the device state; one host read."""
+        cg = self._traversability_loss._confidence_generator
+        tr = self._optimizer
+        with self._learning_lock:
+            if self._cg_version != cg._version:   # constructed, loaded, reset or updated on the host since the last step
+                tr.load_confidence_state(cg)
+                self._cg_version = cg._version
+            losses = tr.train_step(graph.x.to(self._device))
+            tr.store_confidence_state(cg)
+            self._loss = losses[0:1]
+        total = losses[0].item()   # the one host read of the step
+        if log_step:
+            print(f"step: {self._step} | loss: {total:5f} | loss_trav: {0.0:5f} | loss_reco: {0.0:5f}")
+        self._step += 1
+        return_dict["loss_total"], return_dict["loss_trav"], return_dict["loss_reco"] = total, 0.0, 0.0
         return return_dict
 
     def train_on_batch(self, x: torch.Tensor, y: torch.Tensor, y_valid: torch.Tensor) -> torch.Tensor:
@@ -295,7 +327,7 @@ class TraversabilityEstimator:
             torch.save({
                 "step": self._step,
                 "model_state_dict": self._model.state_dict(),
-                "optimizer_state_dict": (self._optimizer.state_dict() if self._anomaly_detection
+                "optimizer_state_dict": (self._optimizer.state_dict() if isinstance(self._optimizer, torch.optim.Optimizer)
                                          else self._optimizer.optimizer_state_dict()),
                 "traversability_loss_state_dict": self._traversability_loss.state_dict(),
                 "loss": self.loss,
@@ -308,7 +340,7 @@ class TraversabilityEstimator:
             self._pause_training = True
             ck = torch.load(checkpoint_path, map_location=self._device, weights_only=False)
             self._model.load_state_dict(ck["model_state_dict"])
-            if self._anomaly_detection:
+            if isinstance(self._optimizer, torch.optim.Optimizer):
                 self._optimizer.load_state_dict(ck["optimizer_state_dict"])
             else:
                 self._optimizer.load_optimizer_state_dict(ck["optimizer_state_dict"])
