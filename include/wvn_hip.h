@@ -405,6 +405,31 @@ int wvn_random_pixels(unsigned seed, unsigned frame0, int B, int H, int W, int n
  * WVN_ERR_ARG: null pointer, B < 1, B > 65535, G < 1, H < 1, H > 32768, D < 1, nr < 1. */
 int wvn_gather_bilinear(const float* tokens, const int* idx, float* feat, int B, int G, int H, int D, int nr, void* stream);
 
+/* feature_type "sift" (feature_extractor.py:65-67, 276-286 of the reference: kornia's DenseSIFTDescriptor per colour channel, 8 + 1
+ * convolutions, then the per-segment means of the [1, 128 C, H, W] map), csrc/dense_sift.hip.  fp32.  The definition the kernels are
+ * held to (tests/dense_sift_ref.py states it in float64; PARITY WITH THE kornia PACKAGE ITSELF IS UNPINNED, the package is absent), for
+ * one channel I [H][W] in [0, 1], eps = 1e-10:
+ *   1. gx[y][x] = (I[y][x+1] - I[y][x-1]) / 2, gy[y][x] = (I[y+1][x] - I[y-1][x]) / 2, replicate padding by one pixel;
+ *   2. mag = sqrt(gx^2 + gy^2 + eps), ori = atan2(gy, gx + eps) + 2 pi, o = 8 ori / (2 pi), b0 = floor(o) mod 8, b1 = (b0 + 1) mod 8,
+ *      w1 = o - floor(o); plane P_a = [b0 = a] (1 - w1) mag + [b1 = a] w1 mag, a = 0..7;
+ *   3. Q_a [H+1][W+1]: Q_a[p][q] = sum_{i,j=0..3} k[i] k[j] P_a[p-2+i][q-2+j], k = [0.25, 0.75, 0.75, 0.25], terms outside the image 0;
+ *   4. d[a*16 + i*4 + j][y][x] = Q_a[y-1+i][x-1+j], i, j = 0..3, terms outside Q 0;
+ *   5. per pixel over the 128 values: d /= max(|d|_2, 1e-12); d = clamp(d, 0, 0.2); d /= max(|d|_2, 1e-12); d = sqrt(d / max(|d|_1, 1e-12) + eps).
+ * img [B][C][H][W] fp32, or uint8 (img_is_u8: x / 255 in fp32, fused into the load); C = 1 or 3; no resize, crop or normalisation.
+ * wvn_dense_sift: out [B][128 C][H][W] fp32, channel c of the frame in out[b][128 c .. 128 c + 127].
+ * wvn_dense_sift_segpool: feat [B][S][128 C] fp32 = the per-segment means of that map over seg [B][H][W] int32, WITHOUT writing the map,
+ *   from the same per-pixel arithmetic: feat = float(double(sum trunc(v 2^32)) / (double(count) 2^32)) (64-bit integer sums: no
+ *   dependence on the order of the atomics; v <= 1, so the product is exact).  Ids outside [0, S) (-1 included) are ignored, an id without
+ *   a pixel gives a NaN row, a tile without a labelled pixel costs a read of its labels.  cnt [B][S] int32 out (pixels per id);
+ *   scratch_sum: B * S * 128 C 8-byte words.  Both are cleared by the call.
+ * WVN_ERR_ARG before any launch: null pointer, B < 1, B * C > 65535, C not 1 or 3, H or W < 4 or > WVN_DENSE_SIFT_MAX_SIDE, S < 1,
+ * S > WVN_DENSE_SIFT_MAX_SEGMENTS, B * S * 128 C >= 2^31. */
+#define WVN_DENSE_SIFT_MAX_SIDE 16384
+#define WVN_DENSE_SIFT_MAX_SEGMENTS (1 << 20)
+int wvn_dense_sift(const void* img, int img_is_u8, float* out, int B, int C, int H, int W, void* stream);
+int wvn_dense_sift_segpool(const void* img, int img_is_u8, const int* seg, float* feat, int* cnt, void* scratch_sum, int B, int C,
+                           int H, int W, int S, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Supervision masks: ImageProjector.project_and_render (image_projector.py:126-197: pinhole projection +
  * kornia draw_convex_polygon) fused with the torch.fmin merge of traversability_estimator.py:281-286, for n mission nodes in

@@ -161,6 +161,8 @@ _SIGNATURES = {
     "wvn_label_pool_batched": ([_p, _i, _i, _i, _i, _i, _p, _p, _p], _i),
     "wvn_random_pixels": ([C.c_uint, C.c_uint, _i, _i, _i, _i, _p, _p, _p], _i),
     "wvn_gather_bilinear": ([_p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
+    "wvn_dense_sift": ([_p, _i, _p, _i, _i, _i, _i, _p], _i),
+    "wvn_dense_sift_segpool": ([_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "wvn_project_render_fmin": ([_p, _i, _p, _i, _i, _i, _i, _i, _p, _f, _p], _i),
     "wvn_wire_bytes": ([_i, _i, _i, _i], _sz),
     "wvn_wire_pack": ([_p, _i, _p, _i, _p, _i, _i, _i, _i, _p], _i),

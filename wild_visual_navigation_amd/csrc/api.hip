@@ -399,6 +399,13 @@ int wvn_slic_connectivity(const int* labels_in, int* labels_out, int B, int H, i
                           size_t scratch_bytes, void* stream) {
   return wvn_slic_connectivity_launch(labels_in, labels_out, B, H, W, K, min_size, scratch, scratch_bytes, (hipStream_t)stream);
 }
+int wvn_dense_sift(const void* img, int img_is_u8, float* out, int B, int C, int H, int W, void* stream) {
+  return wvn_dense_sift_launch(img, img_is_u8, out, B, C, H, W, (hipStream_t)stream);
+}
+int wvn_dense_sift_segpool(const void* img, int img_is_u8, const int* seg, float* feat, int* cnt, void* scratch_sum, int B, int C,
+                           int H, int W, int S, void* stream) {
+  return wvn_dense_sift_segpool_launch(img, img_is_u8, seg, feat, cnt, scratch_sum, B, C, H, W, S, (hipStream_t)stream);
+}
 int wvn_seg_centers(const int* seg, float* centers, void* scratch, int H, int W, int S, void* stream) {
   return wvn_centers_launch(seg, centers, (unsigned long long*)scratch, H, W, S, (hipStream_t)stream);
 }

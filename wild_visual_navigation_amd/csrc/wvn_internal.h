@@ -397,6 +397,11 @@ size_t wvn_slic_connectivity_scratch_bytes_impl(int B, int H, int W, int K);
 int wvn_slic_connectivity_launch(const int* labels_in, int* labels_out, int B, int H, int W, int K, int min_size, void* scratch,
                                  size_t scratch_bytes, hipStream_t st);
 
+// dense SIFT features and their fused per-segment means (dense_sift.hip)
+int wvn_dense_sift_launch(const void* img, int img_is_u8, float* out, int B, int C, int H, int W, hipStream_t st);
+int wvn_dense_sift_segpool_launch(const void* img, int img_is_u8, const int* seg, float* feat, int* cnt, void* scratch_sum, int B, int C,
+                                  int H, int W, int S, hipStream_t st);
+
 // ---- A -> B wire format (wire.hip) ---------------------------------------------------------------------------------------
 size_t wvn_wire_bytes_impl(int H, int W, int S, int D);
 int wvn_wire_pack_launch(const void* seg, int seg_is_i64, const float* feat, int ldf, void* out, int H, int W, int S, int D,

@@ -60,10 +60,15 @@ class FeatureExtractor:
                 pos_embed_rule=kwargs.get("pos_embed_rule", "dino"),
             )
             self._feature_dim = self._extractor.feature_dim
+        elif self._feature_type == "sift":
+            # dense SIFT (csrc/dense_sift.hip): no backbone, no weights.  The reference sets 128 here (feature_extractor.py:65-67) but its
+            # compute_sift concatenates the three colour channels' 128-d maps (:276-286): 384 is the width the features really have
+            self._feature_dim = 3 * ops.DENSE_SIFT_DIM
+            self._extractor = None
         elif self._feature_type == "none":
             self._extractor = None
         else:
-            # sift / torchvision / histogram ablation extractors are outside the MI355X hot path
+            # torchvision / histogram ablation extractors are outside the MI355X hot path
             raise TypeError(f"Extractor[{self._feature_type}] not supported!")
 
         if self.segmentation_type == "slic":
@@ -106,6 +111,8 @@ class FeatureExtractor:
         Returns (edges [2,E] i64, feat [S,D] f32, seg [H,W] i64, center [S,2] f32, dense [1,D,H,H] | None)."""
         img = img.to(self._device)
         want_dense = kwargs.get("return_dense_features", False)
+        if self._feature_type == "sift":
+            return self._extract_sift(img, want_dense, **kwargs)
         if self._segmentation_type == "random":
             tokens = self._feature_tokens(img)
             H, W = img.shape[2:]
@@ -132,10 +139,56 @@ class FeatureExtractor:
         patch-resolution feature tokens [B, G*G, D].  Everything after it (clustering, pooling, the MLP step) consists of
         small kernels that do not fill the GPU; a throughput pipeline runs this stage for batch i+1 on one HIP stream while
         the rest of batch i runs on another (``extract_batch(img, backbone_out=...)``, bench.py)."""
+        self._refuse_sift("backbone_stage")
         img = img.to(self._device)
         if self._feature_type == "stego":
             return self._extractor.code_tokens(img)
         return self._extractor.inference_tokens(img)
+
+    def _refuse_sift(self, who):
+        """Dense SIFT has no patch tokens: the per-pixel kernels interpolate patch-resolution features through a window of at most
+        4 x 4 tokens (csrc/pixel_mlp.hip), and a pixel-resolution map does not fit that scheme.  Refused before any GPU work."""
+        if self._feature_type == "sift":
+            raise _lib.WvnError(f"{who}: feature_type 'sift' has no patch-token stage (its features are computed at pixel resolution); "
+                                f"use predict_per_segment")
+
+    def _extract_sift(self, img, want_dense, **kwargs):
+        """``extract`` for feature_type "sift": the segment map as for every other feature type, feat from the fused descriptor +
+        segment-mean kernel (the [1,384,H,W] map is built only on request)."""
+        if self._segmentation_type == "random":
+            edges, center = None, None
+            seg = self.segment_random(img, **kwargs)[0, 0]
+            n_seg = kwargs.get("n_random_pixels", 100)
+        else:
+            edges, seg, center = self.compute_segments(img, **kwargs)
+            n_seg = center.shape[0]
+        feat = ops.dense_sift_segpool(img, seg[None], n_seg)[0]
+        return edges, feat, seg, center, (ops.dense_sift(img) if want_dense else None)
+
+    def _extract_batch_sift(self, img, **kwargs):
+        """``extract_batch`` for feature_type "sift" (grid, slic or random segmentation; H x W frames): the same segment maps as for
+        the ViT features, feat [B,S,384] from ops.dense_sift_segpool.  Random: the -1 / id map of ops.random_pixels goes through the
+        same kernel, which skips every tile without a sample."""
+        B, _, H, W = img.shape
+        if self._segmentation_type == "grid":
+            cell = kwargs.get("cell_size", 32)
+            seg = self.segment_grid(img, **kwargs)[0, 0].to(torch.int32)[None].expand(B, H, W).contiguous()
+            n_seg = (H // cell) * (W // cell)
+        elif self._segmentation_type == "slic":
+            seg = ops.slic(img, self._slic_num_components, self._slic_compactness, enforce_connectivity=self._slic_enforce_connectivity,
+                           min_size_factor=self._slic_min_size_factor)
+            n_seg = ops.slic_num_clusters(H, W, self._slic_num_components)
+        elif self._segmentation_type == "random":
+            n_seg = kwargs.get("n_random_pixels", 100)
+            frame = kwargs.get("frame_index")
+            if frame is None:
+                frame = self._random_frame
+                self._random_frame = (frame + B) & 0xFFFFFFFF
+            _, seg = ops.random_pixels(B, H, W, n_seg, seed=self._random_seed, frame0=frame, device=self._device)
+        else:
+            raise TypeError(f"extract_batch: segmentation_type [{self._segmentation_type}] not supported with feature_type 'sift'")
+        feat = ops.dense_sift_segpool(img, seg, n_seg)
+        return feat, seg, torch.full((B,), n_seg, dtype=torch.int32, device=self._device)
 
     @torch.no_grad()
     def extract_batch(self, img: torch.Tensor, backbone_out: Optional[torch.Tensor] = None,
@@ -148,8 +201,14 @@ class FeatureExtractor:
         id j, feat[b, j] is the interpolated feature at that pixel (ops.random_pixels, ops.gather_bilinear: no permutation of the frame, no
         pooling pass, no host synchronisation; the single-frame ``extract`` keeps its torch.randperm draw).  SLIC with ``slic_enforce_connectivity=True`` adds one batched
         connectivity pass over the B maps (ops.slic_enforce_connectivity: fragments below slic_min_size_factor of a superpixel go to a
-        neighbour; ids stay cluster ids, emptied ids give NaN rows); the pass has no host synchronisation.  ``backbone_out``: the tokens ``backbone_stage(img)`` returned."""
+        neighbour; ids stay cluster ids, emptied ids give NaN rows); the pass has no host synchronisation.  ``backbone_out``: the tokens ``backbone_stage(img)`` returned.
+        feature_type "sift": grid, slic or random segmentation on H x W frames, feat [B,S,384] from the fused descriptor + segment-mean kernel
+        (``_extract_batch_sift``); there is no backbone stage, so ``backbone_out`` is refused."""
         img = img.to(self._device)
+        if self._feature_type == "sift":
+            if backbone_out is not None:
+                self._refuse_sift("extract_batch(backbone_out=...)")
+            return self._extract_batch_sift(img, **kwargs)
         B, _, H, W = img.shape
         G = self._grid()
         labels_patch = None  # [B,G,G] ids when the segment map is constant on every ViT patch
@@ -212,6 +271,7 @@ class FeatureExtractor:
         kernel (fp16 tokens are rounded to bf16 once), fp32 (exact) extractor -> the hi + lo split form (<= 1e-3 of the reference).
         ``model.input_size`` must equal the extractor's ``feature_dim`` (WvnError otherwise).  Like the reference
         (dino_interface.py:87-90) the map is H x H for an H x W frame."""
+        self._refuse_sift("predict_per_pixel")
         img = img.to(self._device)
         self._check_per_pixel_model(model, "predict_per_pixel")
         rows, _ = self._per_pixel_tokens(img, model)
@@ -226,6 +286,7 @@ class FeatureExtractor:
         ViT run (for stego features with flip TTA: of the one paired run, and its one STEGO head) feed both.  grid, slic, stego or random
         segmentation; dino, dinov2 or stego features; every precision.  SimpleMLP or LinearRnvp (trav = conf = confidence(-score), third map
         -score), anything else is refused before the backbone runs."""
+        self._refuse_sift("predict_and_extract")
         img = img.to(self._device)
         self._check_per_pixel_model(model, "predict_and_extract")
         rows, tokens = self._per_pixel_tokens(img, model)
@@ -390,6 +451,8 @@ class FeatureExtractor:
         """feature_extractor.py:251-274: dense per-pixel features [B,D,H,H] (materialised on request only)."""
         if self._feature_type == "none":
             return None
+        if self._feature_type == "sift":   # feature_extractor.py:276-286: [B,384,H,W], the frame as it is (no resize, crop or normalisation)
+            return ops.dense_sift(img.to(self._device))
         if self._feature_type == "stego":
             if self._stego_features_already_computed_in_segmentation:
                 self._stego_features_already_computed_in_segmentation = False

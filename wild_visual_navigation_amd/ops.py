@@ -58,6 +58,49 @@ def gather_bilinear(tokens: torch.Tensor, idx: torch.Tensor, grid: int, out_size
     return feat
 
 
+DENSE_SIFT_DIM = 128              # descriptor length per image channel (8 angular x 4 x 4 spatial bins)
+
+
+def _sift_frames(img: torch.Tensor, who: str) -> torch.Tensor:
+    require_cuda(img, "img")
+    if img.dim() != 4 or img.shape[1] not in (1, 3) or img.shape[2] < 4 or img.shape[3] < 4:
+        raise _lib.WvnError(f"{who}: img must be [B,C,H,W] with C in (1, 3) and H, W >= 4, not {tuple(img.shape)}")
+    return img.contiguous() if img.dtype == torch.uint8 else img.contiguous().float()
+
+
+def dense_sift(img: torch.Tensor) -> torch.Tensor:
+    """Dense SIFT descriptors (feature_type "sift"; feature_extractor.py:276-286 of the reference): img [B,C,H,W] fp32 in [0,1] or
+    uint8 (x / 255 fused into the load), C in (1, 3), any H, W >= 4 -> [B, 128 C, H, W] fp32, channel c of the frame in columns
+    [128 c, 128 c + 128).  The definition: include/wvn_hip.h, tests/dense_sift_ref.py."""
+    img = _sift_frames(img, "dense_sift")
+    B, Cc, H, W = img.shape
+    out = torch.empty(B, DENSE_SIFT_DIM * Cc, H, W, dtype=torch.float32, device=img.device)
+    check(lib().wvn_dense_sift(ptr(img), int(img.dtype == torch.uint8), ptr(out), B, Cc, H, W, stream()), "wvn_dense_sift")
+    return out
+
+
+def dense_sift_segpool(img: torch.Tensor, seg: torch.Tensor, n_seg: int, return_counts: bool = False):
+    """Per-segment means of ``dense_sift(img)`` without the dense map: img [B,C,H,W], seg [B,H,W] int (ids outside [0, n_seg), -1
+    included, are ignored) -> feat [B, n_seg, 128 C] fp32, NaN row for an id without a pixel.  feat is
+    float32(sum trunc(dense * 2^32) / (count * 2^32)) over the very bits ``dense_sift`` returns, summed in 64-bit integers: the same
+    result whatever the order of the atomics.  ``return_counts``: also the pixels per id, [B, n_seg] int32."""
+    img = _sift_frames(img, "dense_sift_segpool")
+    require_cuda(seg, "seg")
+    B, Cc, H, W = img.shape
+    if tuple(seg.shape) != (B, H, W):
+        raise _lib.WvnError(f"dense_sift_segpool: seg must be [B,H,W] = {(B, H, W)}, not {tuple(seg.shape)}")
+    if n_seg < 1:
+        raise _lib.WvnError(f"dense_sift_segpool: n_seg={n_seg} must be >= 1")
+    seg = _i32(seg).contiguous()
+    D = DENSE_SIFT_DIM * Cc
+    feat = torch.empty(B, n_seg, D, dtype=torch.float32, device=img.device)
+    cnt = torch.empty(B, n_seg, dtype=torch.int32, device=img.device)
+    ssum = torch.empty(B * n_seg * D, dtype=torch.int64, device=img.device)   # 2^-32 fixed-point sums (cleared by the call)
+    check(lib().wvn_dense_sift_segpool(ptr(img), int(img.dtype == torch.uint8), ptr(seg), ptr(feat), ptr(cnt), ptr(ssum), B, Cc, H, W,
+                                       int(n_seg), stream()), "wvn_dense_sift_segpool")
+    return (feat, cnt) if return_counts else feat
+
+
 def upsample_nearest_labels(labels: torch.Tensor, out_size: int) -> torch.Tensor:
     """labels [B,G,G] int32 -> [B,H,H] int32 (stego_interface.py:108-109)."""
     require_cuda(labels, "labels")
