@@ -821,6 +821,46 @@ int wvn_segment_predict(const wvn_mlp_desc* d, const float* params, const float*
                         size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * SimpleGCN (model/simple_gcn.py, csrc/simple_gcn.hip): three graph-convolution layers D -> H1 (ReLU) -> H2 (ReLU) -> 1 + D
+ * (sigmoid on column 0), each one GCNConv with torch_geometric's defaults: edges with source == target dropped, one self loop
+ * per node added, deg_i = edges into i, out_i = sum_{e: j -> i} deg_j^-1/2 deg_i^-1/2 (x_j W^T) + b.  The edge list is used as
+ * given (not symmetrised, duplicates kept).  desc: D, H1, H2 with reserved = 0; the flat parameter layout [W1|b1|W2|b2|W3|b3] and
+ * wvn_mlp_param_count are SimpleMLP's for the same (D, H1, H2).  Limits: 1 <= D <= 1024, 1 <= H1, H2 <= 256, nodes <= 2^26,
+ * capacity <= 2^30 (WVN_ERR_ARG otherwise, checked on the host before any GPU call; the workspace query returns 0).
+ *
+ * A call sequence shares ONE workspace and the same (nodes, capacity): a graph preparation, then any number of forwards on it.
+ *   capacity : neighbour entries the workspace holds, >= E + nodes for an edge list, >= B * S * S for bitmaps.
+ *   wvn_gcn_graph_from_edges   : edge_index int64, element (row, e) at edge_index[row * ld_row + e * ld_edge], row 0 = source,
+ *                                row 1 = target.  An edge with an endpoint outside [0, nodes) is dropped, never dereferenced, and
+ *                                counted in *bad_edges (device int32, reset by the call).  No host reads; 4 launches.
+ *   wvn_gcn_graph_from_bitmaps : adj uint8, element (b, l, r) at adj[b * ld_b + l * ld_l + r * ld_r], nonzero = an edge from node
+ *                                b * S + l to node b * S + r (ops.seg_adjacency_batched); the diagonal is ignored.  bad_edges
+ *                                (may be NULL) is reset.  3 launches.
+ *   Both leave the target-major form {row pointers, sources in ASCENDING order with the self loop among them, coefficients}.
+ *   wvn_gcn_forward            : x [nodes][ldx >= D] -> out [nodes][1 + D]; 3 launches, one per layer.
+ *   wvn_gcn_segment_predict    : wvn_segment_predict for this model on feat [B * S][ld_row] (node b * S + s): the last layer forms
+ *                                the row's reconstruction loss and confidence and fills the {trav, conf, loss_reco, 0} table, the
+ *                                paint kernel of segment_predict.hip spreads it (same seg id rule); 3 + 1 launches.
+ * fp32 FMA throughout, no floating-point atomics: every sum has one fixed ascending order, so a row's results do not depend on
+ * the edge order, the row's position or the batch around it, and a NaN row reaches only the rows within three hops.
+ * ------------------------------------------------------------------------------------------- */
+size_t wvn_gcn_workspace_bytes(const wvn_mlp_desc* d, int nodes, long long capacity);
+int wvn_gcn_graph_from_edges(const long long* edge_index, long long ld_row, long long ld_edge, int E, int nodes, long long capacity,
+                             int* bad_edges, void* workspace, size_t workspace_bytes, void* stream);
+int wvn_gcn_graph_from_bitmaps(const unsigned char* adj, long long ld_b, long long ld_l, long long ld_r, int B, int S, long long capacity,
+                               int* bad_edges, void* workspace, size_t workspace_bytes, void* stream);
+int wvn_gcn_forward(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, int nodes, long long capacity, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int wvn_gcn_segment_predict(const wvn_mlp_desc* d, const float* params, const float* feat, int ld_row, int B, int S, long long capacity,
+                            const void* seg, int seg_bytes, int H, int W, float mean, float std, float std_factor,
+                            const float* conf_state, float* trav, float* conf, float* loss_reco, void* workspace, size_t workspace_bytes,
+                            void* stream);
+/* wvn_seg_adjacency's bitmap for a batch of frames, without the edge list: adj [B][S][S] uint8, adj[b][r * S + l] = 1 exactly for
+ * the (left l, right r) pairs wvn_seg_adjacency returns for frame b (its transposed view is wvn_gcn_graph_from_bitmaps' (b, l, r)
+ * element).  No host synchronisation. */
+int wvn_seg_adjacency_batched(const int* seg, unsigned char* adj, int B, int H, int W, int S, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * A -> B wire format: the per-frame wild_visual_navigation_msgs/ImageFeatures message built at
  * wvn_feature_extractor_node.py:373-393 (seg.cpu().numpy().astype(np.int32) + feat.cpu().numpy().flatten().tolist()) and
  * decoded at wvn_learning_node.py:651-656.  wvn_wire_pack lays the frame out on the device as the message carries it:

@@ -228,6 +228,12 @@ _SIGNATURES = {
     "wvn_rnvp_train_phase_c": ([_p, _p, _p, _p, _p, _i, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p], _i),
     "wvn_segment_predict_workspace_bytes": ([_p, _i, _i], _sz),
     "wvn_segment_predict": ([_p, _p, _p, _i, _ll, _i, _i, _p, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
+    "wvn_gcn_workspace_bytes": ([_p, _i, _ll], _sz),
+    "wvn_gcn_graph_from_edges": ([_p, _ll, _ll, _i, _i, _ll, _p, _p, _sz, _p], _i),
+    "wvn_gcn_graph_from_bitmaps": ([_p, _ll, _ll, _ll, _i, _i, _ll, _p, _p, _sz, _p], _i),
+    "wvn_gcn_forward": ([_p, _p, _p, _i, _i, _ll, _p, _p, _sz, _p], _i),
+    "wvn_gcn_segment_predict": ([_p, _p, _p, _i, _i, _i, _ll, _p, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
+    "wvn_seg_adjacency_batched": ([_p, _p, _i, _i, _i, _i, _p], _i),
     "wvn_debug_gemm_bf16_timed": ([_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p], _i),
     "wvn_debug_f16_saturate": ([_p, _p, _i, _p], _i),
     "wvn_debug_attention_timing": ([_p], _i),

@@ -64,10 +64,12 @@ class DoubleMlpCfgParams(_Node):
 
 
 @dataclass
-class OtherModelCfgParams(_Node):
-    """Config slot of the model outside this build (SimpleGCN, experiment_params.py:123-129): callers write
-    ``input_size`` into all four slots unconditionally (quick_start.py:131-134); the model itself is outside this build."""
+class SimpleGcnCfgParams(_Node):
+    """SimpleGCN (experiment_params.py:123-129; model/simple_gcn.py).  Callers write ``input_size`` into all four slots
+    unconditionally (quick_start.py:131-134)."""
     input_size: int = 384
+    reconstruction: bool = True
+    hidden_sizes: List[int] = field(default_factory=lambda: [256, 128, 1])
 
 
 @dataclass
@@ -86,7 +88,7 @@ class ModelParams(_Node):
     load_ckpt: Optional[str] = None
     simple_mlp_cfg: SimpleMlpCfgParams = field(default_factory=SimpleMlpCfgParams)
     double_mlp_cfg: DoubleMlpCfgParams = field(default_factory=DoubleMlpCfgParams)
-    simple_gcn_cfg: OtherModelCfgParams = field(default_factory=OtherModelCfgParams)
+    simple_gcn_cfg: SimpleGcnCfgParams = field(default_factory=SimpleGcnCfgParams)
     linear_rnvp_cfg: LinearRnvpCfgParams = field(default_factory=LinearRnvpCfgParams)
 
 

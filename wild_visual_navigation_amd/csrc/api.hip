@@ -413,6 +413,9 @@ int wvn_seg_adjacency(const int* seg, long long* edges, int* count, unsigned cha
                       int max_edges, void* stream) {
   return wvn_adjacency_launch(seg, edges, count, scratch_bitmap, H, W, S, max_edges, (hipStream_t)stream);
 }
+int wvn_seg_adjacency_batched(const int* seg, unsigned char* adj, int B, int H, int W, int S, void* stream) {
+  return wvn_adjacency_batched_launch(seg, adj, B, H, W, S, (hipStream_t)stream);
+}
 int wvn_normalize_rows(const float* code, int ldc, float* xn, int rows, int C, void* stream) {
   return wvn_normalize_rows_launch(code, ldc, xn, rows, C, (hipStream_t)stream);
 }
@@ -901,6 +904,55 @@ int wvn_segment_predict(const wvn_mlp_desc* d, const float* params, const float*
   }
   return wvn_segment_predict_launch(d->D, params, feat, ld_row, ld_frame, B, S, seg, seg_bytes, H, W, mean, std, std_factor,
                                     conf_state, trav, conf, loss_reco, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// SimpleGCN (simple_gcn.hip).  Every check is host arithmetic: a refused call touches no GPU state
+namespace {
+bool gcn_ok(const wvn_mlp_desc* d) { return d && d->reserved == 0 && wvn_gcn_supported(d->D, d->H1, d->H2); }
+bool gcn_size_ok(long long nodes, long long capacity) { return nodes >= 1 && nodes <= (1ll << 26) && capacity >= nodes && capacity <= (1ll << 30); }
+}  // namespace
+size_t wvn_gcn_workspace_bytes(const wvn_mlp_desc* d, int nodes, long long capacity) {
+  if (!gcn_ok(d) || !gcn_size_ok(nodes, capacity)) return 0;
+  return wvn_gcn_workspace_bytes_impl(d->H1, d->H2, nodes, capacity);
+}
+int wvn_gcn_graph_from_edges(const long long* edge_index, long long ld_row, long long ld_edge, int E, int nodes, long long capacity,
+                             int* bad_edges, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!bad_edges || !workspace || E < 0 || (E > 0 && !edge_index) || !gcn_size_ok(nodes, capacity)) return WVN_ERR_ARG;
+  if (capacity < (long long)E + nodes) return WVN_ERR_ARG;
+  if (((uintptr_t)edge_index & 7) || ((uintptr_t)workspace & 15) || ((uintptr_t)bad_edges & 3)) return WVN_ERR_ARG;
+  if (workspace_bytes < wvn_gcn_workspace_bytes_impl(0, 0, nodes, capacity)) return WVN_ERR_WORKSPACE;
+  return wvn_gcn_graph_edges_launch(edge_index, ld_row, ld_edge, E, nodes, capacity, bad_edges, workspace, (hipStream_t)stream);
+}
+int wvn_gcn_graph_from_bitmaps(const unsigned char* adj, long long ld_b, long long ld_l, long long ld_r, int B, int S, long long capacity,
+                               int* bad_edges, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!adj || !workspace || B < 1 || S < 1 || ld_b < 0 || ld_l < 0 || ld_r < 0) return WVN_ERR_ARG;
+  if (!gcn_size_ok((long long)B * S, capacity) || capacity < (long long)B * S * S) return WVN_ERR_ARG;
+  if (((uintptr_t)workspace & 15) || ((uintptr_t)bad_edges & 3)) return WVN_ERR_ARG;
+  if (workspace_bytes < wvn_gcn_workspace_bytes_impl(0, 0, B * S, capacity)) return WVN_ERR_WORKSPACE;
+  return wvn_gcn_graph_bitmaps_launch(adj, ld_b, ld_l, ld_r, B, S, capacity, bad_edges, workspace, (hipStream_t)stream);
+}
+int wvn_gcn_forward(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, int nodes, long long capacity, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  if (!gcn_ok(d) || !params || !x || !out || !workspace || !gcn_size_ok(nodes, capacity) || ldx < d->D) return WVN_ERR_ARG;
+  if (((uintptr_t)workspace & 15) || (((uintptr_t)params | (uintptr_t)x | (uintptr_t)out) & 3)) return WVN_ERR_ARG;
+  if (workspace_bytes < wvn_gcn_workspace_bytes_impl(d->H1, d->H2, nodes, capacity)) return WVN_ERR_WORKSPACE;
+  return wvn_gcn_layers_launch(d->D, d->H1, d->H2, params, x, ldx, nodes, capacity, out, 1 + d->D, 0, 0.f, 1.f, 0.f, nullptr, workspace,
+                               (hipStream_t)stream);
+}
+int wvn_gcn_segment_predict(const wvn_mlp_desc* d, const float* params, const float* feat, int ld_row, int B, int S, long long capacity,
+                            const void* seg, int seg_bytes, int H, int W, float mean, float std, float std_factor,
+                            const float* conf_state, float* trav, float* conf, float* loss_reco, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  if (!gcn_ok(d) || !params || !feat || !seg || !workspace) return WVN_ERR_ARG;
+  if (B <= 0 || S <= 0 || H <= 0 || W <= 0 || B > 65535 || (long long)H * W > 0x7fffffffll) return WVN_ERR_ARG;
+  if (!gcn_size_ok((long long)B * S, capacity) || ld_row < d->D) return WVN_ERR_ARG;
+  if (seg_bytes != 4 && seg_bytes != 8) return WVN_ERR_ARG;
+  if (((uintptr_t)workspace & 15) || ((uintptr_t)seg & (seg_bytes - 1)) || (((uintptr_t)feat | (uintptr_t)params) & 3)) return WVN_ERR_ARG;
+  if (workspace_bytes < wvn_gcn_workspace_bytes_impl(d->H1, d->H2, B * S, capacity)) return WVN_ERR_WORKSPACE;
+  RET_IF(wvn_gcn_layers_launch(d->D, d->H1, d->H2, params, feat, ld_row, B * S, capacity, nullptr, 0, 1, mean, std, std_factor, conf_state,
+                               workspace, (hipStream_t)stream));
+  return wvn_segment_paint_launch(wvn_gcn_table(workspace, d->H1, d->H2, B * S, capacity), B, S, seg, seg_bytes, H, W, trav, conf,
+                                  loss_reco, (hipStream_t)stream);
 }
 
 int wvn_mlp_confidence(const float* out, int ldo, const float* x, int ldx, float mean, float std, float std_factor,

@@ -241,6 +241,8 @@ __global__ void adjacency_mark_kernel(const int* __restrict__ seg, unsigned char
                                       int S) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= H * Wd) return;
+  seg += (size_t)blockIdx.y * H * Wd;          // frame blockIdx.y of a batch (wvn_adjacency_batched_launch): its map, its bitmap
+  bitmap += (size_t)blockIdx.y * S * S;
   int y = i / Wd, x = i - y * Wd;
   int s = seg[i];
   if (x + 1 < Wd) {
@@ -502,6 +504,16 @@ int wvn_adjacency_launch(const int* seg, long long* edges, int* count, unsigned 
   hipLaunchKernelGGL(adjacency_mark_kernel, dim3(ceil_div(H * Wd, 256)), dim3(256), 0, st, seg, bitmap, H, Wd, S);
   WVN_LAUNCH_CHECK();
   hipLaunchKernelGGL(adjacency_compact_kernel, dim3(1), dim3(1024), 0, st, bitmap, edges, count, S, max_edges);
+  WVN_LAUNCH_CHECK();
+  return WVN_OK;
+}
+
+// the bitmaps alone, one per frame: [B][S][S], bitmap[b][r * S + l] = 1 for the (left l, right r) pairs of frame b
+int wvn_adjacency_batched_launch(const int* seg, unsigned char* bitmap, int B, int H, int Wd, int S, hipStream_t st) {
+  if (!seg || !bitmap || B < 1 || B > 65535 || H < 1 || Wd < 1 || S < 1 || (long long)H * Wd > 0x7fffffffll) return WVN_ERR_ARG;
+  hipError_t e = hipMemsetAsync(bitmap, 0, (size_t)B * S * S, st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(adjacency_mark_kernel, dim3(ceil_div(H * Wd, 256), B), dim3(256), 0, st, seg, bitmap, H, Wd, S);
   WVN_LAUNCH_CHECK();
   return WVN_OK;
 }

@@ -230,6 +230,7 @@ int wvn_centers_launch(const int* seg, float* centers, unsigned long long* scrat
                        hipStream_t st);
 int wvn_adjacency_launch(const int* seg, long long* edges, int* count, unsigned char* bitmap, int H, int Wd, int S,
                          int max_edges, hipStream_t st);
+int wvn_adjacency_batched_launch(const int* seg, unsigned char* bitmap, int B, int H, int Wd, int S, hipStream_t st);
 int wvn_normalize_rows_launch(const float* code, int ldc, float* xn, int rows, int C, hipStream_t st);
 int wvn_argmax_rows_launch(const float* x, int ld, int rows, int cols, int* out, hipStream_t st);
 size_t wvn_kmeans_scratch_floats(int B, int P, int C, int K);
@@ -384,6 +385,19 @@ int wvn_segment_predict_launch(int D, const float* params, const float* feat, in
 // the second half of the above on a table {trav, conf, loss, 0} [B*S][4] that another model's kernel has filled
 int wvn_segment_paint_launch(const float* table, int B, int S, const void* seg, int seg_bytes, int H, int W, float* trav, float* conf,
                              float* loss, hipStream_t st);
+
+// ---- SimpleGCN (simple_gcn.hip): graph preparation into the workspace, the three layer launches ---------------------------
+// cap: the neighbour entries the workspace holds (>= E + N for an edge list, >= B * S * S for bitmaps); the same N and cap in every call on a workspace
+bool wvn_gcn_supported(int D, int h1, int h2);
+size_t wvn_gcn_workspace_bytes_impl(int h1, int h2, int N, long long cap);
+int wvn_gcn_graph_edges_launch(const long long* ei, long long ld_row, long long ld_e, int E, int N, long long cap, int* bad, void* ws,
+                               hipStream_t st);
+int wvn_gcn_graph_bitmaps_launch(const unsigned char* adj, long long ld_b, long long ld_l, long long ld_r, int B, int S, long long cap,
+                                 int* bad, void* ws, hipStream_t st);
+// out (optional where want_table): [N][ldo]; want_table: the last layer also fills the {trav, conf, loss, 0} table (wvn_gcn_table)
+int wvn_gcn_layers_launch(int D, int h1, int h2, const float* params, const float* x, int ldx, int N, long long cap, float* out, int ldo,
+                          int want_table, float mean, float std, float std_factor, const float* conf_state, void* ws, hipStream_t st);
+const float* wvn_gcn_table(void* ws, int h1, int h2, int N, long long cap);
 
 // ---- supervision path (supervision.hip) and SLIC (slic.hip) -------------------------------------------------------------
 int wvn_project_render_fmin_launch(const void* nodes, int n, const float* points, int points_batched, int npts, int C, int H,

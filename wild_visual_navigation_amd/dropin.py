@@ -9,7 +9,7 @@ wvn_learning_node.py:7-24) bind the MI355X classes:
     from wild_visual_navigation import WVN_ROOT_DIR
     from wild_visual_navigation.feature_extractor import FeatureExtractor           (DinoInterface, StegoInterface, SegmentExtractor)
     from wild_visual_navigation.image_projector import ImageProjector
-    from wild_visual_navigation.model import get_model                              (SimpleMLP, DoubleMLP, LinearRnvp)
+    from wild_visual_navigation.model import get_model                              (SimpleMLP, DoubleMLP, LinearRnvp, SimpleGCN)
     from wild_visual_navigation.utils import ConfidenceGenerator, Data, Batch, TraversabilityLoss, AnomalyLoss, WVNMode, make_plane ...
     from wild_visual_navigation.traversability_estimator import TraversabilityEstimator, MissionNode, SupervisionNode, graphs
     from wild_visual_navigation.cfg import ExperimentParams

@@ -357,7 +357,14 @@ class FeatureExtractor:
         ``model.forward_per_segment(feat, seg)``: equivalent to ``feat[seg.reshape(-1)]`` -> ``model.forward`` -> column 0 /
         ``confidence_generator.inference_without_update(mse(pred[:, 1:], x))`` per frame, with the MLP run once per segment
         (csrc/segment_predict.hip).  ``feat`` / ``seg`` / ``nseg`` are extract_batch's, for the training messages of the same pass.
-        A confidence generator on the GPU is read from device memory: no host synchronisation beyond extract_batch's own."""
+        A confidence generator on the GPU is read from device memory: no host synchronisation beyond extract_batch's own.
+        A model that declares ``NEEDS_GRAPH`` (SimpleGCN) also gets the segment graph of every frame, as the adjacency bitmaps
+        ``ops.seg_adjacency_batched(seg, S)`` (grid, slic or stego segmentation; "random" samples have no graph and are refused
+        before the backbone runs)."""
+        graph = getattr(model, "NEEDS_GRAPH", False)
+        if graph and self._segmentation_type == "random":
+            raise _lib.WvnError(f"predict_per_segment: {type(model).__name__} needs the segment graph, and segmentation_type 'random' "
+                                f"has none; use grid, slic or stego segmentation")
         feat, seg, nseg = self.extract_batch(img, backbone_out=backbone_out, **kwargs)
         mean, std, f, conf_state = 0.0, 1.0, 0.5, None
         if confidence_generator is not None:
@@ -367,7 +374,8 @@ class FeatureExtractor:
                                         torch.full((1,), float(cg.std_factor), dtype=torch.float32, device=feat.device)])
             else:
                 mean, std, f = float(cg.mean), float(cg.std), float(cg.std_factor)
-        trav, conf, loss = model.forward_per_segment(feat, seg, mean, std, f, want_loss=want_loss, conf_state=conf_state)
+        extra = {"adjacency": ops.seg_adjacency_batched(seg, feat.shape[1])} if graph else {}
+        trav, conf, loss = model.forward_per_segment(feat, seg, mean, std, f, want_loss=want_loss, conf_state=conf_state, **extra)
         return trav, conf, loss, feat, seg, nseg
 
     def _grid(self) -> int:

@@ -1,13 +1,14 @@
-"""get_model -- wild_visual_navigation/model/network_register.py:44-55 (class-name registry; SimpleMLP, DoubleMLP and LinearRnvp are on
-the MI355X path)."""
+"""get_model -- wild_visual_navigation/model/network_register.py:44-55 (class-name registry; SimpleMLP, DoubleMLP, LinearRnvp and
+SimpleGCN are on the MI355X path)."""
 import inspect
 
 from .double_mlp import DoubleMLP
 from .linear_rnvp import LinearRnvp
+from .simple_gcn import SimpleGCN
 from .simple_mlp import SimpleMLP
 
 _REGISTER = {"SimpleMLP": (SimpleMLP, "simple_mlp_cfg"), "DoubleMLP": (DoubleMLP, "double_mlp_cfg"),
-             "LinearRnvp": (LinearRnvp, "linear_rnvp_cfg")}
+             "LinearRnvp": (LinearRnvp, "linear_rnvp_cfg"), "SimpleGCN": (SimpleGCN, "simple_gcn_cfg")}
 
 
 def _get(cfg, key):

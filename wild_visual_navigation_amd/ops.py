@@ -383,6 +383,20 @@ def seg_adjacency(seg: torch.Tensor, n_seg: int) -> torch.Tensor:
     return edges[: int(count.item())]  # the edge count fixes the output shape: one host sync, as in the reference
 
 
+def seg_adjacency_batched(seg: torch.Tensor, n_seg: int) -> torch.Tensor:
+    """seg [B,H,W] int32 -> adj [B,S,S] uint8 with adj[b, l, r] = 1 exactly for the (left, right) pairs ``seg_adjacency`` returns
+    for frame b: the bitmap that call compacts, for every frame at once, without the edge count and so without a host
+    synchronisation.  (The result is a transposed view: memory is target-major, [b][r][l].)"""
+    require_cuda(seg, "seg")
+    if seg.dim() != 3 or n_seg < 1:
+        raise _lib.WvnError(f"seg_adjacency_batched: seg [B,H,W] and n_seg >= 1 expected, got {tuple(seg.shape)} and {n_seg}")
+    seg = _i32(seg).contiguous()
+    B, H, W = seg.shape
+    adj = torch.empty(B, n_seg, n_seg, dtype=torch.uint8, device=seg.device)
+    check(lib().wvn_seg_adjacency_batched(ptr(seg), ptr(adj), B, H, W, n_seg, stream()), "wvn_seg_adjacency_batched")
+    return adj.transpose(1, 2)
+
+
 def kmeans_cosine(code: torch.Tensor, K: int, iters: int = 10, relabel: bool = True, return_centroids: bool = False):
     """code [B,P,C] fp32 (any row stride) -> (labels [B,P] int32, n_segments [B] int32[, final centroids [B,K,C]])."""
     require_cuda(code, "code")

@@ -11,6 +11,9 @@ small all-reduces keep the replicas identical.
 at inference, and on a GPU device a training step (at most 8 nodes x 100 labelled segment rows) runs in the fused HIP phases of
 rnvp_trainer.py, data-parallel like the MLP step.  On ``device="cpu"`` it runs on autograd over the model's torch statement with
 ``torch.optim.Adam``, on one rank.
+
+``params.model.name == "SimpleGCN"``: inference runs the model's HIP graph kernels; a training step runs the whole ``Batch`` through
+the model's torch statement, ``TraversabilityLoss``, backward and ``torch.optim.Adam`` on one rank (``_train_graph``).
 """
 import os
 from threading import Lock
@@ -86,11 +89,19 @@ class TraversabilityEstimator:
             confidence_std_factor=_get(loss_cfg, "confidence_std_factor"),
             trav_cross_entropy=_get(loss_cfg, "trav_cross_entropy"), log_enabled=_get(gen, "log_confidence"),
             log_folder=_get(gen, "model_path") or "/tmp").to(self._device)
+        self._cg_version = None   # the ConfidenceGenerator state version the trainer's device state was last loaded from
+        self._graph_model = getattr(self._model, "NEEDS_GRAPH", False)
+        if self._graph_model:
+            # SimpleGCN: the whole Batch goes through the model's torch statement, TraversabilityLoss, backward and torch.optim.Adam
+            # (a fused HIP training step for the graph model is the follow-up); the autograd step has no gradient all-reduce
+            if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                raise ValueError(f"{type(self._model).__name__} trains on one rank (the autograd step has no gradient all-reduce)")
+            self._optimizer = torch.optim.Adam(self._model.parameters(), lr=_get(_get(params, "optimizer"), "lr"))
+            return
         self._optimizer = MlpTrainer(self._model, lr=_get(_get(params, "optimizer"), "lr"),
                                      std_factor=_get(loss_cfg, "confidence_std_factor"),
                                      w_trav=_get(loss_cfg, "w_trav"), w_reco=_get(loss_cfg, "w_reco"),
                                      method=_get(loss_cfg, "method"), anomaly_balanced=_get(loss_cfg, "anomaly_balanced"))
-        self._cg_version = None   # the ConfidenceGenerator state version the trainer's device state was last loaded from
 
     # ------------------------------------------------------------------------------------------------
     @property
@@ -247,6 +258,8 @@ class TraversabilityEstimator:
             if graph is not None:
                 if self._anomaly_detection:
                     return self._train_anomaly(graph, return_dict)
+                if self._graph_model:
+                    return self._train_graph(graph, return_dict)
                 with self._learning_lock:
                     losses = self.train_on_batch(graph.x, graph.y, graph.y_valid)
                 log_step = (self._step % 20) == 0
@@ -279,6 +292,25 @@ class TraversabilityEstimator:
         self._step += 1
         return_dict["loss_total"] = total
         return_dict["loss_trav"], return_dict["loss_reco"] = loss_aux["loss_trav"].item(), loss_aux["loss_reco"].item()
+        return return_dict
+
+    def _train_graph(self, graph, return_dict):
+        """traversability_estimator.py:464-495 for the graph model: the Batch (x, edge_index, y, y_valid) through ``model(graph)``
+        (SimpleGCN's torch statement under autograd), TraversabilityLoss, backward, ``torch.optim.Adam`` step."""
+        log_step = (self._step % 20) == 0
+        with self._learning_lock:
+            for k in ("x", "edge_index", "y", "y_valid"):
+                setattr(graph, k, getattr(graph, k).to(self._device))
+            res = self._model(graph)
+            self._loss, loss_aux, _ = self._traversability_loss(graph, res, step=self._step, log_step=log_step)
+            self._optimizer.zero_grad()
+            self._loss.backward()
+            self._optimizer.step()
+        vals = torch.stack([self._loss.detach().reshape(()), loss_aux["loss_trav"].detach(), loss_aux["loss_reco"].detach()]).tolist()
+        if log_step:
+            print(f"step: {self._step} | loss: {vals[0]:5f} | loss_trav: {vals[1]:5f} | loss_reco: {vals[2]:5f}")
+        self._step += 1
+        return_dict["loss_total"], return_dict["loss_trav"], return_dict["loss_reco"] = vals[0], vals[1], vals[2]
         return return_dict
 
     def _train_anomaly_fused(self, graph, return_dict, log_step):
