@@ -855,6 +855,33 @@ int wvn_gcn_segment_predict(const wvn_mlp_desc* d, const float* params, const fl
                             const void* seg, int seg_bytes, int H, int W, float mean, float std, float std_factor,
                             const float* conf_state, float* trav, float* conf, float* loss_reco, void* workspace, size_t workspace_bytes,
                             void* stream);
+/* The SimpleGCN training step (csrc/simple_gcn_train.hip) in the three phases of the MLP step: the same statistic
+ * stats = {n_lab, sum, sum^2, R}, the same grads [wvn_mlp_param_count + 2] with the two loss sums behind the gradient, the same
+ * wvn_conf_desc.  Phase C is wvn_mlp_train_phase_c / wvn_mlp_train_phase_c_conf on the same descriptor.  The caller all-reduces
+ * stats (and MAX-reduces conf->minmax for moving_average) between A and B, and grads between B and C.
+ *   wvn_gcn_train_workspace_bytes : the step's workspace for (nodes, capacity >= E + nodes); nodes <= 65536 (0 otherwise).  Its head is
+ *                                   the inference workspace of the same (nodes, capacity).
+ *   wvn_gcn_train_phase_a : graph preparation from the edge list (the rule for bad edges and *bad_edges as in
+ *                           wvn_gcn_graph_from_edges), its transpose (every source's targets ascending, the coefficient carried
+ *                           with its edge), the three layers with h1, h2 and out kept (the forward values are bit for bit those
+ *                           of wvn_gcn_forward), the rows' reconstruction losses and the local statistic.  sync_word: a device
+ *                           word, zeroed by the call.  conf may be NULL: latest_measurement, anomaly_balanced.  11 launches.
+ *   wvn_gcn_train_phase_b : clears grads; the gradient seed (confidence_out [nodes], optional), the backward layers on the
+ *                           transposed graph, all weight and bias gradients and the loss sums.  5 launches.
+ *   wvn_gcn_train_saved   : byte offsets {h1 [nodes][H1], h2 [nodes][H2], out [nodes][1 + D]} of the values phase A keeps in the
+ *                           workspace (a test and debug accessor; host arithmetic).
+ * Every check is made on the host: a NULL pointer, nodes < 1, an unsupported width or a workspace that is too small gives
+ * WVN_ERR_ARG before any launch.  No floating-point atomics; every sum has one fixed ascending order: a step is bitwise
+ * reproducible and does not depend on the order of the edges.  No launch count depends on nodes or E; nothing is read on the host. */
+size_t wvn_gcn_train_workspace_bytes(const wvn_mlp_desc* d, int nodes, long long capacity);
+int wvn_gcn_train_saved(const wvn_mlp_desc* d, int nodes, long long capacity, size_t* offsets);
+int wvn_gcn_train_phase_a(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const long long* edge_index, long long ld_row,
+                          long long ld_edge, int E, const unsigned char* y_valid, int nodes, long long capacity, double* stats,
+                          int* bad_edges, void* workspace, size_t workspace_bytes, unsigned int* sync_word, const wvn_conf_desc* conf,
+                          void* stream);
+int wvn_gcn_train_phase_b(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const float* y, const unsigned char* y_valid,
+                          int nodes, long long capacity, const double* stats, float std_factor, float w_trav, float w_reco, float* grads,
+                          float* confidence_out, void* workspace, size_t workspace_bytes, const wvn_conf_desc* conf, void* stream);
 /* wvn_seg_adjacency's bitmap for a batch of frames, without the edge list: adj [B][S][S] uint8, adj[b][r * S + l] = 1 exactly for
  * the (left l, right r) pairs wvn_seg_adjacency returns for frame b (its transposed view is wvn_gcn_graph_from_bitmaps' (b, l, r)
  * element).  No host synchronisation. */

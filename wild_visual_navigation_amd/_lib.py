@@ -233,6 +233,10 @@ _SIGNATURES = {
     "wvn_gcn_graph_from_bitmaps": ([_p, _ll, _ll, _ll, _i, _i, _ll, _p, _p, _sz, _p], _i),
     "wvn_gcn_forward": ([_p, _p, _p, _i, _i, _ll, _p, _p, _sz, _p], _i),
     "wvn_gcn_segment_predict": ([_p, _p, _p, _i, _i, _i, _ll, _p, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
+    "wvn_gcn_train_workspace_bytes": ([_p, _i, _ll], _sz),
+    "wvn_gcn_train_saved": ([_p, _i, _ll, _p], _i),
+    "wvn_gcn_train_phase_a": ([_p, _p, _p, _i, _p, _ll, _ll, _i, _p, _i, _ll, _p, _p, _p, _sz, _p, _p, _p], _i),
+    "wvn_gcn_train_phase_b": ([_p, _p, _p, _i, _p, _p, _i, _ll, _p, _f, _f, _f, _p, _p, _p, _sz, _p, _p], _i),
     "wvn_seg_adjacency_batched": ([_p, _p, _i, _i, _i, _i, _p], _i),
     "wvn_debug_gemm_bf16_timed": ([_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p], _i),
     "wvn_debug_f16_saturate": ([_p, _p, _i, _p], _i),

@@ -16,7 +16,7 @@
 
 extern "C" {
 
-int wvn_version(void) { return 101; }   // 101: wvn_flip_average takes the source row stride; wvn_vit_forward_frames_head
+int wvn_version(void) { return 102; }   // 102: wvn_gcn_train_*; 101: wvn_flip_average takes the source row stride; wvn_vit_forward_frames_head
 
 size_t wvn_vit_workspace_bytes(const wvn_vit_model* m, int batch) {
   if (!m || batch <= 0) return 0;
@@ -953,6 +953,49 @@ int wvn_gcn_segment_predict(const wvn_mlp_desc* d, const float* params, const fl
                                workspace, (hipStream_t)stream));
   return wvn_segment_paint_launch(wvn_gcn_table(workspace, d->H1, d->H2, B * S, capacity), B, S, seg, seg_bytes, H, W, trav, conf,
                                   loss_reco, (hipStream_t)stream);
+}
+
+// SimpleGCN training step (simple_gcn_train.hip): phases A and B; phase C is wvn_mlp_train_phase_c(_conf) on the same descriptor
+namespace {
+const int GCN_TRAIN_MAX_NODES = 1 << 16;   // the weight gradients walk the rows un-split
+bool gcn_train_size_ok(long long nodes, long long capacity) { return gcn_size_ok(nodes, capacity) && nodes <= GCN_TRAIN_MAX_NODES; }
+int gcn_conf_args(const wvn_conf_desc* c, ConfArgs* a) { return c ? conf_args(c, a) : WVN_OK; }   // NULL: latest_measurement, balanced
+}  // namespace
+size_t wvn_gcn_train_workspace_bytes(const wvn_mlp_desc* d, int nodes, long long capacity) {
+  if (!gcn_ok(d) || !gcn_train_size_ok(nodes, capacity)) return 0;
+  return wvn_gcn_train_workspace_bytes_impl(d->D, d->H1, d->H2, nodes, capacity);
+}
+int wvn_gcn_train_saved(const wvn_mlp_desc* d, int nodes, long long capacity, size_t* offsets) {
+  if (!gcn_ok(d) || !gcn_train_size_ok(nodes, capacity) || !offsets) return WVN_ERR_ARG;
+  wvn_gcn_train_saved_offsets(d->D, d->H1, d->H2, nodes, capacity, offsets);
+  return WVN_OK;
+}
+int wvn_gcn_train_phase_a(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const long long* edge_index, long long ld_row,
+                          long long ld_edge, int E, const unsigned char* y_valid, int nodes, long long capacity, double* stats,
+                          int* bad_edges, void* workspace, size_t workspace_bytes, unsigned int* sync_word, const wvn_conf_desc* conf,
+                          void* stream) {
+  ConfArgs a;
+  RET_IF(gcn_conf_args(conf, &a));
+  if (!gcn_ok(d) || !params || !x || !y_valid || !stats || !bad_edges || !workspace || !sync_word) return WVN_ERR_ARG;
+  if (!gcn_train_size_ok(nodes, capacity) || ldx < d->D || E < 0 || (E > 0 && !edge_index) || capacity < (long long)E + nodes) return WVN_ERR_ARG;
+  if (((uintptr_t)edge_index & 7) || ((uintptr_t)workspace & 15) || ((uintptr_t)stats & 7)) return WVN_ERR_ARG;
+  if (((uintptr_t)params | (uintptr_t)x | (uintptr_t)bad_edges | (uintptr_t)sync_word) & 3) return WVN_ERR_ARG;
+  if (workspace_bytes < wvn_gcn_train_workspace_bytes_impl(d->D, d->H1, d->H2, nodes, capacity)) return WVN_ERR_ARG;
+  return wvn_gcn_train_phase_a_launch(d->D, d->H1, d->H2, params, x, ldx, edge_index, ld_row, ld_edge, E, y_valid, nodes, capacity, stats,
+                                      bad_edges, workspace, sync_word, a, (hipStream_t)stream);
+}
+int wvn_gcn_train_phase_b(const wvn_mlp_desc* d, const float* params, const float* x, int ldx, const float* y, const unsigned char* y_valid,
+                          int nodes, long long capacity, const double* stats, float std_factor, float w_trav, float w_reco, float* grads,
+                          float* confidence_out, void* workspace, size_t workspace_bytes, const wvn_conf_desc* conf, void* stream) {
+  ConfArgs a;
+  RET_IF(gcn_conf_args(conf, &a));
+  if (!gcn_ok(d) || !params || !x || !y || !y_valid || !stats || !grads || !workspace) return WVN_ERR_ARG;
+  if (!gcn_train_size_ok(nodes, capacity) || ldx < d->D) return WVN_ERR_ARG;
+  if (((uintptr_t)workspace & 15) || ((uintptr_t)stats & 7)) return WVN_ERR_ARG;
+  if (((uintptr_t)params | (uintptr_t)x | (uintptr_t)y | (uintptr_t)grads | (uintptr_t)confidence_out) & 3) return WVN_ERR_ARG;
+  if (workspace_bytes < wvn_gcn_train_workspace_bytes_impl(d->D, d->H1, d->H2, nodes, capacity)) return WVN_ERR_ARG;
+  return wvn_gcn_train_phase_b_launch(d->D, d->H1, d->H2, params, x, ldx, y, y_valid, nodes, capacity, stats, std_factor, w_trav, w_reco,
+                                      grads, confidence_out, workspace, a, (hipStream_t)stream);
 }
 
 int wvn_mlp_confidence(const float* out, int ldo, const float* x, int ldx, float mean, float std, float std_factor,

@@ -21,18 +21,11 @@
 // The last layer can keep its tile in LDS, form the row's reconstruction loss against the row's own features (16 lanes per row,
 // strided ascending partials + a butterfly) and write the {trav, conf, loss_reco, 0} table that seg_paint_kernel
 // (segment_predict.hip) spreads onto the segment maps.
-#include "common.h"
-#include "mlp_tile_device.h"
-#include "wvn_internal.h"
+// The tile geometry, gcn_scan_rows, the gather, the tile product and the workspace layout are in simple_gcn_device.h: the training
+// step (simple_gcn_train.hip) runs the same text on the transposed graph.
+#include "simple_gcn_device.h"
 
 namespace {
-
-constexpr int TR = 16;            // target rows per layer workgroup
-constexpr int DMAX = 1024, HMAX = 256;
-constexpr int TCOLS = 4;          // table row: trav, conf, loss, (pad)
-constexpr int ROW_WAVES = 4;      // rows (one wave each) per workgroup of the row-wise graph kernels
-
-__device__ inline float dinv_sqrt(int deg) { return 1.0f / sqrtf((float)deg); }
 
 // ---- graph preparation -------------------------------------------------------------------------------------------------
 struct EdgeList { const long long* ei; long long ld_row, ld_e; int E, N; };   // element (row, e) at ei[row * ld_row + e * ld_e]
@@ -52,31 +45,6 @@ __global__ __launch_bounds__(256) void gcn_count_edges(EdgeList g, int* __restri
   const int kind = edge_kind(g, e, j, i);
   if (kind > 0) atomicAdd(cnt + i, 1);
   else if (kind < 0) atomicAdd(bad, 1);
-}
-
-// single workgroup: rowptr = exclusive sums of cnt[i] + 1 (the self loop).  self_slots != nullptr (edge lists): node i goes into
-// slot 0 of its row there and cnt[i] becomes the next free slot of the row, 1.
-__global__ __launch_bounds__(1024) void gcn_scan_rows(int* __restrict__ cnt, int* __restrict__ rowptr, int* __restrict__ self_slots, int N) {
-  __shared__ int part[1024];
-  const int per = (N + 1023) / 1024;
-  const int beg = min(N, (int)threadIdx.x * per), end = min(N, beg + per);
-  int c = 0;
-  for (int i = beg; i < end; ++i) c += cnt[i] + 1;
-  part[threadIdx.x] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int t = 0; t < 1024; ++t) { const int v = part[t]; part[t] = run; run += v; }
-    rowptr[N] = run;
-  }
-  __syncthreads();
-  int o = part[threadIdx.x];
-  for (int i = beg; i < end; ++i) {
-    rowptr[i] = o;
-    const int d = cnt[i] + 1;
-    if (self_slots) { self_slots[o] = i; cnt[i] = 1; }
-    o += d;
-  }
 }
 
 __global__ __launch_bounds__(256) void gcn_fill_edges(EdgeList g, const int* __restrict__ rowptr, int* __restrict__ next, int* __restrict__ slots) {
@@ -141,52 +109,7 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void gcn_fill_bits(BitMaps g, const
   }
 }
 
-// ---- one layer ----------------------------------------------------------------------------------------------------------
-struct LayerParams {
-  const float* W; const float* b; int K, M;     // W [M][K], b [M]
-  const float* x; int ldx;                      // the layer's input rows [N][ldx]
-  const int* rowptr; const int* src; const float* coef;
-  int N;
-  float* out; int ldo;                          // [N][ldo]; may be NULL in the table form
-  // the table form of the last layer
-  const float* x0; int ldx0;                    // the network's input rows (the reconstruction target), M = 1 + D
-  float* table; float mean, std, std_factor; const float* conf_dev;
-};
-
-__host__ __device__ inline int out_pitch(int M) { return (M + 3) / 4 * 4 + 4; }
-
-// out[r][m] = b[m] + sum_k xs[r][k] W[m][k], one ascending FMA chain per value.  thread -> column lane c of 256 RPT / TR, rows
-// RPT g .. + RPT - 1: narrow layers spread their rows over the threads a wide one spends on columns.
-template <int RPT, typename Put>
-__device__ __forceinline__ void tile_linear(const float* __restrict__ W, const float* __restrict__ bias, int K, int M, const float* xs, Put put) {
-  constexpr int CL = 256 * RPT / TR;
-  const int c = threadIdx.x % CL, g = threadIdx.x / CL, KP = x_pitch(K);
-  const float* xr = xs + g * RPT * KP;
-  for (int m = c; m < M; m += CL) {
-    const float* w = W + (size_t)m * K;
-    float a[RPT];
-    const float bm = bias[m];
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) a[r] = bm;
-    int k = 0;
-    for (; k + 3 < K; k += 4) {
-      const float w0 = w[k], w1 = w[k + 1], w2 = w[k + 2], w3 = w[k + 3];
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) {
-        const f32x4_t x4 = *(const f32x4_t*)(xr + r * KP + k);
-        a[r] = fmaf(x4[3], w3, fmaf(x4[2], w2, fmaf(x4[1], w1, fmaf(x4[0], w0, a[r]))));
-      }
-    }
-    for (; k < K; ++k) {
-      const float w0 = w[k];
-#pragma unroll
-      for (int r = 0; r < RPT; ++r) a[r] = fmaf(xr[r * KP + k], w0, a[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < RPT; ++r) put(g * RPT + r, m, a[r]);
-  }
-}
-
+// ---- one layer (LayerParams, gather_tile, tile_linear: simple_gcn_device.h) ---------------------------------------------------
 // LAST: sigmoid on column 0, no ReLU.  TABLE (LAST only): the tile stays in LDS for the row loss and the table row.
 template <bool LAST, bool TABLE>
 __global__ __launch_bounds__(256) void gcn_layer_kernel(LayerParams p) {
@@ -196,15 +119,7 @@ __global__ __launch_bounds__(256) void gcn_layer_kernel(LayerParams p) {
   float* os = xs + TR * KP;        // [TR][MP] (TABLE)
   const int tid = threadIdx.x, row0 = blockIdx.x * TR;
   // ---- gather: xs[r][k] = sum over the neighbours of row r, ascending source (rows past N: zeros, never written out) ----
-  for (int i = tid; i < TR * K; i += 256) {
-    const int r = i / K, k = i - r * K, g = row0 + r;
-    float a = 0.f;
-    if (g < N) {
-      const int e1 = p.rowptr[g + 1];
-      for (int e = p.rowptr[g]; e < e1; ++e) a = fmaf(p.coef[e], p.x[(size_t)p.src[e] * p.ldx + k], a);
-    }
-    xs[r * KP + k] = a;
-  }
+  gather_tile(xs, KP, K, p.rowptr, p.src, p.coef, p.x, p.ldx, row0, N);
   __syncthreads();
   // ---- the tile product, bias and activation ----
   float* out = p.out;
@@ -215,11 +130,7 @@ __global__ __launch_bounds__(256) void gcn_layer_kernel(LayerParams p) {
     if (TABLE) os[r * MP + m] = v;
     if (out && row0 + r < N) out[(size_t)(row0 + r) * ldo + m] = v;
   };
-  if (M > 128) tile_linear<16>(p.W, p.b, K, M, xs, put);
-  else if (M > 64) tile_linear<8>(p.W, p.b, K, M, xs, put);
-  else if (M > 32) tile_linear<4>(p.W, p.b, K, M, xs, put);
-  else if (M > 16) tile_linear<2>(p.W, p.b, K, M, xs, put);
-  else tile_linear<1>(p.W, p.b, K, M, xs, put);
+  tile_linear_by_width(p.W, p.b, K, M, xs, put);
   if (TABLE) {
     __syncthreads();
     // ---- reconstruction loss of row r against its own features: lane q adds columns q, q + 16, ... in order, then a butterfly ----
@@ -237,24 +148,6 @@ __global__ __launch_bounds__(256) void gcn_layer_kernel(LayerParams p) {
 }
 
 size_t layer_lds_bytes(int K, int M, bool table) { return ((size_t)TR * x_pitch(K) + (table ? (size_t)TR * out_pitch(M) : 0)) * sizeof(float); }
-
-// the workspace: the graph first (its layout needs N and cap only), the activations behind it
-struct GcnWs { int *rowptr, *cnt, *slots, *src; float *coef, *h1, *h2, *table; size_t total; };
-GcnWs carve(void* base, int h1, int h2, int N, long long cap) {
-  GcnWs w{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return (char*)base + at; };
-  w.rowptr = (int*)take(((size_t)N + 1) * sizeof(int));
-  w.cnt = (int*)take((size_t)N * sizeof(int));
-  w.slots = (int*)take((size_t)cap * sizeof(int));
-  w.src = (int*)take((size_t)cap * sizeof(int));
-  w.coef = (float*)take((size_t)cap * sizeof(float));
-  w.h1 = (float*)take((size_t)N * h1 * sizeof(float));
-  w.h2 = (float*)take((size_t)N * h2 * sizeof(float));
-  w.table = (float*)take((size_t)N * TCOLS * sizeof(float));
-  w.total = o;
-  return w;
-}
 
 }  // namespace
 
@@ -304,14 +197,13 @@ int wvn_gcn_graph_bitmaps_launch(const unsigned char* adj, long long ld_b, long 
   return WVN_OK;
 }
 
-int wvn_gcn_layers_launch(int D, int h1, int h2, const float* params, const float* x, int ldx, int N, long long cap, float* out, int ldo,
-                          int want_table, float mean, float std, float std_factor, const float* conf_state, void* ws, hipStream_t st) {
+// the hidden layers x -> h1 -> h2 into the workspace: the first two launches of every forward, the training step's included
+int wvn_gcn_hidden_layers_launch(int D, int h1, int h2, const float* params, const float* x, int ldx, int N, long long cap, void* ws,
+                                 hipStream_t st) {
   const GcnWs w = carve(ws, h1, h2, N, cap);
-  const int O = 1 + D;
   // flat parameters [W1|b1|W2|b2|W3|b3]: SimpleMLP's layout for the same (D, h1, h2)
   const float* W1 = params; const float* b1 = W1 + (size_t)h1 * D;
   const float* W2 = b1 + h1; const float* b2 = W2 + (size_t)h2 * h1;
-  const float* W3 = b2 + h2; const float* b3 = W3 + (size_t)O * h2;
   static LdsOptIn lds_opt_in;   // D = 1024 needs more than 64 KB: opted in once per device for the largest geometry (common.h)
   const size_t lds_a = layer_lds_bytes(DMAX, HMAX, false), lds_b = layer_lds_bytes(HMAX, 1 + DMAX, true);
   const int lds_max = (int)(lds_a > lds_b ? lds_a : lds_b);
@@ -327,6 +219,18 @@ int wvn_gcn_layers_launch(int D, int h1, int h2, const float* params, const floa
   p.W = W2; p.b = b2; p.K = h1; p.M = h2; p.x = w.h1; p.ldx = h1; p.out = w.h2; p.ldo = h2;
   hipLaunchKernelGGL((gcn_layer_kernel<false, false>), grid, dim3(256), layer_lds_bytes(h1, h2, false), st, p);
   WVN_LAUNCH_CHECK();
+  return WVN_OK;
+}
+
+int wvn_gcn_layers_launch(int D, int h1, int h2, const float* params, const float* x, int ldx, int N, long long cap, float* out, int ldo,
+                          int want_table, float mean, float std, float std_factor, const float* conf_state, void* ws, hipStream_t st) {
+  if (const int rc = wvn_gcn_hidden_layers_launch(D, h1, h2, params, x, ldx, N, cap, ws, st)) return rc;   // (opts the kernels in)
+  const GcnWs w = carve(ws, h1, h2, N, cap);
+  const int O = 1 + D;
+  const float* W3 = params + (size_t)h1 * D + h1 + (size_t)h2 * h1 + h2; const float* b3 = W3 + (size_t)O * h2;
+  LayerParams p{};
+  p.rowptr = w.rowptr; p.src = w.src; p.coef = w.coef; p.N = N;
+  const dim3 grid(ceil_div(N, TR));
   p.W = W3; p.b = b3; p.K = h2; p.M = O; p.x = w.h2; p.ldx = h2; p.out = out; p.ldo = ldo;
   if (want_table) {
     p.x0 = x; p.ldx0 = ldx; p.table = w.table;

@@ -398,6 +398,19 @@ int wvn_gcn_graph_bitmaps_launch(const unsigned char* adj, long long ld_b, long 
 int wvn_gcn_layers_launch(int D, int h1, int h2, const float* params, const float* x, int ldx, int N, long long cap, float* out, int ldo,
                           int want_table, float mean, float std, float std_factor, const float* conf_state, void* ws, hipStream_t st);
 const float* wvn_gcn_table(void* ws, int h1, int h2, int N, long long cap);
+int wvn_gcn_hidden_layers_launch(int D, int h1, int h2, const float* params, const float* x, int ldx, int N, long long cap, void* ws,
+                                 hipStream_t st);   // x -> h1 -> h2 into the workspace (2 launches)
+// the training step (simple_gcn_train.hip) on a workspace whose head is the inference workspace for the same (N, cap).  Phase A:
+// graph, transposed graph, the three layers with the row losses and the statistic; phase B: seed, the backward layers on the
+// transposed graph, every weight and bias gradient and the two loss sums -> grads [n + 2]
+size_t wvn_gcn_train_workspace_bytes_impl(int D, int h1, int h2, int N, long long cap);
+void wvn_gcn_train_saved_offsets(int D, int h1, int h2, int N, long long cap, size_t offs[3]);   // byte offsets of h1, h2, out
+int wvn_gcn_train_phase_a_launch(int D, int h1, int h2, const float* params, const float* x, int ldx, const long long* ei, long long ld_row,
+                                 long long ld_e, int E, const unsigned char* valid, int N, long long cap, double* stats, int* bad, void* ws,
+                                 unsigned* ticket, const ConfArgs& conf, hipStream_t st);
+int wvn_gcn_train_phase_b_launch(int D, int h1, int h2, const float* params, const float* x, int ldx, const float* y,
+                                 const unsigned char* valid, int N, long long cap, const double* stats, float std_factor, float w_trav,
+                                 float w_reco, float* grads, float* conf_out, void* ws, const ConfArgs& conf, hipStream_t st);
 
 // ---- supervision path (supervision.hip) and SLIC (slic.hip) -------------------------------------------------------------
 int wvn_project_render_fmin_launch(const void* nodes, int n, const float* points, int points_batched, int npts, int C, int H,

@@ -13,6 +13,10 @@ The edge list is used as given (not symmetrised).  ``state_dict`` keys are PyG's
 ``layers.{0,1,2}.lin.weight`` [out, in]); glorot-uniform weights, zero bias.  The six tensors are views into ONE flat fp32 buffer
 [W1|b1|W2|b2|W3|b3], SimpleMLP's layout for the same (D, h1, h2).  Parity with the ``torch_geometric`` package itself is not
 pinned (it is not a dependency here): tests/simple_gcn_ref.py states the definition in float64.
+
+Training: ``forward`` returns the plain-torch statement whenever a gradient is asked for (autograd, CPU or GPU); the optimisation
+step of ``TraversabilityEstimator`` on a GPU device does not go through it but through the fused HIP phases of
+``traversability_estimator/gcn_trainer.py`` (csrc/simple_gcn_train.hip), on this model's flat buffer.
 """
 import ctypes as C
 import math
@@ -87,7 +91,7 @@ class SimpleGCN(torch.nn.Module):
         first HIP forward).  Reading it is the caller's host synchronisation, not the forward's."""
         return self._bad
 
-    # ---- the plain-torch statement (training: autograd, CPU or GPU) -----------------------------------
+    # ---- the plain-torch statement (autograd, CPU or GPU; the CPU estimator trains on it) -----------------------------------
     def forward_torch(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
         h = torch.relu(self.layers[0](x, edge_index))
         h = torch.relu(self.layers[1](h, edge_index))

@@ -27,7 +27,7 @@ from ..model.simple_mlp import SimpleMLP
 
 
 class TrainerState:
-    """What the fused trainers (MlpTrainer, RnvpTrainer) keep alike: the confidence statistic's device state and its exchange with a
+    """What the fused trainers (MlpTrainer, RnvpTrainer, GcnTrainer) keep alike: the confidence statistic's device state and its exchange with a
     ConfidenceGenerator, the Adam moments in ``torch.optim.Adam.state_dict()`` shape, the timed all-reduce.  A subclass provides
     ``model`` (``flat_params()``, ``_params_in_order()``), ``_state(dev)`` (which creates ``m``, ``v``, ``conf_state``), ``step``,
     ``lr``, ``group``, ``comm_events`` and ``_state_dev``."""

@@ -12,8 +12,10 @@ at inference, and on a GPU device a training step (at most 8 nodes x 100 labelle
 rnvp_trainer.py, data-parallel like the MLP step.  On ``device="cpu"`` it runs on autograd over the model's torch statement with
 ``torch.optim.Adam``, on one rank.
 
-``params.model.name == "SimpleGCN"``: inference runs the model's HIP graph kernels; a training step runs the whole ``Batch`` through
-the model's torch statement, ``TraversabilityLoss``, backward and ``torch.optim.Adam`` on one rank (``_train_graph``).
+``params.model.name == "SimpleGCN"``: inference runs the model's HIP graph kernels; on a GPU device a training step runs the whole
+``Batch`` (x, edge_index, y, y_valid) through the fused HIP phases of gcn_trainer.py, data-parallel like the MLP step (every rank
+trains on its own graphs).  On ``device="cpu"`` it runs through the model's torch statement, ``TraversabilityLoss``, backward and
+``torch.optim.Adam`` on one rank (``_train_graph``).
 """
 import os
 from threading import Lock
@@ -24,6 +26,7 @@ from ..distributed import all_ranks_ready
 from ..model import get_model
 from ..utils import AnomalyLoss, Batch, TraversabilityLoss
 from .. import ops
+from .gcn_trainer import GcnTrainer
 from .graphs import BaseGraph, DistanceWindowGraph, MaxElementsGraph
 from .nodes import MissionNode, SupervisionNode
 from .rnvp_trainer import RnvpTrainer
@@ -92,11 +95,18 @@ class TraversabilityEstimator:
         self._cg_version = None   # the ConfidenceGenerator state version the trainer's device state was last loaded from
         self._graph_model = getattr(self._model, "NEEDS_GRAPH", False)
         if self._graph_model:
-            # SimpleGCN: the whole Batch goes through the model's torch statement, TraversabilityLoss, backward and torch.optim.Adam
-            # (a fused HIP training step for the graph model is the follow-up); the autograd step has no gradient all-reduce
+            # SimpleGCN: a GPU device trains on the fused HIP step (GcnTrainer: data-parallel like MlpTrainer); on the CPU the whole
+            # Batch goes through the model's torch statement, TraversabilityLoss, backward and torch.optim.Adam, and that autograd
+            # step has no gradient all-reduce
+            lr = _get(_get(params, "optimizer"), "lr")
+            if self._device.type == "cuda":
+                self._optimizer = GcnTrainer(self._model, lr=lr, std_factor=_get(loss_cfg, "confidence_std_factor"),
+                                             w_trav=_get(loss_cfg, "w_trav"), w_reco=_get(loss_cfg, "w_reco"),
+                                             method=_get(loss_cfg, "method"), anomaly_balanced=_get(loss_cfg, "anomaly_balanced"))
+                return
             if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-                raise ValueError(f"{type(self._model).__name__} trains on one rank (the autograd step has no gradient all-reduce)")
-            self._optimizer = torch.optim.Adam(self._model.parameters(), lr=_get(_get(params, "optimizer"), "lr"))
+                raise ValueError(f"{type(self._model).__name__} on the CPU trains on one rank (the autograd step has no gradient all-reduce)")
+            self._optimizer = torch.optim.Adam(self._model.parameters(), lr=lr)
             return
         self._optimizer = MlpTrainer(self._model, lr=_get(_get(params, "optimizer"), "lr"),
                                      std_factor=_get(loss_cfg, "confidence_std_factor"),
@@ -127,7 +137,7 @@ class TraversabilityEstimator:
         self._mission_graph.change_device(device)
         self._model = self._model.to(device)
         self._traversability_loss = self._traversability_loss.to(device)
-        if isinstance(self._optimizer, RnvpTrainer):
+        if isinstance(self._optimizer, (RnvpTrainer, GcnTrainer)):
             self._optimizer.to(self._device)
 
     def update_visualization_node(self):
@@ -296,8 +306,11 @@ class TraversabilityEstimator:
 
     def _train_graph(self, graph, return_dict):
         """traversability_estimator.py:464-495 for the graph model: the Batch (x, edge_index, y, y_valid) through ``model(graph)``
-        (SimpleGCN's torch statement under autograd), TraversabilityLoss, backward, ``torch.optim.Adam`` step."""
+        (SimpleGCN's torch statement under autograd), TraversabilityLoss, backward, ``torch.optim.Adam`` step; on a GPU device the
+        fused step (``_train_graph_fused``)."""
         log_step = (self._step % 20) == 0
+        if isinstance(self._optimizer, GcnTrainer):
+            return self._train_graph_fused(graph, return_dict, log_step)
         with self._learning_lock:
             for k in ("x", "edge_index", "y", "y_valid"):
                 setattr(graph, k, getattr(graph, k).to(self._device))
@@ -307,6 +320,30 @@ class TraversabilityEstimator:
             self._loss.backward()
             self._optimizer.step()
         vals = torch.stack([self._loss.detach().reshape(()), loss_aux["loss_trav"].detach(), loss_aux["loss_reco"].detach()]).tolist()
+        if log_step:
+            print(f"step: {self._step} | loss: {vals[0]:5f} | loss_trav: {vals[1]:5f} | loss_reco: {vals[2]:5f}")
+        self._step += 1
+        return_dict["loss_total"], return_dict["loss_trav"], return_dict["loss_reco"] = vals[0], vals[1], vals[2]
+        return return_dict
+
+    def _train_graph_fused(self, graph, return_dict, log_step):
+        """The same step on the HIP phases (GcnTrainer): forward, loss, gradient, Adam and the confidence statistic on the device,
+        with ``train_on_batch``'s hand-off to the ConfidenceGenerator; one host read."""
+        cg = self._traversability_loss._confidence_generator
+        tr = self._optimizer
+        with self._learning_lock:
+            if tr._conf and self._cg_version != cg._version:   # constructed, loaded, reset or updated on the host since the last step
+                tr.load_confidence_state(cg)
+                self._cg_version = cg._version
+            losses = tr.train_step(*(getattr(graph, k).to(self._device) for k in ("x", "edge_index", "y", "y_valid")))
+            with torch.no_grad():
+                if tr._conf:   # mean / var / std (and the running sums) of the step's method
+                    tr.store_confidence_state(cg)
+                else:
+                    cg.mean.copy_(losses[3:4])
+                    cg.std.copy_(losses[4:5])
+            self._loss = losses[0:1]
+        vals = losses.tolist()   # the one host read of the step
         if log_step:
             print(f"step: {self._step} | loss: {vals[0]:5f} | loss_trav: {vals[1]:5f} | loss_reco: {vals[2]:5f}")
         self._step += 1
