@@ -1050,6 +1050,56 @@ int wvn_dense_crf_permutohedral(const float* logits1, int K1, long long s1b, lon
 int wvn_debug_permutohedral_lattice(const unsigned char* image, int B, int H, int W, int bilateral, float xy_std, float rgb_std, int* M,
                                     int* keys, float* bary, int* vert, int* nbr, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- overlays (csrc/overlay.hip; DESIGN.md section 4 "Overlays"; tests/visu_ref.py is the same statement on the CPU) ----
+ * The pictures of visu/visualizer.py of the reference -- plot_image, plot_segmentation, plot_detectron,
+ * plot_detectron_classification, plot_traversability_graph_on_seg, plot_list -- as one pass per output pixel, defined bit for bit.
+ *
+ * Frame -> 8 bits: img [B][3][H][W] fp32 or u8 (img_u8).  unit_range 1: multiplied by 255 (fp32, rounded on its own); 0: taken as
+ * is; < 0: per frame, multiplied iff frame_max[b] <= 1 (frame_max from wvn_frame_max; plot_image's `img.max() <= 1`).  Then
+ * truncated toward zero; outside [0, 255] clamped, NaN -> 0.  (u8 frames: x * 255 saturates, i.e. non-zero -> 255.)
+ * Colour index of pixel p of map m, by `kind`:
+ *   WVN_OVERLAY_VALUES    maps[m] fp32 [B][H][W]: (v * 255) truncated, clipped to [0, 255]; a non-finite product gives 0;
+ *   WVN_OVERLAY_LABELS    maps[m] ids [B][H][W] (id_bytes 4 or 8, signed), used as they are;
+ *   WVN_OVERLAY_SEGMENTS  maps[m] fp32 [B][S] and seg ids [B][H][W] (seg_bytes 4 or 8): s = seg[p], ids in [-S, 0) wrap to s + S,
+ *                         index = (maps[m][b][s] * 255) truncated toward zero (not clipped).
+ * An index outside [0, N) -- and a segment id outside [-S, S), a non-finite per-segment product -- paints the plain frame pixel.
+ * Colour table lut [N][3], N <= WVN_OVERLAY_MAX_COLOURS: u8 (lut_u8), or fp32 converted as (c * 255) -> u8 by the frame's rule.
+ * Blend per channel, source colour s over frame byte d with the alpha byte a (`alpha`; 0 where mask [B][H][W] bytes, optional,
+ * is non-zero): a == 0: d; else t = s (128 a) + d (128 (255 - a)) + (0x80 << 7), out = ((((t >> 8) + t) >> 8) >> 7) --
+ * PIL.Image.alpha_composite over an opaque image.  boundary_seg (optional ids [B][H][W], boundary_bytes 4 or 8) with
+ * boundary_alpha > 0: a pixel one of whose in-image 4-neighbours carries another id gets white composited over the result with
+ * that alpha by the same formula; boundary_alpha == 0 is the identity (the reference's default) and reads nothing.
+ * Output: packed RGB bytes; pixel (y, x) of panel k of frame b at out[b * out_frame_bytes + y * out_row_bytes + 3 * (k * W + x)];
+ * out itself may sit at any byte address (a column offset into a wider image).  Panels: `plain` (0 / 1) plain-frame panel first,
+ * then one per map, nmaps <= WVN_OVERLAY_MAX_MAPS; the frame is converted once.
+ * wvn_overlay: plain == 0 and nmaps == 1.  wvn_overlay_panels: plain == 1, nmaps >= 0 (0: the 8-bit frame alone).  Both are one
+ * launch, stream-ordered, no host synchronisation.  WVN_ERR_ARG before anything is launched for a NULL input, B outside
+ * [1, 65535], H or W < 1, N outside [1, 1024], more than 4 maps, alpha bytes outside [0, 255], id sizes other than 4 / 8, an
+ * unknown kind, or a row pitch smaller than the panels. */
+#define WVN_OVERLAY_MAX_COLOURS 1024
+#define WVN_OVERLAY_MAX_MAPS 4
+#define WVN_OVERLAY_VALUES 0
+#define WVN_OVERLAY_LABELS 1
+#define WVN_OVERLAY_SEGMENTS 2
+typedef struct {
+  const void* img;
+  const float* frame_max;
+  const void* maps[WVN_OVERLAY_MAX_MAPS];
+  const void* seg;
+  const void* lut;
+  const unsigned char* mask;
+  const void* boundary_seg;
+  unsigned char* out;
+  long long out_row_bytes, out_frame_bytes;
+  int img_u8, unit_range, B, H, W;
+  int kind, nmaps, plain, id_bytes, seg_bytes, boundary_bytes, S, lut_u8, N, alpha, boundary_alpha;
+} wvn_overlay_desc;
+/* frame_max[b] = max(0, largest of the n values of frame b) as fp32, NaN when the frame holds a NaN (fp32 frames; n = 3 H W).
+ * A clear and one launch on the stream. */
+int wvn_frame_max(const void* img, int img_u8, int B, long long n, float* frame_max, void* stream);
+int wvn_overlay(const wvn_overlay_desc* d, void* stream);
+int wvn_overlay_panels(const wvn_overlay_desc* d, void* stream);
+
 /* ---- step scheduling (no reference counterpart: the reference runs one frame at a time on one CUDA stream,
  * wild_visual_navigation_ros/scripts/wvn_feature_extractor_node.py:319-363) ----
  * A HIP stream whose kernels may only occupy the compute units named by `mask` (bit i of the `words` 32-bit words = CU i in the

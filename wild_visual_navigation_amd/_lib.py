@@ -90,6 +90,17 @@ class RnvpDesc(C.Structure):
     _fields_ = [("D", C.c_int), ("h", C.c_int), ("flows", C.c_int)]
 
 
+class OverlayDesc(C.Structure):
+    """include/wvn_hip.h: wvn_overlay_desc."""
+    _fields_ = [("img", C.c_void_p), ("frame_max", C.c_void_p), ("maps", C.c_void_p * 4), ("seg", C.c_void_p), ("lut", C.c_void_p),
+                ("mask", C.c_void_p), ("boundary_seg", C.c_void_p), ("out", C.c_void_p),
+                ("out_row_bytes", C.c_longlong), ("out_frame_bytes", C.c_longlong)] + \
+               [(n, C.c_int) for n in ("img_u8", "unit_range", "B", "H", "W", "kind", "nmaps", "plain", "id_bytes", "seg_bytes",
+                                       "boundary_bytes", "S", "lut_u8", "N", "alpha", "boundary_alpha")]
+
+
+OVERLAY_MAX_COLOURS, OVERLAY_MAX_MAPS = 1024, 4
+OVERLAY_VALUES, OVERLAY_LABELS, OVERLAY_SEGMENTS = 0, 1, 2
 MLP_KIND_DOUBLE = 1   # include/wvn_hip.h: WVN_MLP_KIND_DOUBLE (MlpDesc.reserved)
 
 
@@ -248,6 +259,9 @@ _SIGNATURES = {
     "wvn_dense_crf_permutohedral_workspace_bytes": ([_i, _i, _i, _i], _sz),
     "wvn_dense_crf_permutohedral": ([_p, _i, _ll, _ll, _ll, _p, _i, _ll, _ll, _ll, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p], _i),
     "wvn_debug_permutohedral_lattice": ([_p, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p, _sz, _p], _i),
+    "wvn_frame_max": ([_p, _i, _i, _ll, _p, _p], _i),
+    "wvn_overlay": ([_p, _p], _i),
+    "wvn_overlay_panels": ([_p, _p], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

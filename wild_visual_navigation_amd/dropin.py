@@ -13,14 +13,16 @@ wvn_learning_node.py:7-24) bind the MI355X classes:
     from wild_visual_navigation.utils import ConfidenceGenerator, Data, Batch, TraversabilityLoss, AnomalyLoss, WVNMode, make_plane ...
     from wild_visual_navigation.traversability_estimator import TraversabilityEstimator, MissionNode, SupervisionNode, graphs
     from wild_visual_navigation.cfg import ExperimentParams
+    from wild_visual_navigation.visu import LearningVisualizer                       (stand-alone mode, or install(visu=True))
 
 Two situations:
   * the reference package IS importable (a robot with WVN installed): only the hot-path sub-packages listed in ``HOT`` are
-    replaced; everything else the callers import -- ``visu``, ``supervision_generator``, ``cfg.Ros*Params``,
+    replaced; everything else the callers import -- ``supervision_generator``, ``cfg.Ros*Params``,
     ``utils.create_experiment_folder`` -- keeps coming from the reference (those are CPU-side helpers outside this build's
-    scope, SURVEY.md section 2);
+    scope).  ``visu`` stays the reference's too (it has plots this package does not: plot_roc,
+    plot_histogram, the optical-flow plots) unless the caller asks for the GPU overlays with ``install(visu=True)``;
   * it is NOT (this container): a synthetic ``wild_visual_navigation`` package is registered whose sub-modules are the ones of
-    this package, so the import lines above work and anything out of scope raises ImportError as usual.
+    this package (``visu`` included), so the import lines above work and anything out of scope raises ImportError as usual.
 """
 import importlib
 import os
@@ -46,11 +48,13 @@ def _alias_submodules(pkg_mod, alias: str) -> None:
         sys.modules[alias + info.name[len(pkg_mod.__name__):]] = sub
 
 
-def install(force_synthetic: bool = False) -> str:
-    """Returns "overlay" (reference present, hot-path modules replaced) or "synthetic" (stand-alone alias package)."""
+def install(force_synthetic: bool = False, visu: bool = False) -> str:
+    """Returns "overlay" (reference present, hot-path modules replaced) or "synthetic" (stand-alone alias package).
+    ``visu``: with the reference present, replace its ``visu`` package by the GPU overlays as well (always so stand-alone)."""
     import wild_visual_navigation_amd as amd
 
     mods = {name: importlib.import_module(f"wild_visual_navigation_amd.{name}") for name in HOT}
+    amd_visu = importlib.import_module("wild_visual_navigation_amd.visu")
     amd_utils = importlib.import_module("wild_visual_navigation_amd.utils")
     ref = None
     if not force_synthetic:
@@ -76,6 +80,9 @@ def install(force_synthetic: bool = False) -> str:
         sys.modules["wild_visual_navigation.utils"] = amd_utils
         pkg.utils = amd_utils
         _alias_submodules(amd_utils, "wild_visual_navigation.utils")
+        sys.modules["wild_visual_navigation.visu"] = amd_visu
+        pkg.visu = amd_visu
+        _alias_submodules(amd_visu, "wild_visual_navigation.visu")
         return "synthetic"
     for name, m in mods.items():
         if name == "cfg":
@@ -83,6 +90,10 @@ def install(force_synthetic: bool = False) -> str:
         sys.modules[f"wild_visual_navigation.{name}"] = m
         setattr(ref, name, m)
         _alias_submodules(m, f"wild_visual_navigation.{name}")
+    if visu:
+        sys.modules["wild_visual_navigation.visu"] = amd_visu
+        setattr(ref, "visu", amd_visu)
+        _alias_submodules(amd_visu, "wild_visual_navigation.visu")
     ref_utils = importlib.import_module("wild_visual_navigation.utils")
     for n in UTILS_HOT:
         setattr(ref_utils, n, getattr(amd_utils, n))

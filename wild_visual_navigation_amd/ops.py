@@ -954,3 +954,164 @@ class MaskedStream:
             torch.cuda.synchronize()
             check(lib().wvn_stream_destroy(self.handle), "wvn_stream_destroy")
             self.handle = None
+
+
+# ---- overlays (csrc/overlay.hip; include/wvn_hip.h "overlays"; tests/visu_ref.py) -------------------------------------------
+def alpha_byte(alpha) -> int:
+    """``np.uint8(alpha * 255)`` of the reference's ``fore[:, :, 3] = alpha * 255`` (float64 product, truncated), clamped to a byte."""
+    return max(0, min(255, int(float(alpha) * 255)))
+
+
+def _overlay_frames(img: torch.Tensor, who: str) -> torch.Tensor:
+    if img.dim() == 3:
+        img = img[None]
+    if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
+        raise _lib.WvnError(f"{who}: img shape must be [B,3,H,W] or [3,H,W], not {tuple(img.shape)}")
+    require_cuda(img, "img")
+    return img.contiguous() if img.dtype == torch.uint8 else img.contiguous().float()
+
+
+def _overlay_ids(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous() if t.dtype in (torch.int32, torch.int64) else t.to(torch.int32).contiguous()
+
+
+def frame_max(img: torch.Tensor) -> torch.Tensor:
+    """img [B,3,H,W] fp32 or uint8 -> fp32 [B]: max(0, the frame's maximum), NaN for a frame that holds a NaN (plot_image's
+    ``img.max() <= 1`` decision, left on the device)."""
+    img = _overlay_frames(img, "frame_max")
+    B = img.shape[0]
+    out = torch.empty(B, dtype=torch.float32, device=img.device)
+    check(lib().wvn_frame_max(ptr(img), int(img.dtype == torch.uint8), B, img[0].numel(), ptr(out), stream()), "wvn_frame_max")
+    return out
+
+
+def _overlay_call(who, img, maps, kind, seg, lut, alpha, overlay_mask, boundary_seg, boundary_alpha, unit_range, out, plain):
+    if len(maps) > _lib.OVERLAY_MAX_MAPS:
+        raise _lib.WvnError(f"{who}: at most {_lib.OVERLAY_MAX_MAPS} maps per call, got {len(maps)}")
+    img = _overlay_frames(img, who)
+    B, _, H, W = img.shape
+    dev = img.device
+    d = _lib.OverlayDesc()
+    keep = [img]
+
+    def frames(t, name, ids=False):
+        if t.dim() == 2:
+            t = t[None]
+        if tuple(t.shape) != (B, H, W):
+            raise _lib.WvnError(f"{who}: {name} shape must be [B,H,W] = {(B, H, W)}, not {tuple(t.shape)}")
+        require_cuda(t, name)
+        t = _overlay_ids(t) if ids else t
+        keep.append(t)
+        return t
+
+    if maps:
+        if lut is None or lut.dim() != 2 or lut.shape[1] != 3 or not (1 <= lut.shape[0] <= _lib.OVERLAY_MAX_COLOURS):
+            raise _lib.WvnError(f"{who}: lut shape must be [N,3] with 1 <= N <= {_lib.OVERLAY_MAX_COLOURS}, "
+                                f"not {None if lut is None else tuple(lut.shape)}")
+        require_cuda(lut, "lut")
+        if lut.dtype not in (torch.uint8, torch.float32):   # (c * 255) in the table's own precision, as the reference's c_map * 255
+            lut = torch.nan_to_num(lut * 255, nan=0.0).clamp(0, 255).to(torch.uint8)
+        lut = lut.contiguous()
+        keep.append(lut)
+        d.lut, d.lut_u8, d.N = ptr(lut), int(lut.dtype == torch.uint8), lut.shape[0]
+        d.kind = kind
+        if kind == _lib.OVERLAY_SEGMENTS:
+            seg = frames(seg, "seg", ids=True)
+            d.seg, d.seg_bytes = ptr(seg), seg.element_size()
+            vecs = []
+            for v in maps:
+                v = v[None] if v.dim() == 1 else v
+                if v.dim() != 2 or v.shape[0] != B or v.shape[1] < 1 or (vecs and v.shape != vecs[0].shape):
+                    raise _lib.WvnError(f"{who}: per-segment values shape must be [B,S] (B = {B}), the same for every map, not {tuple(v.shape)}")
+                require_cuda(v, "values")
+                vecs.append(v.contiguous().float())
+            keep += vecs
+            d.S = vecs[0].shape[1]
+            for i, v in enumerate(vecs):
+                d.maps[i] = ptr(v)
+        else:
+            for i, m in enumerate(maps):
+                m = frames(m, "labels" if kind == _lib.OVERLAY_LABELS else "values", ids=kind == _lib.OVERLAY_LABELS)
+                if kind == _lib.OVERLAY_VALUES:
+                    m = m.float().contiguous()
+                    keep.append(m)
+                if kind == _lib.OVERLAY_LABELS:
+                    if i and m.element_size() != d.id_bytes:
+                        raise _lib.WvnError(f"{who}: label maps of one call share a dtype")
+                    d.id_bytes = m.element_size()
+                d.maps[i] = ptr(m)
+        d.alpha = alpha_byte(alpha)
+        if overlay_mask is not None:
+            mk = frames(overlay_mask, "overlay_mask")
+            mk = mk.contiguous() if mk.dtype in (torch.bool, torch.uint8) else (mk != 0)
+            keep.append(mk)
+            d.mask = ptr(mk)
+        ba = int(boundary_alpha)
+        if not 0 <= ba <= 255:
+            raise _lib.WvnError(f"{who}: boundary_alpha is the alpha BYTE of the reference (0..255), not {boundary_alpha}")
+        d.boundary_alpha = ba
+        if boundary_seg is not None and ba > 0:
+            bs = frames(boundary_seg, "boundary_seg", ids=True)
+            d.boundary_seg, d.boundary_bytes = ptr(bs), bs.element_size()
+    npan = plain + len(maps)
+    if out is None:
+        out = torch.empty(B, H, npan * W, 3, dtype=torch.uint8, device=dev)
+    else:
+        if out.dtype != torch.uint8 or tuple(out.shape) != (B, H, npan * W, 3) or out.device != dev or out.stride(3) != 1 \
+                or out.stride(2) != 3 or out.stride(1) < 3 * npan * W or (B > 1 and out.stride(0) < H * out.stride(1)):
+            raise _lib.WvnError(f"{who}: out must be a uint8 [B,H,{npan}*W,3] = {(B, H, npan * W, 3)} view on {dev} with packed pixels "
+                                f"(rows and frames may be pitched), not {tuple(out.shape)} {out.dtype} strides {out.stride()}")
+    d.img, d.img_u8, d.B, d.H, d.W = ptr(img), int(img.dtype == torch.uint8), B, H, W
+    d.nmaps, d.plain = len(maps), plain
+    if unit_range is None:
+        fm = frame_max(img)
+        keep.append(fm)
+        d.frame_max, d.unit_range = ptr(fm), -1
+    else:
+        d.unit_range = int(bool(unit_range))
+    d.out, d.out_row_bytes, d.out_frame_bytes = ptr(out), out.stride(1), out.stride(0)
+    fn = lib().wvn_overlay_panels if plain else lib().wvn_overlay
+    check(fn(C.byref(d), stream()), "wvn_overlay_panels" if plain else "wvn_overlay")
+    return out
+
+
+def image_to_u8(img: torch.Tensor, unit_range: Optional[bool] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """plot_image (visualizer.py:516-537) on the device: img [B,3,H,W] (or [3,H,W]) fp32 / uint8 -> uint8 [B,H,W,3].  A frame
+    whose maximum is <= 1 is multiplied by 255 (``unit_range`` True / False states the range and skips the reduction), then
+    truncated; outside [0, 255]: clamped, NaN -> 0."""
+    return _overlay_call("image_to_u8", img, [], 0, None, None, 0, None, None, 0, unit_range, out, 1)
+
+
+def _overlay_kind(who, values, labels, seg):
+    if (values is None) == (labels is None) or (labels is not None and seg is not None):
+        raise _lib.WvnError(f"{who}: pass values [B,H,W], labels [B,H,W], or values [B,S] with seg [B,H,W]")
+    return _lib.OVERLAY_LABELS if labels is not None else (_lib.OVERLAY_SEGMENTS if seg is not None else _lib.OVERLAY_VALUES)
+
+
+def overlay(img: torch.Tensor, values: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+            seg: Optional[torch.Tensor] = None, lut: Optional[torch.Tensor] = None, alpha: float = 0.5,
+            overlay_mask: Optional[torch.Tensor] = None, boundary_seg: Optional[torch.Tensor] = None, boundary_alpha: int = 0,
+            unit_range: Optional[bool] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's overlay pictures in one launch -> uint8 [B,H,W,3] (include/wvn_hip.h "overlays" is the definition).
+    ``values`` [B,H,W] float: index (v * 255) truncated and clipped (plot_detectron_classification); ``labels`` [B,H,W] int: the
+    index itself (plot_segmentation / plot_detectron); ``values`` [B,S] with ``seg`` [B,H,W]: (values[seg] * 255) truncated, ids
+    in [-S, 0) wrapping (plot_traversability_graph_on_seg).  ``lut`` [N,3], N <= 1024, floats in [0,1] or uint8.  An index outside
+    the table leaves the plain pixel.  ``alpha``: the reference's float (its byte is ``alpha_byte``); ``overlay_mask`` pixels get
+    no overlay; ``boundary_seg`` with ``boundary_alpha`` (a byte, 0 = off) composites white over 4-neighbour label edges.
+    ``out``: a uint8 [B,H,W,3] view, e.g. a column slice of a wider image."""
+    kind = _overlay_kind("overlay", values, labels, seg)
+    return _overlay_call("overlay", img, [labels if labels is not None else values], kind, seg, lut, alpha, overlay_mask,
+                         boundary_seg, boundary_alpha, unit_range, out, 0)
+
+
+def overlay_panels(img: torch.Tensor, maps, lut: Optional[torch.Tensor] = None, alpha: float = 0.5, labels: bool = False,
+                   seg: Optional[torch.Tensor] = None, overlay_mask: Optional[torch.Tensor] = None,
+                   boundary_seg: Optional[torch.Tensor] = None, boundary_alpha: int = 0, unit_range: Optional[bool] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[plain frame | overlay of maps[0] | overlay of maps[1] | ...] side by side, uint8 [B,H,(1 + len(maps)) * W,3], the frame
+    converted once, one launch (quick_start.py's ``plot_list([original, conf, trav])``).  ``maps``: up to 4 value maps [B,H,W]
+    (label maps with ``labels=True``, per-segment vectors [B,S] with ``seg``); the other arguments as ``overlay``."""
+    maps = list(maps)
+    kind = _lib.OVERLAY_LABELS if labels else (_lib.OVERLAY_SEGMENTS if seg is not None else _lib.OVERLAY_VALUES)
+    return _overlay_call("overlay_panels", img, maps, kind, seg, lut, alpha, overlay_mask, boundary_seg, boundary_alpha, unit_range,
+                         out, 1)

@@ -2,7 +2,8 @@
 wild_visual_navigation/traversability_estimator/traversability_estimator.py:33-505, hot-path slice:
 constructor (10 reference arguments), ``train() -> dict``, ``make_batch``, ``add_mission_node``, ``add_supervision_node``
 (projection + polygon fill + fmin + label pooling on HIP kernels), ``change_device``, ``save_checkpoint`` /
-``load_checkpoint`` (same dict keys, interchangeable with the reference), and the private attributes the learning node reads
+``load_checkpoint`` (same dict keys, interchangeable with the reference), ``plot_mission_node_prediction`` /
+``plot_mission_node_training`` (overlays on csrc/overlay.hip through ``_visualizer``), and the private attributes the learning node reads
 (``_model``, ``_traversability_loss._confidence_generator``, ``_mission_graph``, ``_step``, ``_visualizer``).  Forward, loss, backward and Adam run in the fused HIP phases
 (trainer.py); with torch.distributed initialised every rank trains on its own frames and the two
 small all-reduces keep the replicas identical.
@@ -25,6 +26,7 @@ import torch
 from ..distributed import all_ranks_ready
 from ..model import get_model
 from ..utils import AnomalyLoss, Batch, TraversabilityLoss
+from ..visu import LearningVisualizer
 from .. import ops
 from .gcn_trainer import GcnTrainer
 from .graphs import BaseGraph, DistanceWindowGraph, MaxElementsGraph
@@ -57,7 +59,7 @@ class TraversabilityEstimator:
         else:
             self._mission_graph = BaseGraph(edge_distance=image_distance_thr)
         self._vis_mission_node = None
-        self._visualizer = None   # LearningVisualizer (matplotlib overlays) is outside the MI355X path; the attribute exists
+        self._visualizer = LearningVisualizer()   # overlays on csrc/overlay.hip; nothing is uploaded until the first picture
         self._learning_lock = Lock()
         self._pause_training = False
         self._pause_mission_graph = False
@@ -386,6 +388,14 @@ class TraversabilityEstimator:
                 cg.std.copy_(losses[4:5])
         self._loss = losses[0:1]
         return losses
+
+    def plot_mission_node_prediction(self, node: MissionNode):
+        """traversability_estimator.py:500-501: (traversability picture, confidence picture) of a node, np.uint8 HWC each."""
+        return self._visualizer.plot_mission_node_prediction(node)
+
+    def plot_mission_node_training(self, node: MissionNode):
+        """traversability_estimator.py:504-505: (supervision graph picture, supervision mask picture)."""
+        return self._visualizer.plot_mission_node_training(node)
 
     # ------------------------------------------------------------------------------------------------
     def save_checkpoint(self, mission_path: str, checkpoint_name: str = "last_checkpoint.pt"):
