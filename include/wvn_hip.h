@@ -1110,6 +1110,63 @@ int wvn_overlay_panels(const wvn_overlay_desc* d, void* stream);
 int wvn_stream_create_cu_mask(void** stream, const unsigned int* mask, int words);
 int wvn_stream_destroy(void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * feature_type "torchvision" (torchvision_interface.py of the reference: resnet18, eval mode, return nodes layer{1,2,3,4}.1.relu_1;
+ * feature_extractor.py:314-366: the multi-scale segment pooling), csrc/resnet.hip and csrc/pyramid_pool.hip.  Exact fp32 on the
+ * fp32-input MFMA.  tests/resnet_ref.py states network and pooling in float64; PARITY WITH THE torchvision PACKAGE AND WITH A RELEASED
+ * CHECKPOINT IS UNPINNED (both are absent).
+ *
+ * Activations are NHWC fp32 [B][h][w][C].  A convolution is out[b][oy][ox][n] = epilogue(sum_k A[k] Wp[k][n]), k = (ky * ksize + kx) *
+ * Cin + cin ascending in ONE fmaf chain from 0 (terms outside the input are 0): the bits of an element depend on neither the batch nor
+ * the launch geometry.  epilogue(v) = fmaf(v, scale[n], shift[n]) (+ residual[b][oy][ox][n]) (then v < 0 ? 0 : v when relu): eval-mode
+ * BatchNorm folded to scale = weight / sqrt(running_var + eps), shift = bias - running_mean * scale, formed by the caller in float64.
+ *   wvn_conv2d_pack_floats / wvn_conv2d_pack: w [Cout][Cin][ksize][ksize] -> packed [Kpad][Cout], Kpad = Cin ksize^2 rounded up to 32.
+ *   wvn_conv2d_bn_act: in_kind WVN_CONV_IN_NHWC: in is an activation [B][H][W][Cin], Cin % 32 == 0;
+ *       WVN_CONV_IN_FRAME_F32 / _U8: in is a frame [B][3][H][W] (fp32 in [0, 1] / uint8 as v / 255), read as (v - mean[c]) / std[c] with
+ *       T.Normalize([0.485, 0.456, 0.406], [0.229, 0.224, 0.225]) -- the stem; a uint8 frame gives the bits of its fp32 twin.
+ *       Cout % 64 == 0, ksize 1..7 (square), stride 1 or 2, pad 0..3.  residual may be NULL.
+ *   wvn_maxpool3x3s2: 3 x 3, stride 2, pad 1 with -inf padding, NHWC [B][H][W][C] -> [B][(H - 1) / 2 + 1][(W - 1) / 2 + 1][C].
+ * The whole network: the 20 convolutions in the order
+ *   conv1; layer1.0.conv1, layer1.0.conv2, layer1.1.conv1, layer1.1.conv2;
+ *   layerL.0.conv1, layerL.0.conv2, layerL.0.downsample.0, layerL.1.conv1, layerL.1.conv2   for L = 2, 3, 4
+ * (each with the BatchNorm that follows it).  wvn_resnet18_pack takes three HOST arrays of WVN_RESNET18_NCONV device pointers (weights
+ * [Cout][Cin][k][k], scale [Cout], shift [Cout]) and writes one packed image of wvn_resnet18_pack_bytes() bytes.
+ * wvn_resnet18_forward: frames [B][3][H][W] (fp32, or uint8 when frames_u8), H and W multiples of 32 -> the four level maps in the
+ * workspace, level l = 1..4 (stride 2^(l+1), 32 * 2^l channels, NHWC) at byte offset wvn_resnet18_level_offset(B, H, W, l); the rest
+ * of the workspace holds temporaries.  21 launches on the stream, no allocation.
+ *
+ * wvn_segpool_pyramid: feat [B][S][960] fp32 from the four level maps and seg [B][H][W] int32, columns [0, 64) [64, 192) [192, 448)
+ * [448, 960) for levels 1..4.  Per level with stride s (h = H / s, w = W / s): row i = the mean of the level's vectors over the cells
+ * (cy, cx) with seg[cy s][cx s] == i (summed in float64 in raster order, rounded once: reproducible bit for bit and independent of the
+ * batch; no floating-point atomics).  Where no cell carries id i -- the published code raises there -- the row is the vector of the
+ * cell (min(Cy / s, h - 1), min(Cx / s, w - 1)), Cy = floor(sum of the segment's pixel rows / its pixel count), Cx likewise (integers,
+ * full resolution), copied bit for bit.  An id below S without a pixel gives NaN in all four blocks; ids outside [0, S) are ignored.
+ * scratch: wvn_segpool_pyramid_scratch_bytes(B, S) bytes, cleared by the call.
+ *
+ * Every function returns WVN_ERR_ARG before any launch for a null pointer or a shape outside the above (the size queries return 0),
+ * WVN_ERR_WORKSPACE for a workspace or scratch buffer that is too small.
+ * ------------------------------------------------------------------------------------------- */
+#define WVN_CONV_IN_NHWC 0
+#define WVN_CONV_IN_FRAME_F32 1
+#define WVN_CONV_IN_FRAME_U8 2
+#define WVN_RESNET18_NCONV 20
+#define WVN_SEGPOOL_PYRAMID_MAX_SEGMENTS (1 << 20)
+size_t wvn_conv2d_pack_floats(int Cout, int Cin, int ksize);
+int wvn_conv2d_pack(const float* w, float* packed, int Cout, int Cin, int ksize, void* stream);
+int wvn_conv2d_bn_act(const void* in, int in_kind, const float* packed, const float* scale, const float* shift, const float* residual,
+                      int relu, float* out, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, void* stream);
+int wvn_maxpool3x3s2(const float* in, float* out, int B, int H, int W, int C, void* stream);
+size_t wvn_resnet18_pack_bytes(void);
+int wvn_resnet18_pack(const void* const* conv_w, const void* const* scale, const void* const* shift, void* packed, size_t packed_bytes,
+                      void* stream);
+size_t wvn_resnet18_workspace_bytes(int B, int H, int W);
+size_t wvn_resnet18_level_offset(int B, int H, int W, int level);
+int wvn_resnet18_forward(const void* packed, const void* frames, int frames_u8, int B, int H, int W, void* workspace,
+                         size_t workspace_bytes, void* stream);
+size_t wvn_segpool_pyramid_scratch_bytes(int B, int S);
+int wvn_segpool_pyramid(const float* feat1, const float* feat2, const float* feat3, const float* feat4, const int* seg, float* feat,
+                        void* scratch, size_t scratch_bytes, int B, int H, int W, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

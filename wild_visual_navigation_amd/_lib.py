@@ -262,6 +262,17 @@ _SIGNATURES = {
     "wvn_frame_max": ([_p, _i, _i, _ll, _p, _p], _i),
     "wvn_overlay": ([_p, _p], _i),
     "wvn_overlay_panels": ([_p, _p], _i),
+    "wvn_conv2d_pack_floats": ([_i, _i, _i], _sz),
+    "wvn_conv2d_pack": ([_p, _p, _i, _i, _i, _p], _i),
+    "wvn_conv2d_bn_act": ([_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),
+    "wvn_maxpool3x3s2": ([_p, _p, _i, _i, _i, _i, _p], _i),
+    "wvn_resnet18_pack_bytes": ([], _sz),
+    "wvn_resnet18_pack": ([_p, _p, _p, _p, _sz, _p], _i),
+    "wvn_resnet18_workspace_bytes": ([_i, _i, _i], _sz),
+    "wvn_resnet18_level_offset": ([_i, _i, _i, _i], _sz),
+    "wvn_resnet18_forward": ([_p, _p, _i, _i, _i, _i, _p, _sz, _p], _i),
+    "wvn_segpool_pyramid_scratch_bytes": ([_i, _i], _sz),
+    "wvn_segpool_pyramid": ([_p, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

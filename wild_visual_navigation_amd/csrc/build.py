@@ -21,7 +21,7 @@ SOURCES = [
     "api.hip", "vit_forward.hip", "gemm_bf16.hip", "gemm_a384.hip", "gemm_n384.hip", "mlp_fused.hip", "qkv_fused.hip", "gemm_proj.hip", "gemm_x3.hip", "gemm_a384_x3.hip", "gemm_n384_x3.hip", "gemm_fp8.hip", "gemm_fp8_dma.hip", "gemm_a768_fp8.hip", "fp8.hip", "gemm_f32.hip", "elementwise.hip", "attention_bf16.hip",
     "attention_x3.hip", "attention_f32.hip",
     "segments.hip", "stego.hip", "stego_linear.hip", "mlp.hip", "mlp_train.hip", "double_mlp.hip", "pixel_mlp.hip", "rnvp.hip", "rnvp_train.hip", "segment_predict.hip", "simple_gcn.hip", "simple_gcn_train.hip", "supervision.hip", "slic.hip", "slic_connectivity.hip", "wire.hip", "random_pixels.hip", "dense_sift.hip",
-    "dense_crf.hip", "dense_crf_permutohedral.hip", "overlay.hip",
+    "dense_crf.hip", "dense_crf_permutohedral.hip", "overlay.hip", "resnet.hip", "pyramid_pool.hip",
 ]
 # the kernels of the 16-bit-operand speed path are compiled twice (operand.h): bf16 operands, and fp16 operands (-> <name>_f16.o)
 DUAL_OPERAND = ["gemm_bf16.hip", "gemm_a384.hip", "gemm_n384.hip", "mlp_fused.hip", "qkv_fused.hip", "gemm_proj.hip", "attention_bf16.hip"]

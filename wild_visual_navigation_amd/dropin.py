@@ -7,7 +7,7 @@ After ``install()`` the reference's own import lines (quick_start.py:6-18, wvn_f
 wvn_learning_node.py:7-24) bind the MI355X classes:
 
     from wild_visual_navigation import WVN_ROOT_DIR
-    from wild_visual_navigation.feature_extractor import FeatureExtractor           (DinoInterface, StegoInterface, SegmentExtractor)
+    from wild_visual_navigation.feature_extractor import FeatureExtractor           (DinoInterface, StegoInterface, TorchVisionInterface, SegmentExtractor)
     from wild_visual_navigation.image_projector import ImageProjector
     from wild_visual_navigation.model import get_model                              (SimpleMLP, DoubleMLP, LinearRnvp, SimpleGCN)
     from wild_visual_navigation.utils import ConfidenceGenerator, Data, Batch, TraversabilityLoss, AnomalyLoss, WVNMode, make_plane ...

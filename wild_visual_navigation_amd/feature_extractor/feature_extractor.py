@@ -14,11 +14,14 @@ from .. import _lib, ops
 from .dino_interface import DinoInterface
 from .segment_extractor import SegmentExtractor
 from .stego_interface import StegoInterface
+from .torchvision_interface import TorchVisionInterface
 
 
 class FeatureExtractor:
     def __init__(self, device: str, segmentation_type: str = "slic", feature_type: str = "dino",
                  input_size: int = 448, **kwargs):
+        if feature_type == "torchvision":   # refused before anything is moved to the GPU
+            self._check_torchvision_args(device, segmentation_type, input_size, kwargs)
         self._device = torch.device(device)
         self._segmentation_type = segmentation_type
         self._feature_type = feature_type
@@ -65,10 +68,18 @@ class FeatureExtractor:
             # compute_sift concatenates the three colour channels' 128-d maps (:276-286): 384 is the width the features really have
             self._feature_dim = 3 * ops.DENSE_SIFT_DIM
             self._extractor = None
+        elif self._feature_type == "torchvision":
+            # the CNN baseline of the paper's ablation (slic100_resnet18.yaml): ResNet-18 stage maps pooled per segment at four scales
+            # (csrc/resnet.hip, csrc/pyramid_pool.hip).  The reference leaves feature_dim unset; 64 + 128 + 256 + 512 is what it yields
+            self._feature_dim = ops.PYRAMID_DIM
+            self._extractor = TorchVisionInterface(
+                device=device, model_type=kwargs.get("model_type", "resnet18"), input_size=input_size,
+                pretrained=kwargs.get("pretrained", True), pretrained_weights=kwargs.get("pretrained_weights"),
+                allow_synthetic=kwargs.get("allow_synthetic", False))
         elif self._feature_type == "none":
             self._extractor = None
         else:
-            # torchvision / histogram ablation extractors are outside the MI355X hot path
+            # the histogram ablation extractor raises NotImplementedError in the reference itself
             raise TypeError(f"Extractor[{self._feature_type}] not supported!")
 
         if self.segmentation_type == "slic":
@@ -109,10 +120,14 @@ class FeatureExtractor:
         """feature_extractor.py:95-128.  img [1,3,H,W] fp32 in [0,1], or the raw uint8 frame (then x/255 is fused into
         the backbone's patch gather: same features, a quarter of the upload).
         Returns (edges [2,E] i64, feat [S,D] f32, seg [H,W] i64, center [S,2] f32, dense [1,D,H,H] | None)."""
+        if self._feature_type == "torchvision":
+            self._extractor.check_frames(img, "extract")
         img = img.to(self._device)
         want_dense = kwargs.get("return_dense_features", False)
         if self._feature_type == "sift":
             return self._extract_sift(img, want_dense, **kwargs)
+        if self._feature_type == "torchvision":
+            return self._extract_pyramid(img, want_dense, **kwargs)
         if self._segmentation_type == "random":
             tokens = self._feature_tokens(img)
             H, W = img.shape[2:]
@@ -140,6 +155,7 @@ class FeatureExtractor:
         small kernels that do not fill the GPU; a throughput pipeline runs this stage for batch i+1 on one HIP stream while
         the rest of batch i runs on another (``extract_batch(img, backbone_out=...)``, bench.py)."""
         self._refuse_sift("backbone_stage")
+        self._refuse_pyramid("backbone_stage")
         img = img.to(self._device)
         if self._feature_type == "stego":
             return self._extractor.code_tokens(img)
@@ -151,6 +167,56 @@ class FeatureExtractor:
         if self._feature_type == "sift":
             raise _lib.WvnError(f"{who}: feature_type 'sift' has no patch-token stage (its features are computed at pixel resolution); "
                                 f"use predict_per_segment")
+
+    @staticmethod
+    def _check_torchvision_args(device, segmentation_type, input_size, kwargs):
+        """What feature_type "torchvision" does not serve, each refusal naming its argument (TorchVisionInterface refuses model_type and
+        input_size the same way; they are repeated here so that nothing is moved to the GPU first)."""
+        model_type = kwargs.get("model_type", "resnet18")
+        if model_type != "resnet18":
+            raise _lib.WvnError(f"feature_type 'torchvision': model_type '{model_type}' is not supported: only 'resnet18' (resnet50, "
+                                f"resnet50_dino and the EfficientNets need bottleneck or depthwise blocks)")
+        if not isinstance(input_size, int) or input_size < 32 or input_size % 32:
+            raise _lib.WvnError(f"feature_type 'torchvision': input_size={input_size} must be a positive multiple of 32")
+        if segmentation_type not in ("grid", "slic"):
+            raise _lib.WvnError(f"feature_type 'torchvision': segmentation_type '{segmentation_type}' is not supported: the multi-scale "
+                                f"pooling needs segments ('grid' or 'slic'), not 'random', 'stego' or 'none'")
+        if torch.device(device).type != "cuda":
+            raise _lib.WvnError(f"feature_type 'torchvision': device '{device}' is not a GPU; the HIP path has no CPU fallback")
+
+    def _refuse_pyramid(self, who):
+        """The ResNet-18 pyramid has four maps at four resolutions, not one patch-token map: the token stage and the per-pixel kernels
+        built on it do not apply.  Refused before any GPU work."""
+        if self._feature_type == "torchvision":
+            raise _lib.WvnError(f"{who}: feature_type 'torchvision' has no patch-token stage (its features are four maps at strides 4 to "
+                                f"32, pooled per segment); use predict_per_segment")
+
+    def _pyramid_dense(self):
+        """The reference's dict of dense maps (NCHW copies of the level maps of the last forward pass)."""
+        return {f"feat{i + 1}": m.permute(0, 3, 1, 2).contiguous() for i, m in enumerate(self._extractor._levels)}
+
+    def _extract_pyramid(self, img, want_dense, **kwargs):
+        """``extract`` for feature_type "torchvision": feat [S,960] from the pooling kernel on the level maps in the workspace; the dict
+        of dense maps is built only on request."""
+        edges, seg, center = self.compute_segments(img, **kwargs)
+        n_seg = center.shape[0]
+        levels = self._extractor.forward_levels(img)
+        feat = ops.segpool_pyramid(levels, seg[None], n_seg)[0]
+        return edges, feat, seg, center, (self._pyramid_dense() if want_dense else None)
+
+    def _extract_batch_pyramid(self, img, **kwargs):
+        """``extract_batch`` for feature_type "torchvision" (grid or slic segmentation): feat [B,S,960]."""
+        B, _, H, W = img.shape
+        if self._segmentation_type == "grid":
+            cell = kwargs.get("cell_size", 32)
+            seg = self.segment_grid(img, **kwargs)[0, 0].to(torch.int32)[None].expand(B, H, W).contiguous()
+            n_seg = (H // cell) * (W // cell)
+        else:
+            seg = ops.slic(img, self._slic_num_components, self._slic_compactness, enforce_connectivity=self._slic_enforce_connectivity,
+                           min_size_factor=self._slic_min_size_factor)
+            n_seg = ops.slic_num_clusters(H, W, self._slic_num_components)
+        feat = ops.segpool_pyramid(self._extractor.forward_levels(img), seg, n_seg)
+        return feat, seg, torch.full((B,), n_seg, dtype=torch.int32, device=self._device)
 
     def _extract_sift(self, img, want_dense, **kwargs):
         """``extract`` for feature_type "sift": the segment map as for every other feature type, feat from the fused descriptor +
@@ -203,12 +269,20 @@ class FeatureExtractor:
         connectivity pass over the B maps (ops.slic_enforce_connectivity: fragments below slic_min_size_factor of a superpixel go to a
         neighbour; ids stay cluster ids, emptied ids give NaN rows); the pass has no host synchronisation.  ``backbone_out``: the tokens ``backbone_stage(img)`` returned.
         feature_type "sift": grid, slic or random segmentation on H x W frames, feat [B,S,384] from the fused descriptor + segment-mean kernel
-        (``_extract_batch_sift``); there is no backbone stage, so ``backbone_out`` is refused."""
+        (``_extract_batch_sift``); there is no backbone stage, so ``backbone_out`` is refused.
+        feature_type "torchvision": grid or slic segmentation on input_size x input_size frames, feat [B,S,960] from the ResNet-18 level
+        maps and the pyramid pooling kernel (``_extract_batch_pyramid``); ``backbone_out`` is refused."""
+        if self._feature_type == "torchvision":
+            if backbone_out is not None:
+                self._refuse_pyramid("extract_batch(backbone_out=...)")
+            self._extractor.check_frames(img, "extract_batch")
         img = img.to(self._device)
         if self._feature_type == "sift":
             if backbone_out is not None:
                 self._refuse_sift("extract_batch(backbone_out=...)")
             return self._extract_batch_sift(img, **kwargs)
+        if self._feature_type == "torchvision":
+            return self._extract_batch_pyramid(img, **kwargs)
         B, _, H, W = img.shape
         G = self._grid()
         labels_patch = None  # [B,G,G] ids when the segment map is constant on every ViT patch
@@ -272,6 +346,7 @@ class FeatureExtractor:
         ``model.input_size`` must equal the extractor's ``feature_dim`` (WvnError otherwise).  Like the reference
         (dino_interface.py:87-90) the map is H x H for an H x W frame."""
         self._refuse_sift("predict_per_pixel")
+        self._refuse_pyramid("predict_per_pixel")
         img = img.to(self._device)
         self._check_per_pixel_model(model, "predict_per_pixel")
         rows, _ = self._per_pixel_tokens(img, model)
@@ -287,6 +362,7 @@ class FeatureExtractor:
         segmentation; dino, dinov2 or stego features; every precision.  SimpleMLP or LinearRnvp (trav = conf = confidence(-score), third map
         -score), anything else is refused before the backbone runs."""
         self._refuse_sift("predict_and_extract")
+        self._refuse_pyramid("predict_and_extract")
         img = img.to(self._device)
         self._check_per_pixel_model(model, "predict_and_extract")
         rows, tokens = self._per_pixel_tokens(img, model)
@@ -461,6 +537,8 @@ class FeatureExtractor:
             return None
         if self._feature_type == "sift":   # feature_extractor.py:276-286: [B,384,H,W], the frame as it is (no resize, crop or normalisation)
             return ops.dense_sift(img.to(self._device))
+        if self._feature_type == "torchvision":   # the dict feat1 .. feat4 of NCHW maps, as the reference's interface returns it
+            return self._extractor.inference(img)
         if self._feature_type == "stego":
             if self._stego_features_already_computed_in_segmentation:
                 self._stego_features_already_computed_in_segmentation = False
@@ -475,6 +553,9 @@ class FeatureExtractor:
         through the same segment-mean kernels (grid == image size)."""
         if self._feature_type in ["histogram"] or self._segmentation_type in ["none"]:
             return dense_features
+        if isinstance(dense_features, dict):   # feature_extractor.py:314-366: the multi-scale branch (feat1 .. feat4, NCHW, one frame)
+            levels = [dense_features[f"feat{i + 1}"].permute(0, 2, 3, 1).contiguous() for i in range(4)]
+            return ops.segpool_pyramid(levels, seg[None], int(seg.max().item()) + 1)[0]
         _lib.require_cuda(dense_features, "dense_features")
         _, D, H, W = dense_features.shape
         if H != W:

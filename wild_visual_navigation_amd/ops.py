@@ -101,6 +101,167 @@ def dense_sift_segpool(img: torch.Tensor, seg: torch.Tensor, n_seg: int, return_
     return (feat, cnt) if return_counts else feat
 
 
+CONV_IN_NHWC, CONV_IN_FRAME_F32, CONV_IN_FRAME_U8 = 0, 1, 2   # include/wvn_hip.h: WVN_CONV_IN_*
+RESNET18_NCONV = 20
+PYRAMID_CHANNELS = (64, 128, 256, 512)   # ResNet-18 stages at strides 4, 8, 16, 32
+PYRAMID_DIM = sum(PYRAMID_CHANNELS)      # 960
+
+
+def bn_scale_shift(weight, bias, running_mean, running_var, eps: float = 1e-5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Eval-mode BatchNorm folded to y = x * scale + shift: formed in float64 on the host, then rounded to fp32 (CPU tensors)."""
+    w, b, m, v = (t.detach().to("cpu", torch.float64) for t in (weight, bias, running_mean, running_var))
+    scale = w / torch.sqrt(v + eps)
+    return scale.float(), (b - m * scale).float()
+
+
+def conv2d_pack(weight: torch.Tensor) -> torch.Tensor:
+    """weight [Cout,Cin,k,k] fp32 on the GPU -> the packed [Kpad,Cout] image ``conv2d_bn_act`` reads (k = (ky, kx, cin) major)."""
+    require_cuda(weight, "weight")
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.dtype != torch.float32:
+        raise _lib.WvnError(f"conv2d_pack: weight must be fp32 [Cout,Cin,k,k], not {weight.dtype} {tuple(weight.shape)}")
+    Cout, Cin, k, _ = weight.shape
+    n = lib().wvn_conv2d_pack_floats(Cout, Cin, k)
+    if n == 0:
+        raise _lib.WvnError(f"conv2d_pack: unsupported shape {tuple(weight.shape)}")
+    packed = torch.empty(n // Cout, Cout, dtype=torch.float32, device=weight.device)
+    check(lib().wvn_conv2d_pack(ptr(weight.contiguous()), ptr(packed), Cout, Cin, k, stream()), "wvn_conv2d_pack")
+    return packed
+
+
+def conv2d_bn_act(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, ksize: int, stride: int, pad: int,
+                  residual: Optional[torch.Tensor] = None, relu: bool = True, frame: bool = False) -> torch.Tensor:
+    """Convolution + folded BatchNorm (+ residual) (+ ReLU) on the fp32-input MFMA (csrc/resnet.hip).  x: an NHWC fp32 activation
+    [B,H,W,Cin] (Cin % 32 == 0), or with ``frame=True`` an NCHW frame [B,3,H,W] (fp32 in [0,1] or uint8) that is normalised with the
+    ImageNet mean / std on load (the stem).  packed: ``conv2d_pack(weight)``.  Returns NHWC [B,OH,OW,Cout]; residual has that shape."""
+    for t, n in ((x, "x"), (packed, "packed"), (scale, "scale"), (shift, "shift")):
+        require_cuda(t, n)
+    if x.dim() != 4:
+        raise _lib.WvnError(f"conv2d_bn_act: x must have four dimensions, not {tuple(x.shape)}")
+    if frame:
+        B, Cin, H, W = x.shape
+        kind = CONV_IN_FRAME_U8 if x.dtype == torch.uint8 else CONV_IN_FRAME_F32
+        x = x.contiguous() if x.dtype == torch.uint8 else x.contiguous().float()
+    else:
+        B, H, W, Cin = x.shape
+        kind = CONV_IN_NHWC
+        if x.dtype != torch.float32:
+            raise _lib.WvnError(f"conv2d_bn_act: fp32 activations expected, got {x.dtype}")
+        x = x.contiguous()
+    Cout = packed.shape[1]
+    if packed.shape[0] * Cout != lib().wvn_conv2d_pack_floats(Cout, Cin, ksize) or scale.numel() != Cout or shift.numel() != Cout:
+        raise _lib.WvnError(f"conv2d_bn_act: packed {tuple(packed.shape)} / scale / shift do not fit Cin={Cin}, ksize={ksize}")
+    if H + 2 * pad < ksize or W + 2 * pad < ksize or stride < 1:
+        raise _lib.WvnError(f"conv2d_bn_act: ksize={ksize} does not fit {H} x {W} with pad={pad}")
+    OH, OW = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    out = torch.empty(B, OH, OW, Cout, dtype=torch.float32, device=x.device)
+    if residual is not None:
+        require_cuda(residual, "residual")
+        if tuple(residual.shape) != tuple(out.shape) or residual.dtype != torch.float32:
+            raise _lib.WvnError(f"conv2d_bn_act: residual must be fp32 {tuple(out.shape)}, not {residual.dtype} {tuple(residual.shape)}")
+        residual = residual.contiguous()
+    check(lib().wvn_conv2d_bn_act(ptr(x), kind, ptr(packed.contiguous()), ptr(scale.contiguous().float()), ptr(shift.contiguous().float()),
+                                  ptr(residual), int(bool(relu)), ptr(out), B, H, W, Cin, Cout, ksize, stride, pad, stream()),
+          "wvn_conv2d_bn_act")
+    return out
+
+
+def maxpool3x3s2(x: torch.Tensor) -> torch.Tensor:
+    """F.max_pool2d(kernel 3, stride 2, padding 1) on an NHWC fp32 activation [B,H,W,C] (the padding is -inf)."""
+    require_cuda(x, "x")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise _lib.WvnError(f"maxpool3x3s2: fp32 [B,H,W,C] expected, got {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
+    B, H, W, Cc = x.shape
+    out = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc, dtype=torch.float32, device=x.device)
+    check(lib().wvn_maxpool3x3s2(ptr(x), ptr(out), B, H, W, Cc, stream()), "wvn_maxpool3x3s2")
+    return out
+
+
+def resnet18_pack(weights, scales, shifts) -> torch.Tensor:
+    """The packed image of ResNet-18 for ``resnet18_forward``: three lists of RESNET18_NCONV GPU tensors in the order of
+    include/wvn_hip.h (weights [Cout,Cin,k,k], folded BatchNorm scale / shift [Cout])."""
+    if not (len(weights) == len(scales) == len(shifts) == RESNET18_NCONV):
+        raise _lib.WvnError(f"resnet18_pack: {RESNET18_NCONV} convolutions expected")
+    keep = []
+    arrays = []
+    for ts in (weights, scales, shifts):
+        arr = (C.c_void_p * RESNET18_NCONV)()
+        for i, t in enumerate(ts):
+            require_cuda(t, "resnet18 parameter")
+            t = t.contiguous().float()
+            keep.append(t)
+            arr[i] = t.data_ptr()
+        arrays.append(arr)
+    nbytes = lib().wvn_resnet18_pack_bytes()
+    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=weights[0].device)
+    check(lib().wvn_resnet18_pack(arrays[0], arrays[1], arrays[2], ptr(packed), nbytes, stream()), "wvn_resnet18_pack")
+    torch.cuda.current_stream().synchronize()   # `keep` may be released after the copies have run
+    return packed
+
+
+def resnet18_workspace(B: int, H: int, W: int, device) -> torch.Tensor:
+    nbytes = lib().wvn_resnet18_workspace_bytes(B, H, W)
+    if nbytes == 0:
+        raise _lib.WvnError(f"resnet18: frames [B={B},3,{H},{W}] are not supported (H and W must be multiples of 32)")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def resnet18_levels(workspace: torch.Tensor, B: int, H: int, W: int):
+    """The four NHWC level maps [B,H/s,W/s,C] (s = 4, 8, 16, 32) as views of a ``resnet18_forward`` workspace."""
+    out = []
+    for l, Cc in enumerate(PYRAMID_CHANNELS, start=1):
+        s = 2 << l
+        off = lib().wvn_resnet18_level_offset(B, H, W, l) // 4
+        out.append(workspace[off: off + B * (H // s) * (W // s) * Cc].view(B, H // s, W // s, Cc))
+    return out
+
+
+def resnet18_forward(packed: torch.Tensor, img: torch.Tensor, workspace: Optional[torch.Tensor] = None):
+    """ResNet-18 (eval mode) on frames [B,3,H,W] (fp32 in [0,1] or uint8; H, W multiples of 32) -> (the four NHWC level maps as views of
+    the workspace, the workspace).  A given workspace must be ``resnet18_workspace(B, H, W, device)`` or larger."""
+    require_cuda(img, "img")
+    require_cuda(packed, "packed")
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise _lib.WvnError(f"resnet18_forward: img must be [B,3,H,W], not {tuple(img.shape)}")
+    img = img.contiguous() if img.dtype == torch.uint8 else img.contiguous().float()
+    B, _, H, W = img.shape
+    if workspace is None:
+        workspace = resnet18_workspace(B, H, W, img.device)
+    check(lib().wvn_resnet18_forward(ptr(packed), ptr(img), int(img.dtype == torch.uint8), B, H, W, ptr(workspace),
+                                     workspace.numel() * workspace.element_size(), stream()), "wvn_resnet18_forward")
+    return resnet18_levels(workspace, B, H, W), workspace
+
+
+def segpool_pyramid(levels, seg: torch.Tensor, n_seg: int) -> torch.Tensor:
+    """The multi-scale segment pooling (feature_extractor.py:314-366 of the reference): levels = four NHWC maps [B,H/s,W/s,C] with
+    C = 64, 128, 256, 512 at s = 4, 8, 16, 32, seg [B,H,W] int -> feat [B,n_seg,960].  Per level the mean over the cells of seg[::s, ::s]
+    that carry the id; where none does, the cell holding the segment's centroid; NaN rows for ids without a pixel (include/wvn_hip.h)."""
+    require_cuda(seg, "seg")
+    if seg.dim() != 3:
+        raise _lib.WvnError(f"segpool_pyramid: seg must be [B,H,W], not {tuple(seg.shape)}")
+    B, H, W = seg.shape
+    if len(levels) != 4 or H % 32 or W % 32:
+        raise _lib.WvnError(f"segpool_pyramid: four level maps and H, W multiples of 32 expected (H={H}, W={W})")
+    maps = []
+    for l, (m, Cc) in enumerate(zip(levels, PYRAMID_CHANNELS)):
+        s = 4 << l
+        require_cuda(m, "level map")
+        if tuple(m.shape) != (B, H // s, W // s, Cc) or m.dtype != torch.float32:
+            raise _lib.WvnError(f"segpool_pyramid: level {l + 1} must be fp32 NHWC {(B, H // s, W // s, Cc)}, not {m.dtype} {tuple(m.shape)}")
+        maps.append(m.contiguous())
+    if n_seg < 1:
+        raise _lib.WvnError(f"segpool_pyramid: n_seg={n_seg} must be >= 1")
+    seg = _i32(seg).contiguous()
+    nbytes = lib().wvn_segpool_pyramid_scratch_bytes(B, int(n_seg))
+    if nbytes == 0:
+        raise _lib.WvnError(f"segpool_pyramid: B={B}, n_seg={n_seg} not supported")
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=seg.device)
+    feat = torch.empty(B, n_seg, PYRAMID_DIM, dtype=torch.float32, device=seg.device)
+    check(lib().wvn_segpool_pyramid(ptr(maps[0]), ptr(maps[1]), ptr(maps[2]), ptr(maps[3]), ptr(seg), ptr(feat), ptr(scratch), nbytes, B, H,
+                                    W, int(n_seg), stream()), "wvn_segpool_pyramid")
+    return feat
+
+
 def upsample_nearest_labels(labels: torch.Tensor, out_size: int) -> torch.Tensor:
     """labels [B,G,G] int32 -> [B,H,H] int32 (stego_interface.py:108-109)."""
     require_cuda(labels, "labels")
