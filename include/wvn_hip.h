@@ -1100,6 +1100,63 @@ int wvn_frame_max(const void* img, int img_u8, int B, long long n, float* frame_
 int wvn_overlay(const wvn_overlay_desc* d, void* stream);
 int wvn_overlay_panels(const wvn_overlay_desc* d, void* stream);
 
+/* ---- evaluation metrics (csrc/metrics.hip; DESIGN.md section 4 "Evaluation metrics"; tests/metrics_ref.py is the definition) ----
+ * ROC at T thresholds, binned and exact AUROC, accuracy -- what the reference's MetricLogger takes from torchmetrics -- from integer
+ * counts.  PARITY WITH THE torchmetrics PACKAGE IS UNPINNED (the package is absent); the definitions restate its published behaviour.
+ *
+ * thresholds: fp32 [T], ascending, 2 <= T <= WVN_METRIC_MAX_T -- torch.linspace(0, 1, T) made on the CPU; an input, never recomputed.
+ * Bin of a score p: k(p) = #{t : thresholds[t] <= p} in 0..T (fp32 comparisons against the table; -inf -> 0, +inf -> T).
+ * Target value: u8 / i32 as they are, fp32 truncated toward zero (`.type(torch.long)`); 1 positive, 0 negative, everything else
+ * (NaN, other integers, ignore_index when has_ignore) skipped.
+ * A source is WVN_METRIC_DENSE ([B][H][W]) or WVN_METRIC_PER_SEGMENT: element (row(b, s) * stride) of a table, s = seg[b][y][x] (seg_bytes 4: int32 ids, 8: int64 ids),
+ * row(b, s) = seg_off[b] + s with seg_off[b + 1] - seg_off[b] segments in frame b (seg_off int64 [B + 1], ragged graphs), or
+ * b * S + s with S segments (seg_off NULL).  Where any source of the call is per-segment, a pixel whose id is < 0 or >= the frame's
+ * segment count is skipped for every pair.
+ * State of pair (i, j) = score i x target j, int64 words at state + (i * n_targets + j) * state_stride, ADDED INTO:
+ *   [0, 2 (T + 1))     hist[k][c]: pixels of bin k and class c
+ *   + 0..3             cm[c][p > tau] (strict)
+ *   + 4, 5, 6          n_nan (NaN score: not binned), n_ignored (target or segment skipped), n_out_of_range (p < 0 or p > 1: binned all the same)
+ *   + 7                reserved            (state_stride >= 2 (T + 1) + WVN_METRIC_STATE_TAIL)
+ * A skipped pixel is counted once, in n_ignored, whatever its score; sum(hist) + n_nan + n_ignored = pixels.
+ * seg_counts (optional, needs seg): int32 [rows][n_targets][2], ADDED INTO: pixels of segment row with target j in class c.
+ * wvn_metric_accumulate: one launch, integer atomics only, no host synchronisation; the result depends on neither the launch
+ * geometry nor the arrival order.  WVN_ERR_ARG before the launch: B H W outside [1, 2^31), T out of range, a per-segment source
+ * without seg, a NULL or misaligned required pointer, counts outside 1..2, B S >= 2^27, seg with seg_bytes other than 4 / 8.
+ *
+ * wvn_metric_curve: one pair state -> fpr, tpr, thr fp64 [T] in ascending fpr (index i is threshold T - 1 - i):
+ * tps[t] = sum_{k > t} hist[k][1], fps likewise, tpr = tps / P (0 where P == 0), fpr = fps / N; scal[0] = the binned AUROC =
+ * sum_{i = 1}^{T - 1} ((fpr[i] - fpr[i-1]) * (tpr[i] + tpr[i-1])) * 0.5 added in ascending i (0 when degenerate), scal[1] = the
+ * accuracy (cm[1][1] + cm[0][0]) / sum cm (0 when empty); cnt = {P, N, degenerate (P == 0 or N == 0)}.  One launch.
+ *
+ * wvn_metric_auroc_weighted: E <= 2^24 entries (score fp32, pos, neg int64 >= 0) SORTED by score (either direction); entries of equal
+ * score form a group; U2 = sum_groups neg_g (2 pos_before_g + pos_g); scal[0] = double(U2) / double(2 P N) -- for descending scores the
+ * AUROC -- 0 when degenerate; cnt = {U2, P, N, degenerate}.  NaN-scored entries count nothing.  One launch, no atomics. */
+#define WVN_METRIC_MAX_T 8192
+#define WVN_METRIC_STATE_TAIL 8
+#define WVN_METRIC_DENSE 0
+#define WVN_METRIC_PER_SEGMENT 1
+#define WVN_METRIC_U8 0
+#define WVN_METRIC_I32 1
+#define WVN_METRIC_F32 2
+typedef struct {
+  const float* score[2];
+  const void* target[2];
+  const void* seg;
+  const long long* seg_off;
+  const float* thresholds;
+  long long* state;
+  int* seg_counts;
+  long long score_stride[2], target_stride[2], state_stride;
+  float tau;
+  int score_kind[2], target_kind[2], target_dtype[2];
+  int n_scores, n_targets, B, H, W, S, T, has_ignore, ignore_index, seg_bytes;
+} wvn_metric_desc;
+int wvn_metric_accumulate(const wvn_metric_desc* d, void* stream);
+int wvn_metric_curve(const long long* state, const float* thresholds, int T, double* fpr, double* tpr, double* thr, double* scal,
+                     long long* cnt, void* stream);
+int wvn_metric_auroc_weighted(const float* score, const long long* pos, const long long* neg, long long E, double* scal,
+                              long long* cnt, void* stream);
+
 /* ---- step scheduling (no reference counterpart: the reference runs one frame at a time on one CUDA stream,
  * wild_visual_navigation_ros/scripts/wvn_feature_extractor_node.py:319-363) ----
  * A HIP stream whose kernels may only occupy the compute units named by `mask` (bit i of the `words` 32-bit words = CU i in the

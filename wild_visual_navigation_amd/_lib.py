@@ -99,6 +99,18 @@ class OverlayDesc(C.Structure):
                                        "boundary_bytes", "S", "lut_u8", "N", "alpha", "boundary_alpha")]
 
 
+class MetricDesc(C.Structure):
+    """include/wvn_hip.h: wvn_metric_desc."""
+    _fields_ = [("score", C.c_void_p * 2), ("target", C.c_void_p * 2), ("seg", C.c_void_p), ("seg_off", C.c_void_p),
+                ("thresholds", C.c_void_p), ("state", C.c_void_p), ("seg_counts", C.c_void_p),
+                ("score_stride", C.c_longlong * 2), ("target_stride", C.c_longlong * 2), ("state_stride", C.c_longlong),
+                ("tau", C.c_float), ("score_kind", C.c_int * 2), ("target_kind", C.c_int * 2), ("target_dtype", C.c_int * 2)] + \
+               [(n, C.c_int) for n in ("n_scores", "n_targets", "B", "H", "W", "S", "T", "has_ignore", "ignore_index", "seg_bytes")]
+
+
+METRIC_MAX_T, METRIC_STATE_TAIL = 8192, 8
+METRIC_DENSE, METRIC_PER_SEGMENT = 0, 1
+METRIC_U8, METRIC_I32, METRIC_F32 = 0, 1, 2
 OVERLAY_MAX_COLOURS, OVERLAY_MAX_MAPS = 1024, 4
 OVERLAY_VALUES, OVERLAY_LABELS, OVERLAY_SEGMENTS = 0, 1, 2
 MLP_KIND_DOUBLE = 1   # include/wvn_hip.h: WVN_MLP_KIND_DOUBLE (MlpDesc.reserved)
@@ -262,6 +274,9 @@ _SIGNATURES = {
     "wvn_frame_max": ([_p, _i, _i, _ll, _p, _p], _i),
     "wvn_overlay": ([_p, _p], _i),
     "wvn_overlay_panels": ([_p, _p], _i),
+    "wvn_metric_accumulate": ([_p, _p], _i),
+    "wvn_metric_curve": ([_p, _p, _i, _p, _p, _p, _p, _p, _p], _i),
+    "wvn_metric_auroc_weighted": ([_p, _p, _p, _ll, _p, _p, _p], _i),
     "wvn_conv2d_pack_floats": ([_i, _i, _i], _sz),
     "wvn_conv2d_pack": ([_p, _p, _i, _i, _i, _p], _i),
     "wvn_conv2d_bn_act": ([_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),

@@ -10,7 +10,7 @@ wvn_learning_node.py:7-24) bind the MI355X classes:
     from wild_visual_navigation.feature_extractor import FeatureExtractor           (DinoInterface, StegoInterface, TorchVisionInterface, SegmentExtractor)
     from wild_visual_navigation.image_projector import ImageProjector
     from wild_visual_navigation.model import get_model                              (SimpleMLP, DoubleMLP, LinearRnvp, SimpleGCN)
-    from wild_visual_navigation.utils import ConfidenceGenerator, Data, Batch, TraversabilityLoss, AnomalyLoss, WVNMode, make_plane ...
+    from wild_visual_navigation.utils import ConfidenceGenerator, Data, Batch, TraversabilityLoss, AnomalyLoss, WVNMode, make_plane, MetricLogger ...
     from wild_visual_navigation.traversability_estimator import TraversabilityEstimator, MissionNode, SupervisionNode, graphs
     from wild_visual_navigation.cfg import ExperimentParams
     from wild_visual_navigation.visu import LearningVisualizer                       (stand-alone mode, or install(visu=True))
@@ -32,7 +32,7 @@ import types
 HOT = ("feature_extractor", "model", "traversability_estimator", "image_projector", "cfg")
 # names of wild_visual_navigation.utils that belong to the hot path (the rest of utils stays the reference's)
 UTILS_HOT = ("Data", "Batch", "ConfidenceGenerator", "TraversabilityLoss", "AnomalyLoss", "WVNMode", "make_plane",
-             "make_dense_plane", "make_polygon_from_points")
+             "make_dense_plane", "make_polygon_from_points", "MetricLogger", "BinaryROC", "BinaryAUROC", "BinaryAccuracy")
 
 
 def _alias_submodules(pkg_mod, alias: str) -> None:

@@ -1276,3 +1276,192 @@ def overlay_panels(img: torch.Tensor, maps, lut: Optional[torch.Tensor] = None, 
     kind = _lib.OVERLAY_LABELS if labels else (_lib.OVERLAY_SEGMENTS if seg is not None else _lib.OVERLAY_VALUES)
     return _overlay_call("overlay_panels", img, maps, kind, seg, lut, alpha, overlay_mask, boundary_seg, boundary_alpha, unit_range,
                          out, 1)
+
+
+# ---- evaluation metrics (csrc/metrics.hip; include/wvn_hip.h "evaluation metrics"; tests/metrics_ref.py) ----------------------
+class PerSegment:
+    """Marks a source of ``metric_accumulate`` as a per-segment table, gathered through ``seg`` on load: ``[B,S]`` (row b S + s),
+    or with ``seg_off`` any tensor whose first dimension is the concatenated segments (row seg_off[b] + s; column 0 of a matrix)."""
+
+    def __init__(self, table: torch.Tensor):
+        self.table = table
+
+
+def metric_state_words(T: int) -> int:
+    return 2 * (int(T) + 1) + _lib.METRIC_STATE_TAIL
+
+
+def metric_state(n_pairs: int, T: int, device) -> torch.Tensor:
+    """Zeroed pair states int64 [n_pairs][2 (T + 1) + 8]: hist [T+1][2], cm [2][2], n_nan, n_ignored, n_out_of_range, reserved."""
+    return torch.zeros(int(n_pairs), metric_state_words(T), dtype=torch.int64, device=device)
+
+
+_METRIC_DTYPES = {torch.uint8: _lib.METRIC_U8, torch.bool: _lib.METRIC_U8, torch.int32: _lib.METRIC_I32, torch.float32: _lib.METRIC_F32}
+
+
+def metric_accumulate(state: torch.Tensor, thresholds: torch.Tensor, scores, targets, seg: Optional[torch.Tensor] = None,
+                      seg_off: Optional[torch.Tensor] = None, tau: float = 0.5, ignore_index: Optional[int] = None,
+                      seg_counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The fused pixel pass: every (score, target) pair state of ``state`` [len(scores) * len(targets)][words] is added into, in one
+    launch.  A source is a dense map ``[B,H,W]`` / ``[N]`` (fp32 scores; uint8, bool, int32 or fp32 targets) or ``PerSegment(table)``
+    with ``seg`` ``[B,H,W]`` (int32 or int64 ids, read as they are).  ``seg_counts`` int32 ``[rows][len(targets)][2]`` (optional) receives the per-segment class counts."""
+    scores, targets = list(scores), list(targets)
+    if not 1 <= len(scores) <= 2 or not 1 <= len(targets) <= 2:
+        raise _lib.WvnError("metric_accumulate: one or two scores and one or two targets per call")
+    require_cuda(state, "state")
+    require_cuda(thresholds, "thresholds")
+    T = thresholds.numel()
+    if thresholds.dtype != torch.float32 or not thresholds.is_contiguous():
+        raise _lib.WvnError("metric_accumulate: thresholds must be a contiguous fp32 vector")
+    words = metric_state_words(T)
+    if state.dtype != torch.int64 or state.dim() != 2 or state.shape[0] != len(scores) * len(targets) or state.shape[1] < words \
+            or state.stride(1) != 1:
+        raise _lib.WvnError(f"metric_accumulate: state must be int64 [{len(scores) * len(targets)}][>= {words}]")
+    shape = None
+    if seg is not None:
+        require_cuda(seg, "seg")
+        if seg.dim() == 2:
+            seg = seg[None]
+        if seg.dim() != 3:
+            raise _lib.WvnError(f"metric_accumulate: seg must be [B,H,W], not {tuple(seg.shape)}")
+        seg = (seg if seg.dtype in (torch.int32, torch.int64) else _i32(seg)).contiguous()   # int64 ids (the reference's graphs) are read as they are
+        shape = tuple(seg.shape)
+    for t in scores + targets:
+        if not isinstance(t, PerSegment):
+            sh = tuple(t.shape) if t.dim() == 3 else (1, 1, t.numel())
+            if t.dim() not in (1, 3):
+                raise _lib.WvnError(f"metric_accumulate: a dense source must be [B,H,W] or [N], not {tuple(t.shape)}")
+            if shape is None:
+                shape = sh
+            if sh != shape:
+                raise _lib.WvnError(f"metric_accumulate: source shapes differ: {sh} and {shape}")
+    if shape is None:
+        raise _lib.WvnError("metric_accumulate: per-segment sources need seg")
+    B, H, W = shape
+    d = _lib.MetricDesc()
+    keep = []
+    S = 0
+    table_rows = []   # with seg_off: the rows of every per-segment table (and of seg_counts) must agree
+    if seg_off is not None:
+        require_cuda(seg_off, "seg_off")
+        seg_off = seg_off.to(torch.int64).contiguous()
+        if seg_off.numel() != B + 1:
+            raise _lib.WvnError(f"metric_accumulate: seg_off must hold B + 1 = {B + 1} offsets")
+        keep.append(seg_off)
+
+    def source(t, name, is_score):
+        nonlocal S
+        if isinstance(t, PerSegment):
+            tab = t.table
+            require_cuda(tab, name)
+            if seg is None:
+                raise _lib.WvnError(f"metric_accumulate: {name} is per-segment but seg is missing")
+            if seg_off is None:
+                if tab.dim() != 2 or tab.shape[0] != B:
+                    raise _lib.WvnError(f"metric_accumulate: per-segment {name} must be [B,S] (or pass seg_off), not {tuple(tab.shape)}")
+                if S and tab.shape[1] != S:
+                    raise _lib.WvnError("metric_accumulate: per-segment sources differ in S")
+                S = int(tab.shape[1])
+                tab = tab.contiguous()
+                stride = 1
+            else:
+                if tab.dim() == 2:
+                    tab = tab[:, 0]
+                if tab.dim() != 1:
+                    raise _lib.WvnError(f"metric_accumulate: per-segment {name} must be [N] or [N,C] with seg_off")
+                table_rows.append(int(tab.shape[0]))
+                stride = int(tab.stride(0)) if tab.numel() > 1 else 1
+                if stride < 1:
+                    tab, stride = tab.contiguous(), 1
+            kind = _lib.METRIC_PER_SEGMENT
+        else:
+            require_cuda(t, name)
+            tab, stride, kind = t.contiguous(), 1, _lib.METRIC_DENSE
+        if is_score:
+            if tab.dtype != torch.float32:
+                tab = tab.float()
+                stride = int(tab.stride(0)) if (kind == _lib.METRIC_PER_SEGMENT and tab.dim() == 1 and tab.numel() > 1) else 1
+            dt = _lib.METRIC_F32
+        else:
+            if tab.dtype not in _METRIC_DTYPES:
+                if tab.dtype.is_floating_point:
+                    tab = tab.float()
+                else:   # wider integers: every value that is no label becomes one value that is none
+                    keepv = (tab == 0) | (tab == 1)
+                    if ignore_index is not None:
+                        keepv = keepv & (tab != int(ignore_index))
+                    tab = torch.where(keepv, tab, torch.full_like(tab, 2)).to(torch.uint8)
+                if kind == _lib.METRIC_PER_SEGMENT and tab.dim() == 1 and tab.numel() > 1:
+                    stride = int(tab.stride(0))
+            dt = _METRIC_DTYPES[tab.dtype]
+        keep.append(tab)
+        return ptr(tab), kind, stride, dt
+
+    for i, t in enumerate(scores):
+        d.score[i], d.score_kind[i], d.score_stride[i], _ = source(t, f"scores[{i}]", True)
+    for j, t in enumerate(targets):
+        d.target[j], d.target_kind[j], d.target_stride[j], d.target_dtype[j] = source(t, f"targets[{j}]", False)
+    if seg is not None and seg_off is None and S == 0:
+        S = 1 if seg_counts is None else int(seg_counts.shape[0]) // B
+    if seg_counts is not None:
+        require_cuda(seg_counts, "seg_counts")
+        if seg is None or seg_counts.dtype != torch.int32 or not seg_counts.is_contiguous() or seg_counts.dim() != 3 \
+                or tuple(seg_counts.shape[1:]) != (len(targets), 2) or (seg_off is None and seg_counts.shape[0] != B * S):
+            raise _lib.WvnError(f"metric_accumulate: seg_counts must be contiguous int32 [rows][{len(targets)}][2] and needs seg")
+        if seg_off is not None:
+            table_rows.append(int(seg_counts.shape[0]))
+    if len(set(table_rows)) > 1:
+        raise _lib.WvnError(f"metric_accumulate: the per-segment tables and seg_counts differ in their rows: {table_rows}")
+    if ignore_index is not None and not -2 ** 31 <= int(ignore_index) < 2 ** 31:
+        raise _lib.WvnError("metric_accumulate: ignore_index must fit 32 bits")
+    d.seg, d.seg_off, d.thresholds, d.state, d.seg_counts = ptr(seg), ptr(seg_off), ptr(thresholds), ptr(state), ptr(seg_counts)
+    d.state_stride = int(state.stride(0))
+    d.tau = float(tau)
+    d.n_scores, d.n_targets, d.B, d.H, d.W, d.S, d.T = len(scores), len(targets), B, H, W, S, T
+    d.has_ignore, d.ignore_index = int(ignore_index is not None), int(ignore_index or 0)
+    d.seg_bytes = 0 if seg is None else seg.element_size()
+    check(lib().wvn_metric_accumulate(C.byref(d), stream()), "wvn_metric_accumulate")
+    return state
+
+
+def metric_curve(state: torch.Tensor, thresholds: torch.Tensor):
+    """One pair state (int64 [words]) -> (fpr, tpr, thresholds) fp64 [T] in ascending fpr, scal fp64 [2] = {binned AUROC, accuracy},
+    cnt int64 [3] = {P, N, degenerate}: all on the device, one launch."""
+    require_cuda(state, "state")
+    require_cuda(thresholds, "thresholds")
+    T = thresholds.numel()
+    if state.dtype != torch.int64 or state.dim() != 1 or state.numel() < metric_state_words(T) or not state.is_contiguous():
+        raise _lib.WvnError(f"metric_curve: state must be a contiguous int64 vector of >= {metric_state_words(T)} words")
+    if thresholds.dtype != torch.float32 or not thresholds.is_contiguous():
+        raise _lib.WvnError("metric_curve: thresholds must be a contiguous fp32 vector")
+    dev = state.device
+    curves = torch.empty(3, T, dtype=torch.float64, device=dev)
+    scal = torch.empty(2, dtype=torch.float64, device=dev)
+    cnt = torch.empty(3, dtype=torch.int64, device=dev)
+    check(lib().wvn_metric_curve(ptr(state), ptr(thresholds), T, ptr(curves[0]), ptr(curves[1]), ptr(curves[2]), ptr(scal), ptr(cnt),
+                                 stream()), "wvn_metric_curve")
+    return curves[0], curves[1], curves[2], scal, cnt
+
+
+def metric_auroc_weighted(score: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor):
+    """Exact AUROC of weighted entries (score fp32, pos / neg pixel counts) -> scal fp64 [1], cnt int64 [4] = {U2, P, N, degenerate}.
+    The entries are sorted here (torch.sort: plumbing); ties, prefixes and U2 are the kernel's.  No entries: the degenerate result."""
+    require_cuda(score, "score")
+    require_cuda(pos, "pos")
+    require_cuda(neg, "neg")
+    E = score.numel()
+    if pos.numel() != E or neg.numel() != E:
+        raise _lib.WvnError("metric_auroc_weighted: score, pos and neg differ in length")
+    if E > 2 ** 24:
+        raise _lib.WvnError(f"metric_auroc_weighted: at most 2^24 entries, got {E}")
+    dev = score.device
+    scal = torch.zeros(1, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(4, dtype=torch.int64, device=dev)
+    if E == 0:
+        cnt[3] = 1
+        return scal, cnt
+    s, order = torch.sort(score.reshape(-1).float(), descending=True)
+    p = pos.reshape(-1).to(torch.int64)[order].contiguous()
+    n = neg.reshape(-1).to(torch.int64)[order].contiguous()
+    check(lib().wvn_metric_auroc_weighted(ptr(s), ptr(p), ptr(n), E, ptr(scal), ptr(cnt), stream()), "wvn_metric_auroc_weighted")
+    return scal, cnt
