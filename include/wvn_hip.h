@@ -1100,6 +1100,46 @@ int wvn_frame_max(const void* img, int img_u8, int B, long long n, float* frame_
 int wvn_overlay(const wvn_overlay_desc* d, void* stream);
 int wvn_overlay_panels(const wvn_overlay_desc* d, void* stream);
 
+/* ---- overlays: vector primitives (csrc/draw.hip; DESIGN.md section 4 "Overlays: vector primitives"; tests/visu_draw_ref.py is
+ * the same statement in plain loops, tests/test_visu_draw_host.py holds it to PIL.ImageDraw) ----
+ * What plot_traversability_graph, plot_graph_result, plot_optical_flow and plot_sparse_optical_flow of the reference draw with
+ * PIL.ImageDraw, painted in place on a canvas of packed RGB bytes: pixel (y, x) of panel k of frame b at
+ * canvas[b * frame_bytes + y * row_bytes + 3 * (k * Wp + x)], P panels of width Wp, canvas at any byte address (the layout of
+ * wvn_overlay's `out`: a draw can run on an overlay result or on a column slice of a wider image).
+ * Primitive i of N: kinds[i], points[i] = {x0, y0, x1, y1} fp32 in PANEL-LOCAL pixel coordinates, colours[i] = {r, g, b} bytes,
+ * frame[i] in [0, B), panel[i] in [0, P).  Every coordinate is truncated toward zero as a double, as PIL's (int) cast does.
+ *   WVN_DRAW_LINE   ImageDraw.line(width 0 / 1): Bresenham from the first to the second truncated end point, both painted, no swap;
+ *                   the major axis is x when |dx| > |dy|; error 2 minor - major, a minor step when it is >= 0.
+ *   WVN_DRAW_LINE2  ImageDraw.line(width 2): the polygon (x0, y0 + ey), (x1, y1 + ey), (x1 + ex, y1), (x0 + ex, y0) with
+ *                   ex = sign(dy) if 3 dy^2 > dx^2 else 0, ey = sign(dx) if 3 dx^2 > dy^2 else 0, filled by Pillow's scanline rule
+ *                   (fp32 edge slopes); zero length: one pixel.
+ *   WVN_DRAW_DISC   ImageDraw.ellipse([cx - 5, cy - 5, cx + 5, cy + 5], fill): the centre is (x0, y0), (x1, y1) is not read; the
+ *                   corners are computed in double from the fp32 centre and truncated; the box is 9 or 10 wide and high, and pixel
+ *                   (u, v) of a box (w, h) is painted iff min(u, w - u) + min(v, h - v) >= 3.
+ * A primitive paints only inside its own panel.  A pixel gets the colour of the highest-index primitive that covers it; a pixel no
+ * primitive covers is not written.  Defined beyond PIL: a primitive one of whose coordinates is not finite or truncates outside
+ * [-32768, 32767] (for a disc: the box corners), of an unknown kind, or with frame / panel outside the canvas is skipped, and
+ * *skipped (int, optional) is incremented once for it.
+ * One launch, stream-ordered, no host synchronisation, no workspace; N == 0 launches nothing.  WVN_ERR_ARG before anything is
+ * launched: a NULL canvas (or list, when N > 0), N outside [0, WVN_DRAW_MAX_PRIMITIVES], B outside [1, 65535], P outside
+ * [1, WVN_OVERLAY_MAX_MAPS + 1], H or Wp < 1, a row pitch smaller than the panels, a frame pitch smaller than a frame. */
+#define WVN_DRAW_MAX_PRIMITIVES 65536
+#define WVN_DRAW_LINE 0
+#define WVN_DRAW_LINE2 1
+#define WVN_DRAW_DISC 2
+typedef struct {
+  unsigned char* canvas;
+  const int* kinds;
+  const float* points;
+  const unsigned char* colours;
+  const int* frame;
+  const int* panel;
+  int* skipped;
+  long long row_bytes, frame_bytes;
+  int B, H, P, Wp, N;
+} wvn_draw_desc;
+int wvn_draw(const wvn_draw_desc* d, void* stream);
+
 /* ---- evaluation metrics (csrc/metrics.hip; DESIGN.md section 4 "Evaluation metrics"; tests/metrics_ref.py is the definition) ----
  * ROC at T thresholds, binned and exact AUROC, accuracy -- what the reference's MetricLogger takes from torchmetrics -- from integer
  * counts.  PARITY WITH THE torchmetrics PACKAGE IS UNPINNED (the package is absent); the definitions restate its published behaviour.

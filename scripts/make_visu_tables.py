@@ -6,6 +6,8 @@
   rdylbu_stretched_256.txt  visualizer.py:379-384 of the reference (plot_detectron_classification's default), then the
                             conversion of plot_segmentation (:505): fp32 table, (c * 255) truncated to uint8
   rdylbu_256.txt            sns.color_palette("RdYlBu", 256) by seaborn's sampling rule on matplotlib (visu/colormaps.py), converted alike
+  rdylbu_graph_256.txt      visualizer.py:458-459 of the reference (plot_graph_result): the map resampled to 255 entries, sampled at
+                            linspace(0, 1, 256), np.uint8(c * 255) in float64
 
 --check compares the files with what matplotlib gives now and exits 1 on a difference."""
 import os
@@ -30,10 +32,18 @@ def stretched_rdylbu():
     return to_u8(np.concatenate([cmap(np.linspace(0, s, 128)), cmap(np.linspace(1 - s, 1.0, 128))]))
 
 
+def graph_result_rdylbu():
+    import matplotlib
+
+    cmap = matplotlib.colormaps["RdYlBu"].resampled(255)   # cm.get_cmap("RdYlBu", 255)
+    return np.uint8(cmap(np.linspace(0, 1, 256))[:, :3] * 255)
+
+
 def tables():
     from wild_visual_navigation_amd.visu.colormaps import sample_matplotlib
 
-    return {"rdylbu_stretched_256.txt": stretched_rdylbu(), "rdylbu_256.txt": to_u8(sample_matplotlib("RdYlBu", 256))}
+    return {"rdylbu_stretched_256.txt": stretched_rdylbu(), "rdylbu_256.txt": to_u8(sample_matplotlib("RdYlBu", 256)),
+            "rdylbu_graph_256.txt": graph_result_rdylbu()}
 
 
 def main():

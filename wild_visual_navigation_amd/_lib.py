@@ -99,6 +99,12 @@ class OverlayDesc(C.Structure):
                                        "boundary_bytes", "S", "lut_u8", "N", "alpha", "boundary_alpha")]
 
 
+class DrawDesc(C.Structure):
+    """include/wvn_hip.h: wvn_draw_desc."""
+    _fields_ = [(n, C.c_void_p) for n in ("canvas", "kinds", "points", "colours", "frame", "panel", "skipped")] + \
+               [("row_bytes", C.c_longlong), ("frame_bytes", C.c_longlong)] + [(n, C.c_int) for n in ("B", "H", "P", "Wp", "N")]
+
+
 class MetricDesc(C.Structure):
     """include/wvn_hip.h: wvn_metric_desc."""
     _fields_ = [("score", C.c_void_p * 2), ("target", C.c_void_p * 2), ("seg", C.c_void_p), ("seg_off", C.c_void_p),
@@ -113,6 +119,8 @@ METRIC_DENSE, METRIC_PER_SEGMENT = 0, 1
 METRIC_U8, METRIC_I32, METRIC_F32 = 0, 1, 2
 OVERLAY_MAX_COLOURS, OVERLAY_MAX_MAPS = 1024, 4
 OVERLAY_VALUES, OVERLAY_LABELS, OVERLAY_SEGMENTS = 0, 1, 2
+DRAW_MAX_PRIMITIVES = 65536
+DRAW_LINE, DRAW_LINE2, DRAW_DISC = 0, 1, 2
 MLP_KIND_DOUBLE = 1   # include/wvn_hip.h: WVN_MLP_KIND_DOUBLE (MlpDesc.reserved)
 
 
@@ -274,6 +282,7 @@ _SIGNATURES = {
     "wvn_frame_max": ([_p, _i, _i, _ll, _p, _p], _i),
     "wvn_overlay": ([_p, _p], _i),
     "wvn_overlay_panels": ([_p, _p], _i),
+    "wvn_draw": ([_p, _p], _i),
     "wvn_metric_accumulate": ([_p, _p], _i),
     "wvn_metric_curve": ([_p, _p, _i, _p, _p, _p, _p, _p, _p], _i),
     "wvn_metric_auroc_weighted": ([_p, _p, _p, _ll, _p, _p, _p], _i),

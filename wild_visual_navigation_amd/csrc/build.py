@@ -21,7 +21,7 @@ SOURCES = [
     "api.hip", "vit_forward.hip", "gemm_bf16.hip", "gemm_a384.hip", "gemm_n384.hip", "mlp_fused.hip", "qkv_fused.hip", "gemm_proj.hip", "gemm_x3.hip", "gemm_a384_x3.hip", "gemm_n384_x3.hip", "gemm_fp8.hip", "gemm_fp8_dma.hip", "gemm_a768_fp8.hip", "fp8.hip", "gemm_f32.hip", "elementwise.hip", "attention_bf16.hip",
     "attention_x3.hip", "attention_f32.hip",
     "segments.hip", "stego.hip", "stego_linear.hip", "mlp.hip", "mlp_train.hip", "double_mlp.hip", "pixel_mlp.hip", "rnvp.hip", "rnvp_train.hip", "segment_predict.hip", "simple_gcn.hip", "simple_gcn_train.hip", "supervision.hip", "slic.hip", "slic_connectivity.hip", "wire.hip", "random_pixels.hip", "dense_sift.hip",
-    "dense_crf.hip", "dense_crf_permutohedral.hip", "overlay.hip", "resnet.hip", "pyramid_pool.hip", "metrics.hip",
+    "dense_crf.hip", "dense_crf_permutohedral.hip", "overlay.hip", "draw.hip", "resnet.hip", "pyramid_pool.hip", "metrics.hip",
 ]
 # the kernels of the 16-bit-operand speed path are compiled twice (operand.h): bf16 operands, and fp16 operands (-> <name>_f16.o)
 DUAL_OPERAND = ["gemm_bf16.hip", "gemm_a384.hip", "gemm_n384.hip", "mlp_fused.hip", "qkv_fused.hip", "gemm_proj.hip", "attention_bf16.hip"]
@@ -34,7 +34,8 @@ EXTRA = {"stego.hip": ["-ffp-contract=off"], "stego_linear.hip": ["-ffp-contract
          "dense_crf_permutohedral.hip": ["-ffp-contract=off"],   # the lattice construction is fp32, one operation at a time
          "dense_sift.hip": ["-ffp-contract=off"],   # one descriptor function, two kernels, the same bits: every fma is written
          "overlay.hip": ["-ffp-contract=off"],   # the two multiplications by 255 are rounded on their own: the picture is defined bit for bit
-         "metrics.hip": ["-ffp-contract=off"],   # the binned AUROC is a fixed sequence of fp64 operations, each rounded on its own
+         "draw.hip": ["-ffp-contract=off"],   # the polygon scanline of the 2-pixel line is Pillow's fp32 arithmetic, one operation at a time
+         "metrics.hip": ["-ffp-contract=off"],  # the binned AUROC is a fixed sequence of fp64 operations, each rounded on its own
          "attention_bf16.hip": ["-fno-honor-nans"] + os.environ.get("WVN_ATTN_FLAGS", "").split(),
          "attention_x3.hip": ["-fno-honor-nans"], "mlp_fused.hip": os.environ.get("WVN_MLP_FLAGS", "").split()}
 

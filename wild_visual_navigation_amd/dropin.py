@@ -20,7 +20,7 @@ Two situations:
     replaced; everything else the callers import -- ``supervision_generator``, ``cfg.Ros*Params``,
     ``utils.create_experiment_folder`` -- keeps coming from the reference (those are CPU-side helpers outside this build's
     scope).  ``visu`` stays the reference's too (it has plots this package does not: plot_roc,
-    plot_histogram, the optical-flow plots) unless the caller asks for the GPU overlays with ``install(visu=True)``;
+    plot_histogram) unless the caller asks for the GPU overlays with ``install(visu=True)``;
   * it is NOT (this container): a synthetic ``wild_visual_navigation`` package is registered whose sub-modules are the ones of
     this package (``visu`` included), so the import lines above work and anything out of scope raises ImportError as usual.
 """

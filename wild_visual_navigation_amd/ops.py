@@ -1278,6 +1278,58 @@ def overlay_panels(img: torch.Tensor, maps, lut: Optional[torch.Tensor] = None, 
                          out, 1)
 
 
+# ---- overlays: vector primitives (csrc/draw.hip; include/wvn_hip.h "overlays: vector primitives"; tests/visu_draw_ref.py) ------
+def draw(canvas: torch.Tensor, kinds: torch.Tensor, points: torch.Tensor, colours: torch.Tensor, frame: Optional[torch.Tensor] = None,
+         panel: Optional[torch.Tensor] = None, panel_width: Optional[int] = None, skipped: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PIL.ImageDraw's thin line, 2-pixel line and +-5 ellipse, bit for bit, IN PLACE on ``canvas``: a uint8 [B,H,P*Wp,3] (or
+    [H,P*Wp,3]) device tensor or view with packed pixels (rows and frames may be pitched: an overlay result, a column slice).
+    ``kinds`` [N] (``DRAW_LINE`` / ``DRAW_LINE2`` / ``DRAW_DISC``), ``points`` [N,4] = x0, y0, x1, y1 in panel-local pixels (a
+    disc reads its centre x0, y0), ``colours`` [N,3] uint8, ``frame`` and ``panel`` [N] (default 0), ``panel_width`` Wp (default:
+    the whole width).  One launch; the highest-index primitive covering a pixel wins.  A primitive with a coordinate that is not
+    finite or truncates outside [-32768, 32767], or with a frame / panel outside the canvas, is skipped and added to ``skipped``
+    (int32 [1], optional).  Returns ``canvas``."""
+    require_cuda(canvas, "canvas")
+    c4 = canvas[None] if canvas.dim() == 3 else canvas
+    if c4.dim() != 4 or c4.dtype != torch.uint8 or c4.shape[3] != 3 or min(c4.shape[:3]) < 1:
+        raise _lib.WvnError(f"draw: canvas must be uint8 [B,H,W,3] or [H,W,3], not {tuple(canvas.shape)} {canvas.dtype}")
+    B, H, Wc, _ = c4.shape
+    Wp = Wc if panel_width is None else int(panel_width)
+    if Wp < 1 or Wc % Wp:
+        raise _lib.WvnError(f"draw: panel_width {panel_width} does not divide the canvas width {Wc}")
+    if c4.stride(3) != 1 or c4.stride(2) != 3 or c4.stride(1) < 3 * Wc or (B > 1 and c4.stride(0) < H * c4.stride(1)):
+        raise _lib.WvnError(f"draw: canvas needs packed pixels (rows and frames may be pitched), strides {canvas.stride()}")
+    dev = canvas.device
+    N = int(kinds.shape[0])
+    if kinds.dim() != 1 or tuple(points.shape) != (N, 4) or tuple(colours.shape) != (N, 3) or colours.dtype != torch.uint8:
+        raise _lib.WvnError(f"draw: kinds [N], points [N,4], colours uint8 [N,3]; got {tuple(kinds.shape)}, {tuple(points.shape)}, "
+                            f"{tuple(colours.shape)} {colours.dtype}")
+    if N > _lib.DRAW_MAX_PRIMITIVES:
+        raise _lib.WvnError(f"draw: at most {_lib.DRAW_MAX_PRIMITIVES} primitives per call, got {N}")
+
+    def ints(t, name):
+        if t is None:
+            return torch.zeros(N, dtype=torch.int32, device=dev)
+        if tuple(t.shape) != (N,):
+            raise _lib.WvnError(f"draw: {name} shape must be [N] = {(N,)}, not {tuple(t.shape)}")
+        require_cuda(t, name)
+        return t.to(torch.int32).contiguous()
+
+    for t, name in ((kinds, "kinds"), (points, "points"), (colours, "colours")):
+        require_cuda(t, name)
+    keep = [ints(kinds, "kinds"), points.float().contiguous(), colours.contiguous(), ints(frame, "frame"), ints(panel, "panel")]
+    d = _lib.DrawDesc()
+    d.canvas, d.row_bytes, d.frame_bytes = ptr(c4), c4.stride(1), c4.stride(0)
+    d.kinds, d.points, d.colours, d.frame, d.panel = (ptr(t) for t in keep)
+    if skipped is not None:
+        require_cuda(skipped, "skipped")
+        if skipped.dtype != torch.int32 or skipped.numel() != 1:
+            raise _lib.WvnError(f"draw: skipped must be int32 [1], not {tuple(skipped.shape)} {skipped.dtype}")
+        d.skipped = ptr(skipped)
+    d.B, d.H, d.P, d.Wp, d.N = B, H, Wc // Wp, Wp, N
+    check(lib().wvn_draw(C.byref(d), stream()), "wvn_draw")
+    return canvas
+
+
 # ---- evaluation metrics (csrc/metrics.hip; include/wvn_hip.h "evaluation metrics"; tests/metrics_ref.py) ----------------------
 class PerSegment:
     """Marks a source of ``metric_accumulate`` as a per-segment table, gathered through ``seg`` on load: ``[B,S]`` (row b S + s),

@@ -9,6 +9,9 @@ default pictures need no plotting package at run time:
   rdylbu_256.txt             sns.color_palette("RdYlBu", 256): the default ``colormap`` of plot_traversability_graph_on_seg,
                              plot_mission_node_prediction / _training -- by seaborn's sampling rule, see below
 
+  rdylbu_graph_256.txt       the table of plot_graph_result (visualizer.py:458-459 of the reference): matplotlib's "RdYlBu"
+                             resampled to 255 entries, sampled at linspace(0, 1, 256), (c * 255) truncated to uint8
+
 Any other name resolves through seaborn when it is importable, otherwise through matplotlib with seaborn's sampling rule
 (seaborn.palettes.mpl_palette): a qualitative map's colours cycled to n entries, any other map sampled at the interior points
 of linspace(0, 1, n + 2).  UNPINNED: seaborn is not installed where this was written, so that rule is taken from seaborn's
@@ -22,6 +25,7 @@ from .._lib import WvnError
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _PACKAGED = {("RdYlBu", 256): "rdylbu_256.txt"}
 _DEFAULT = "rdylbu_stretched_256.txt"
+_GRAPH_RESULT = {"RdYlBu": "rdylbu_graph_256.txt"}
 # matplotlib's qualitative maps and the number of colours seaborn takes from each (seaborn.palettes.MPL_QUAL_PALS)
 QUALITATIVE = {"tab10": 10, "tab20": 20, "tab20b": 20, "tab20c": 20, "Set1": 9, "Set2": 8, "Set3": 12, "Accent": 8, "Paired": 12,
                "Pastel1": 9, "Pastel2": 8, "Dark2": 8}
@@ -76,4 +80,24 @@ def colour_table(name: str, n: int) -> torch.Tensor:
         else:
             pal = sns.color_palette(name, n)
         _cache[key] = torch.tensor([[float(v) for v in c[:3]] for c in pal], dtype=torch.float32)
+    return _cache[key]
+
+
+def graph_result_table(name: str = "RdYlBu") -> torch.Tensor:
+    """uint8 [256,3] on the CPU: ``np.uint8(cm.get_cmap(name, 255)(np.linspace(0, 1, 256))[:, :3] * 255)`` of plot_graph_result.
+    "RdYlBu" is packaged; any other name needs matplotlib (``matplotlib.colormaps[name].resampled(255)`` is the same construction)."""
+    if name in _GRAPH_RESULT:
+        return _read(_GRAPH_RESULT[name])
+    key = ("graph_result", name)
+    if key not in _cache:
+        try:
+            import matplotlib
+            import numpy as np
+        except ImportError as e:
+            raise WvnError(f"colour map {name!r} of plot_graph_result is not packaged: it needs matplotlib, which is not installed") from e
+        try:
+            cmap = matplotlib.colormaps[name].resampled(255)
+        except KeyError as e:
+            raise WvnError(f"colour map {name!r} is not packaged and matplotlib does not know the name") from e
+        _cache[key] = torch.from_numpy(np.uint8(cmap(np.linspace(0, 1, 256))[:, :3] * 255))
     return _cache[key]
