@@ -42,7 +42,8 @@ extern "C" {
                            error) on the fp16-operand kernel of WVN_PREC_F16, fed fp16 q / k / v^T by the QKV epilogue and writing  \
                            its output as hi + lo planes from its fp32 accumulators.  Weights as for WVN_PREC_X3 */
 
-int wvn_version(void); /* 101 (100 -> 101: wvn_flip_average gained ld_src; wvn_vit_forward_frames_head, wvn_stego_head added) */
+int wvn_version(void); /* 103 (100 -> 101: wvn_flip_average gained ld_src; wvn_vit_forward_frames_head, wvn_stego_head added; 102: wvn_gcn_train_*;
+                          103: wvn_debug_slic_lab) */
 
 /* ---------------------------------------------------------------------------------------------
  * DINO ViT backbone  (replaces stego.backbones.backbone.get_backbone(cfg)(img), called from
@@ -955,6 +956,9 @@ int wvn_debug_stego_head_fused(const float* x, int ldx, const float* stats, cons
  * 4 total}]; NULL switches the instrumented build off again. */
 /* (test hook) out_f16[i] = fp16(in[i]) as the kernels convert: finite values beyond the fp16 range saturate to +-65504 (MODE.FP16_OVFL) */
 int wvn_debug_f16_saturate(const float* in, void* out_f16, int n, void* stream);
+/* (test hook) the Lab conversion of wvn_slic alone (slic_lab_kernel, one launch): img [3][npix] planar, uint8 (img_is_u8) or float;
+ * lut_lin / lut_f as for wvn_slic; lab [3][npix] int32 = (L, a, b) * 64.  WVN_ERR_ARG for a NULL pointer or npix <= 0. */
+int wvn_debug_slic_lab(const void* img, int img_is_u8, int npix, const int* lut_lin, const int* lut_f, int* lab, void* stream);
 int wvn_debug_attention_timing(long long* dbg);
 /* which form of the pre-scaled (scale == 0) attention kernel subsequent launches use: 0 = exact per-tile row max, 1 = lazy (no
  * per-tile max; the row sums raise the alarm and the tile is redone exactly -- the default), < 0 = back to the default.  Same

@@ -1,12 +1,23 @@
 """GPU SLIC (csrc/slic.hip) against its integer-arithmetic numpy oracle (oracle/slic.py), bit for bit, and the reference's class
-default FeatureExtractor(device) -- segmentation_type="slic" -- constructing and extracting (feature_extractor.py:20-27, 84-90)."""
+default FeatureExtractor(device) -- segmentation_type="slic" -- constructing and extracting (feature_extractor.py:20-27, 84-90).
+
+The rows of tests/slic_cases.py (odd frame sizes, one row / column of cells, ties, emptied clusters, negative centre sums, the dynamic
+LDS limit, argument edges) are there for a rule of the algorithm each: tests/test_slic_host.py shows on the CPU that a kernel with
+that rule wrong gives other labels on them."""
+import functools
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
-from oracle import slic as OSL, vit as OV
-from wild_visual_navigation_amd import ops
-from wild_visual_navigation_amd.feature_extractor import FeatureExtractor
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import slic_cases as SC  # noqa: E402
+
+from oracle import slic as OSL, vit as OV  # noqa: E402
+from wild_visual_navigation_amd import _lib, ops  # noqa: E402
+from wild_visual_navigation_amd.feature_extractor import FeatureExtractor  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -58,3 +69,181 @@ def test_feature_extractor_default_constructs_and_extracts_with_slic(dev, golden
     assert torch.isnan(feat.cpu()[~ok]).all()
     fb, sb, nb = fe.extract_batch(img.expand(2, -1, -1, -1).contiguous())
     assert torch.equal(sb[0].long(), seg) and (torch.nan_to_num(fb[0, :S]) - torch.nan_to_num(feat)).abs().max().item() < 1e-5
+
+
+# ---- the case table of tests/slic_cases.py -----------------------------------------------------------------------------------
+WVN_ERR_ARG = 1001
+SENTINEL = -0x5A5A5A5B   # (no label, no Lab value and no centre sum looks like it)
+
+
+def _frame(case, dev):
+    return torch.from_numpy(SC.image(case).copy()).to(dev)
+
+
+def _raw_slic(img, num_components, compactness, iters, labels_ptr, scratch, scratch_bytes):
+    """lib().wvn_slic on caller-owned buffers: img [3,H,W] contiguous on the GPU, labels_ptr a device address, scratch a uint8 tensor."""
+    lin, f = ops.slic_tables(img.device)
+    _, H, W = img.shape
+    return _lib.lib().wvn_slic(img.data_ptr(), int(img.dtype == torch.uint8), H, W, num_components, float(compactness), iters,
+                               lin.data_ptr(), f.data_ptr(), labels_ptr, scratch.data_ptr(), scratch_bytes, _lib.stream())
+
+
+@pytest.mark.parametrize("case", SC.CASES, ids=lambda c: c.name)
+def test_slic_case_table_matches_oracle(dev, case):
+    img = _frame(case, dev)
+    assert (img.dtype == torch.float32) == (case.builder in SC.FLOAT_BUILDERS)
+    a = ops.slic(img, case.num_components, case.compactness, case.iters)
+    b = ops.slic(img, case.num_components, case.compactness, case.iters)
+    assert torch.equal(a, b), "two calls on the same frame give different labels"
+    got, want = a.cpu().numpy(), SC.oracle_labels(case)
+    assert got.dtype == np.int32 and got.shape == (case.H, case.W)
+    assert np.array_equal(got, want), f"{(got != want).mean():.4f} of the labels differ"
+    assert got.min() >= 0 and got.max() < ops.slic_num_clusters(case.H, case.W, case.num_components)
+
+
+@pytest.mark.parametrize("case", SC.LDS_ROWS, ids=lambda c: c.name)
+def test_slic_launches_above_48_kb_of_dynamic_lds(dev, case):
+    """K = 2601 .. 3072 clusters: 52 020 .. 61 440 B of centres staged in LDS, the last exactly the 60 KB the launcher accepts.  A launch
+    the runtime refused would come back as its error code from the raw call."""
+    K = ops.slic_num_clusters(case.H, case.W, case.num_components)
+    assert 48 * 1024 < 5 * K * 4 <= 60 * 1024
+    img = _frame(case, dev)
+    labels = torch.full((case.H, case.W), SENTINEL, dtype=torch.int32, device=dev)
+    nbytes = _lib.lib().wvn_slic_scratch_bytes(case.H, case.W, case.num_components)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rc = _raw_slic(img, case.num_components, case.compactness, case.iters, labels.data_ptr(), scratch, nbytes)
+    torch.cuda.synchronize()
+    assert rc == 0, f"wvn_slic returned {rc} at K = {K}"
+    assert np.array_equal(labels.cpu().numpy(), SC.oracle_labels(case))
+
+
+def test_slic_refuses_more_than_60_kb_of_lds_and_writes_nothing(dev):
+    H, W, nc = 56, 55, 3080
+    assert ops.slic_num_clusters(H, W, nc) == 3080 and 5 * 3080 * 4 == 61600 > 60 * 1024
+    img = torch.from_numpy(SC.noise(H, W, 1)).to(dev)
+    labels = torch.full((H, W), SENTINEL, dtype=torch.int32, device=dev)
+    nbytes = _lib.lib().wvn_slic_scratch_bytes(H, W, nc)
+    scratch = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device=dev)
+    rc = _raw_slic(img, nc, 10.0, 10, labels.data_ptr(), scratch, nbytes)
+    torch.cuda.synchronize()
+    assert rc == WVN_ERR_ARG
+    assert bool((labels == SENTINEL).all()) and bool((scratch == 0xA5).all())
+    with pytest.raises(_lib.WvnError):
+        ops.slic(img, nc, 10.0)
+
+
+@pytest.mark.parametrize("name", ["tail169-smooth-37x53-n12-m10-it10", "tail169-noise-37x53-n12-m10-it10",
+                                  "tail255-smooth-65x63-n9-m10-it10", "tail255-noise-65x63-n9-m10-it10"])
+def test_slic_writes_inside_its_buffers_only(dev, name):
+    """A partly filled last block (169 and 255 of 256 lanes live): labels go into the interior of a buffer with 256 sentinel words on
+    each side, the scratch is exactly wvn_slic_scratch_bytes followed by 4096 sentinel bytes; both guards are intact afterwards."""
+    case = SC.by_name(name)
+    npix = case.H * case.W
+    assert npix % 256 in (169, 255)
+    img = _frame(case, dev)
+    buf = torch.full((256 + npix + 256,), SENTINEL, dtype=torch.int32, device=dev)
+    nbytes = _lib.lib().wvn_slic_scratch_bytes(case.H, case.W, case.num_components)
+    scratch = torch.full((nbytes + 4096,), 0xA5, dtype=torch.uint8, device=dev)
+    rc = _raw_slic(img, case.num_components, case.compactness, case.iters, buf.data_ptr() + 256 * 4, scratch, nbytes)
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert bool((buf[:256] == SENTINEL).all()) and bool((buf[256 + npix:] == SENTINEL).all()), "labels written outside [0, H*W)"
+    assert bool((scratch[nbytes:] == 0xA5).all()), "scratch written past wvn_slic_scratch_bytes"
+    assert np.array_equal(buf[256:256 + npix].reshape(case.H, case.W).cpu().numpy(), SC.oracle_labels(case))
+
+
+def test_slic_batch_equals_single_frames(dev):
+    """[4,3,70,90]: a noise, a flat, a block and a smooth frame share one scratch buffer in stream order (sums left by one frame must not
+    reach the next); and a non-contiguous input, the CHW view of an HWC tensor."""
+    H, W = 70, 90
+    frames = np.stack([SC.noise(H, W, 11), SC.const(H, W, 12), SC.blocks(H, W, SC.BLOCKS_SEED), SC.smooth(H, W, 14)])
+    batch = torch.from_numpy(frames).to(dev)
+    got = ops.slic(batch, 20, 10.0)
+    assert got.shape == (4, H, W) and got.dtype == torch.int32
+    for b in range(4):
+        single = ops.slic(batch[b], 20, 10.0)
+        assert torch.equal(got[b], single), f"frame {b} of the batch differs from its single-frame call"
+        assert np.array_equal(single.cpu().numpy(), OSL.slic(frames[b], 20, 10.0)), b
+    hwc = torch.from_numpy(np.ascontiguousarray(frames[0].transpose(1, 2, 0))).to(dev)
+    view = hwc.permute(2, 0, 1)
+    assert not view.is_contiguous()
+    assert torch.equal(ops.slic(view, 20, 10.0), got[0])
+
+
+# ---- the Lab conversion alone, on every colour ---------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _lab_of_every_colour():
+    """oracle.slic.lab64 of all 2^24 colours, int32 [3, 2^24], pixel index = R * 65536 + G * 256 + B (computed once, read-only)."""
+    out = np.empty((3, 1 << 24), np.int32)
+    for r0 in range(0, 256, 16):
+        out[:, r0 << 16:(r0 + 16) << 16] = OSL.lab64(SC.all_colours_slab(r0, r0 + 16))
+    out.setflags(write=False)
+    return out
+
+
+def _debug_lab(img, dev):
+    npix = img.shape[1]
+    lin, f = ops.slic_tables(dev)
+    lab = torch.full((3, npix), SENTINEL, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().wvn_debug_slic_lab(img.data_ptr(), int(img.dtype == torch.uint8), npix, lin.data_ptr(), f.data_ptr(),
+                                             lab.data_ptr(), _lib.stream()), "wvn_debug_slic_lab")
+    return lab.cpu().numpy()
+
+
+def test_lab_kernel_on_every_colour_u8(dev):
+    img = torch.from_numpy(SC.all_colours_slab(0, 256)).to(dev)
+    got = _debug_lab(img, dev)
+    want = _lab_of_every_colour()
+    assert np.array_equal(got, want), f"{(got != want).any(0).sum()} of 2^24 colours differ"
+
+
+def test_lab_kernel_on_every_colour_float(dev):
+    """The float image u8 / 255 (divided on the host, so that both sides see the same floats): the kernel's (int)(unsigned char)(int)(v * 255)
+    against the oracle's to_u8, colour for colour."""
+    u8 = SC.all_colours_slab(0, 256)
+    f32 = u8.astype(np.float32) / np.float32(255.0)
+    back = OSL.to_u8(f32)
+    print(f"{(back != u8).any(0).sum()} of 2^24 colours change under float -> uint8 truncation of u8 / 255")
+    idx = (back[0].astype(np.int64) << 16) | (back[1].astype(np.int64) << 8) | back[2]
+    want = _lab_of_every_colour()[:, idx]
+    got = _debug_lab(torch.from_numpy(f32).to(dev), dev)
+    assert np.array_equal(got, want), f"{(got != want).any(0).sum()} of 2^24 colours differ"
+
+
+def test_lab_kernel_partly_filled_block_and_guards(dev):
+    """npix = 1000 (232 of the last block's 256 lanes live), float values outside [0, 1]: the three planes land in the interior of a guarded buffer."""
+    npix = 1000
+    f32 = SC.float_wrap(1, npix, 9).reshape(3, npix)
+    lin, f = ops.slic_tables(dev)
+    buf = torch.full((256 + 3 * npix + 256,), SENTINEL, dtype=torch.int32, device=dev)
+    img = torch.from_numpy(f32).to(dev)
+    rc = _lib.lib().wvn_debug_slic_lab(img.data_ptr(), 0, npix, lin.data_ptr(), f.data_ptr(), buf.data_ptr() + 256 * 4, _lib.stream())
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert bool((buf[:256] == SENTINEL).all()) and bool((buf[256 + 3 * npix:] == SENTINEL).all())
+    want = OSL.lab64(OSL.to_u8(f32))
+    assert np.array_equal(buf[256:256 + 3 * npix].reshape(3, npix).cpu().numpy(), want)
+
+
+# ---- end to end on a non-square frame ------------------------------------------------------------------------------------------
+def test_sift_feature_extractor_with_slic_on_a_non_square_batch(dev):
+    """FeatureExtractor(feature_type="sift", segmentation_type="slic") needs no checkpoint and takes H x W frames: [2,3,72,104]."""
+    H, W = 72, 104
+    c0 = SC.by_name("float-smooth_float-72x104-n100-m10-it10")
+    f1 = SC.two_level_noise(H, W, 1).astype(np.float32) / np.float32(255.0)   # (its map leaves one id without pixels: checked below)
+    frames = np.stack([SC.image(c0), f1])
+    fe = FeatureExtractor(dev, feature_type="sift", segmentation_type="slic")
+    feat, seg, n = fe.extract_batch(torch.from_numpy(frames).to(dev))
+    K = ops.slic_num_clusters(H, W, 100)
+    assert K == 117 and n.tolist() == [K, K]
+    assert seg.shape == (2, H, W) and feat.shape == (2, K, fe.feature_dim) and fe.feature_dim == 384
+    n_empty = 0
+    for b, want in enumerate((SC.oracle_labels(c0), OSL.slic(f1, 100, 10.0))):
+        got = seg[b].cpu().numpy()
+        assert np.array_equal(got, want), f"frame {b}: {(got != want).mean():.4f} of the labels differ"
+        empty = torch.from_numpy(np.bincount(want.ravel(), minlength=K) == 0)
+        nan = torch.isnan(feat[b].cpu())
+        assert bool(nan[empty].all()) and not bool(nan[~empty].any()), "NaN rows are exactly the ids without pixels"
+        print(f"frame {b}: {int(empty.sum())} of {K} ids without pixels")
+        n_empty += int(empty.sum())
+    assert n_empty >= 1, "no id without pixels: the NaN rows were not tested"

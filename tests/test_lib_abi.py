@@ -99,6 +99,7 @@ def test_argument_validation_without_gpu():
     assert h.wvn_project_render_fmin(None, 1, None, 0, 4, 3, 8, 8, None, 1.0, None) == 1001
     assert h.wvn_label_pool_batched(None, 1, 3, 8, 8, 4, None, None, None) == 1001
     assert h.wvn_slic(None, 1, 8, 8, 4, 10.0, 10, None, None, None, None, 0, None) == 1001
+    assert h.wvn_debug_slic_lab(None, 1, 64, None, None, None, None) == 1001
     assert h.wvn_wire_pack(None, 1, None, 4, None, 8, 8, 2, 4, None) == 1001
     assert h.wvn_slic_num_clusters(448, 448, 100) == 100 and h.wvn_slic_num_clusters(224, 224, 100) == 100
     assert h.wvn_wire_bytes(224, 224, 100, 384) == 64 + 224 * 224 * 4 + 100 * 384 * 4

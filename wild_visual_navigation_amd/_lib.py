@@ -271,6 +271,7 @@ _SIGNATURES = {
     "wvn_seg_adjacency_batched": ([_p, _p, _i, _i, _i, _i, _p], _i),
     "wvn_debug_gemm_bf16_timed": ([_p, _i, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p], _i),
     "wvn_debug_f16_saturate": ([_p, _p, _i, _p], _i),
+    "wvn_debug_slic_lab": ([_p, _i, _i, _p, _p, _p, _p], _i),
     "wvn_debug_attention_timing": ([_p], _i),
     "wvn_debug_gemm_n384": ([_p, _i, _p, _i, _p, _p, _i, _i, _i, _p], _i),
     "wvn_dense_crf_workspace_bytes": ([_i, _i, _i, _i], _sz),

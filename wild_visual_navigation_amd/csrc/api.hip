@@ -16,7 +16,7 @@
 
 extern "C" {
 
-int wvn_version(void) { return 102; }   // 102: wvn_gcn_train_*; 101: wvn_flip_average takes the source row stride; wvn_vit_forward_frames_head
+int wvn_version(void) { return 103; }   // 103: wvn_debug_slic_lab; 102: wvn_gcn_train_*; 101: wvn_flip_average takes the source row stride; wvn_vit_forward_frames_head
 
 size_t wvn_vit_workspace_bytes(const wvn_vit_model* m, int batch) {
   if (!m || batch <= 0) return 0;
@@ -215,6 +215,9 @@ int wvn_attention_x3(const void* q_hi, const void* q_lo, const void* k_hi, const
 
 int wvn_debug_f16_saturate(const float* in, void* out_f16, int n, void* stream) {
   return (in && out_f16 && n > 0) ? wvn_f16_saturate_probe_launch(in, (uint16_t*)out_f16, n, (hipStream_t)stream) : WVN_ERR_ARG;
+}
+int wvn_debug_slic_lab(const void* img, int img_is_u8, int npix, const int* lut_lin, const int* lut_f, int* lab, void* stream) {
+  return wvn_slic_lab_launch(img, img_is_u8, npix, lut_lin, lut_f, lab, (hipStream_t)stream);
 }
 int wvn_debug_attention_timing(long long* dbg) { wvn_attention_bf16_set_debug(dbg); return WVN_OK; }
 int wvn_debug_mlp_fused_timing(long long* dbg) { g_mlp_fused_dbg = dbg; return WVN_OK; }

@@ -153,6 +153,15 @@ size_t wvn_slic_scratch_bytes_impl(int H, int W, int num_components) {
          align_up((size_t)6 * g.K * sizeof(long long), 256);
 }
 
+// (test hook) the Lab conversion alone, exactly as wvn_slic_launch launches it: lab [3][npix]
+int wvn_slic_lab_launch(const void* img, int img_u8, int npix, const int* lut_lin, const int* lut_f, int* lab, hipStream_t st) {
+  if (!img || !lut_lin || !lut_f || !lab || npix <= 0) return WVN_ERR_ARG;
+  if (img_u8) hipLaunchKernelGGL(slic_lab_kernel<unsigned char>, dim3(ceil_div(npix, 256)), dim3(256), 0, st, (const unsigned char*)img, lut_lin, lut_f, lab, npix);
+  else hipLaunchKernelGGL(slic_lab_kernel<float>, dim3(ceil_div(npix, 256)), dim3(256), 0, st, (const float*)img, lut_lin, lut_f, lab, npix);
+  WVN_LAUNCH_CHECK();
+  return WVN_OK;
+}
+
 int wvn_slic_launch(const void* img, int img_u8, int H, int W, int num_components, float compactness, int iters,
                     const int* lut_lin, const int* lut_f, int* labels, void* scratch, size_t scratch_bytes, hipStream_t st) {
   if (!img || !lut_lin || !lut_f || !labels || !scratch || H <= 0 || W <= 0 || num_components <= 0 || iters < 1) return WVN_ERR_ARG;

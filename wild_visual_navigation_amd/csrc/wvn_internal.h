@@ -419,6 +419,7 @@ int wvn_slic_num_clusters_impl(int H, int W, int num_components);
 size_t wvn_slic_scratch_bytes_impl(int H, int W, int num_components);
 int wvn_slic_launch(const void* img, int img_u8, int H, int W, int num_components, float compactness, int iters,
                     const int* lut_lin, const int* lut_f, int* labels, void* scratch, size_t scratch_bytes, hipStream_t st);
+int wvn_slic_lab_launch(const void* img, int img_u8, int npix, const int* lut_lin, const int* lut_f, int* lab, hipStream_t st);
 // connectivity enforcement of label maps (slic_connectivity.hip)
 size_t wvn_slic_connectivity_scratch_bytes_impl(int B, int H, int W, int K);
 int wvn_slic_connectivity_launch(const int* labels_in, int* labels_out, int B, int H, int W, int K, int min_size, void* scratch,
