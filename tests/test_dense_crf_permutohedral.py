@@ -3,7 +3,9 @@ StegoInterface(run_crf=True, crf="permutohedral")) against the statements of DES
 
 Two statements live here and nowhere else: the lattice construction in float32, one numpy operation per statement of the reading
 (``lattice32``), and the filter and CRF on that lattice in float64 (``filter64``, ``crf_lattice64``).  The CPU tests pin both to a
-literal per-pixel loop transcription of the reading; the GPU tests hold the kernels to them (the lattice bit for bit)."""
+literal per-pixel loop transcription of the reading; the GPU tests hold the kernels to them (the lattice bit for bit).  The same
+statements at production tile counts, other pass counts, contributor extremes, tiny frames and in the second group of a shared pass:
+tests/test_gpu_dense_crf_permutohedral_edges.py, on the frames of tests/dense_crf_cases.py (tests/test_dense_crf_cases_host.py)."""
 import ctypes as C
 import math
 
