@@ -1268,6 +1268,94 @@ size_t wvn_segpool_pyramid_scratch_bytes(int B, int S);
 int wvn_segpool_pyramid(const float* feat1, const float* feat2, const float* feat3, const float* feat4, const int* seg, float* feat,
                         void* scratch, size_t scratch_bytes, int B, int H, int W, int S, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * JPEG ingest (the CompressedImage branch of the reference's ros_image_to_torch, ros_converter.py:117-121: cv2.imdecode): compressed
+ * camera frames -> uint8 [B][3][H][W] in device memory, BIT-IDENTICAL to what libjpeg(-turbo) with default settings decodes from the
+ * same bytes (islow IDCT, fancy upsampling, 16-bit colour tables).  tests/jpeg_ref.py states the whole decoder in numpy.
+ *
+ * Host stage (csrc/jpeg_host.cpp, no HIP): marker parser (SOI, APPn, COM, DQT with 8- and 16-bit tables, SOF0 / SOF1 with 8-bit
+ * samples, DHT, DRI, SOS, RSTn, EOI, byte stuffing) and the sequential Huffman decoder.  Accepted: 1 component (any sampling
+ * factor), or 3 components YCbCr with luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and chroma 1x1, in ONE interleaved scan.
+ * Refused with WVN_JPEG_UNSUPPORTED: progressive, lossless, hierarchical, arithmetic coding, 12-bit samples, 2 or 4 components, any
+ * other sampling (4:4:0 and 4:1:1 included), RGB-coded files (Adobe transform 0, or ids 'R' 'G' 'B' without JFIF), several scans,
+ * DNL, a side above WVN_JPEG_MAX_DIM.  The input is untrusted: a short stream is WVN_JPEG_TRUNCATED, a wrong marker, length or RSTn
+ * WVN_JPEG_BAD_MARKER, a bad DQT / DHT or a missing table WVN_JPEG_BAD_TABLE, a bit pattern that is no code WVN_JPEG_BAD_HUFFMAN, a
+ * run past coefficient 63 or a DC value outside int16 WVN_JPEG_BAD_COEFFICIENT.  Nothing is padded or guessed: such a frame has a
+ * status and no pixels.  EOI must follow the scan; bytes after it are ignored.  Whole bytes left between the last coded bit and an RSTn
+ * or EOI are WVN_JPEG_BAD_MARKER (libjpeg skips such "extraneous bytes"); only the fewer than 8 padding bits are dropped.
+ * Precedence: the first error met in stream order decides; WVN_JPEG_OUT_OF_RANGE is given only to a stream that is otherwise whole.
+ * wvn_jpeg_info walks the whole header (tables and scan header included).  wvn_jpeg_probe_batch is the cheap form a batch uses to learn
+ * its geometries in one call: markers and lengths up to SOS, Huffman codes not built; g [B] and status [B] are host arrays.
+ * WVN_JPEG_OUT_OF_RANGE: a block whose dequantised coefficients or first-pass values leave int16, or whose samples before the + 128
+ * leave [-512, 511].  There libjpeg has no single answer -- its C code and its SIMD code wrap and saturate differently -- so the
+ * frame is refused.  Streams encoded from 8-bit pictures stay inside (the widest sample met in the tests: 338, a saturated checkerboard at quality 1).  The host checks it exactly: blocks
+ * with sum |coef q| <= 2000 cannot leave the range, the others run the integer IDCT once on the host.
+ *
+ * Coefficients: int16 [blocks][64], quantised (NOT dequantised), natural order (index 8 v + u), component after component, each
+ * component a raster of bw x bh blocks padded to whole MCUs: with hmax x vmax the luma factors, mcus_x = ceil(width / (8 hmax)),
+ * bw = mcus_x h_c, likewise bh.  4:2:0 is 1.5 samples per pixel x 2 B = 3 B per pixel: the upload is the size of the RGB8 frame.
+ * wvn_jpeg_coefficients is the host stage alone for one frame: coef (coef_bytes >= wvn_jpeg_coef_bytes(g)) and the quantisation
+ * tables of the components, uint16 [3][64] in natural order; both are all zero unless the status is WVN_JPEG_OK.
+ * wvn_jpeg_coefficients_batch is the host stage of wvn_jpeg_decode_batch without the device: B frames of geometry g on the same
+ * workers into HOST arrays coef [B][blocks][64] (coef_bytes >= B wvn_jpeg_coef_bytes(g)) and qtables [B][3][64], status [B].
+ *
+ * Device stage (csrc/jpeg.hip), integers only:
+ *   1. dequantise (coef * q in 32 bits) + libjpeg's jidctint "islow" 8 x 8 inverse DCT (CONST_BITS 13, PASS1_BITS 2, descale with
+ *      round-half-up, + 128, range limit through libjpeg's 10-bit mask) -> component planes uint8 [bh 8][bw 8];
+ *   2. fancy upsampling + YCbCr -> RGB per output pixel.  h2v1: out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2)
+ *      >> 2; h2v2: with t[i] = 3 near[i] + far[i] over the nearer and farther chroma row, out[2i] = (3 t[i] + t[i-1] + 8) >> 4,
+ *      out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4; at the first and last column of the component's REAL width cw = ceil(width / 2) the
+ *      missing neighbour is the sample itself; above the first and below the last real row (ch = ceil(height / 2)) the row itself.
+ *      A component of real width <= 2 is replicated (libjpeg switches fancy upsampling off there).  Colour: R = Y + ((91881 (Cr -
+ *      128) + 32768) >> 16), B = Y + ((116130 (Cb - 128) + 32768) >> 16), G = Y + ((-22554 (Cb - 128) - 46802 (Cr - 128) + 32768)
+ *      >> 16), clamped to [0, 255].  One component: the luma plane replicated (or one channel with gray_out).
+ *
+ * wvn_jpeg_decode_batch: B frames of ONE geometry g (a frame of another geometry: WVN_JPEG_GEOMETRY_MISMATCH) ->
+ * out_u8 [B][gray_out ? 1 : 3][height][width].  gray_out needs a one-component geometry.  The host stage runs on
+ * min(threads, B, WVN_JPEG_MAX_THREADS) workers (threads < 1 counts as 1) and writes into a pinned staging buffer owned by the
+ * library; one asynchronous upload and two launches follow on the stream.  Two staging buffers alternate, each guarded by an event
+ * recorded behind its upload, so a call never overwrites bytes a previous call's upload still reads.  status: HOST int [B], valid on
+ * return; a frame with a status other than WVN_JPEG_OK is ALL ZERO in out_u8 and does not disturb its neighbours.  workspace: device
+ * memory of wvn_jpeg_workspace_bytes(g, B) bytes (per frame 512 B of tables + the coefficients + the planes, 256-byte aligned).
+ * wvn_jpeg_device_stage is the second half alone, for coefficients that are already in the workspace (laid out as above: frame b at
+ * byte b (512 + wvn_jpeg_coef_bytes(g)): uint16 q[3][64], uint16 valid, padding to 512 B, then the coefficients): the two launches.
+ * Returns WVN_ERR_ARG before anything runs for a null pointer, B < 1, B > WVN_JPEG_MAX_BATCH, a geometry wvn_jpeg_info does not
+ * produce or gray_out on a colour geometry; per-frame failures are statuses, not a return value.  The size queries return 0 for
+ * such a geometry.
+ * ------------------------------------------------------------------------------------------- */
+#define WVN_JPEG_OK 0
+#define WVN_JPEG_TRUNCATED 1
+#define WVN_JPEG_BAD_MARKER 2
+#define WVN_JPEG_BAD_TABLE 3
+#define WVN_JPEG_BAD_HUFFMAN 4
+#define WVN_JPEG_BAD_COEFFICIENT 5
+#define WVN_JPEG_UNSUPPORTED 6
+#define WVN_JPEG_GEOMETRY_MISMATCH 7
+#define WVN_JPEG_BAD_GEOMETRY 8
+#define WVN_JPEG_OUT_OF_RANGE 9
+#define WVN_JPEG_GRAY 0
+#define WVN_JPEG_444 1
+#define WVN_JPEG_422 2
+#define WVN_JPEG_420 3
+#define WVN_JPEG_MAX_DIM 16384
+#define WVN_JPEG_MAX_THREADS 16
+#define WVN_JPEG_MAX_BATCH 4096
+typedef struct {
+  int width, height, components, sampling, restart_interval;
+} wvn_jpeg_geometry;
+int wvn_jpeg_info(const void* data, size_t n, wvn_jpeg_geometry* out);
+int wvn_jpeg_probe_batch(const void* const* data, const size_t* sizes, int B, wvn_jpeg_geometry* g, int* status);
+size_t wvn_jpeg_coef_bytes(const wvn_jpeg_geometry* g);
+size_t wvn_jpeg_plane_bytes(const wvn_jpeg_geometry* g);
+size_t wvn_jpeg_workspace_bytes(const wvn_jpeg_geometry* g, int B);
+int wvn_jpeg_coefficients(const void* data, size_t n, const wvn_jpeg_geometry* g, short* coef, size_t coef_bytes,
+                          unsigned short* qtables);
+int wvn_jpeg_coefficients_batch(const void* const* data, const size_t* sizes, int B, const wvn_jpeg_geometry* g, short* coef,
+                                size_t coef_bytes, unsigned short* qtables, int threads, int* status);
+int wvn_jpeg_device_stage(const wvn_jpeg_geometry* g, int B, void* workspace, void* out_u8, int gray_out, void* stream);
+int wvn_jpeg_decode_batch(const void* const* data, const size_t* sizes, int B, const wvn_jpeg_geometry* g, void* out_u8, int gray_out,
+                          void* workspace, int threads, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

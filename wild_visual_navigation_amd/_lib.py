@@ -114,6 +114,19 @@ class MetricDesc(C.Structure):
                [(n, C.c_int) for n in ("n_scores", "n_targets", "B", "H", "W", "S", "T", "has_ignore", "ignore_index", "seg_bytes")]
 
 
+class JpegGeometry(C.Structure):
+    """include/wvn_hip.h: wvn_jpeg_geometry."""
+    _fields_ = [(n, C.c_int) for n in ("width", "height", "components", "sampling", "restart_interval")]
+
+
+# include/wvn_hip.h: WVN_JPEG_* statuses and samplings
+JPEG_STATUS = ("OK", "TRUNCATED", "BAD_MARKER", "BAD_TABLE", "BAD_HUFFMAN", "BAD_COEFFICIENT", "UNSUPPORTED", "GEOMETRY_MISMATCH",
+               "BAD_GEOMETRY", "OUT_OF_RANGE")
+(JPEG_OK, JPEG_TRUNCATED, JPEG_BAD_MARKER, JPEG_BAD_TABLE, JPEG_BAD_HUFFMAN, JPEG_BAD_COEFFICIENT, JPEG_UNSUPPORTED,
+ JPEG_GEOMETRY_MISMATCH, JPEG_BAD_GEOMETRY, JPEG_OUT_OF_RANGE) = range(10)
+JPEG_SAMPLING = ("gray", "4:4:4", "4:2:2", "4:2:0")
+JPEG_MAX_THREADS = 16
+JPEG_MAX_BATCH = 4096
 METRIC_MAX_T, METRIC_STATE_TAIL = 8192, 8
 METRIC_DENSE, METRIC_PER_SEGMENT = 0, 1
 METRIC_U8, METRIC_I32, METRIC_F32 = 0, 1, 2
@@ -298,6 +311,15 @@ _SIGNATURES = {
     "wvn_resnet18_forward": ([_p, _p, _i, _i, _i, _i, _p, _sz, _p], _i),
     "wvn_segpool_pyramid_scratch_bytes": ([_i, _i], _sz),
     "wvn_segpool_pyramid": ([_p, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _p], _i),
+    "wvn_jpeg_info": ([_p, _sz, _p], _i),
+    "wvn_jpeg_probe_batch": ([_p, _p, _i, _p, _p], _i),
+    "wvn_jpeg_coef_bytes": ([_p], _sz),
+    "wvn_jpeg_plane_bytes": ([_p], _sz),
+    "wvn_jpeg_workspace_bytes": ([_p, _i], _sz),
+    "wvn_jpeg_coefficients": ([_p, _sz, _p, _p, _sz, _p], _i),
+    "wvn_jpeg_coefficients_batch": ([_p, _p, _i, _p, _p, _sz, _p, _i, _p], _i),
+    "wvn_jpeg_device_stage": ([_p, _i, _p, _p, _i, _p], _i),
+    "wvn_jpeg_decode_batch": ([_p, _p, _i, _p, _p, _i, _p, _i, _p, _p], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -22,10 +22,14 @@ SOURCES = [
     "attention_x3.hip", "attention_f32.hip",
     "segments.hip", "stego.hip", "stego_linear.hip", "mlp.hip", "mlp_train.hip", "double_mlp.hip", "pixel_mlp.hip", "rnvp.hip", "rnvp_train.hip", "segment_predict.hip", "simple_gcn.hip", "simple_gcn_train.hip", "supervision.hip", "slic.hip", "slic_connectivity.hip", "wire.hip", "random_pixels.hip", "dense_sift.hip",
     "dense_crf.hip", "dense_crf_permutohedral.hip", "overlay.hip", "draw.hip", "resnet.hip", "pyramid_pool.hip", "metrics.hip",
+    "jpeg.hip",
 ]
+# plain C++ without device code (the host stage of the JPEG ingest: parser + Huffman decoder), compiled by the same driver as C++
+HOST_SOURCES = ["jpeg_host.cpp"]
+HOST_FLAGS = ["-x", "c++", "-O3", "-std=c++17", "-fPIC", "-Wall", "-pthread"]
 # the kernels of the 16-bit-operand speed path are compiled twice (operand.h): bf16 operands, and fp16 operands (-> <name>_f16.o)
 DUAL_OPERAND = ["gemm_bf16.hip", "gemm_a384.hip", "gemm_n384.hip", "mlp_fused.hip", "qkv_fused.hip", "gemm_proj.hip", "attention_bf16.hip"]
-HEADERS = ["common.h", "operand.h", "mlp_device.h", "mlp_tile_device.h", "mlp_train_device.h", "rnvp_device.h", "simple_gcn_device.h", "split_operand.h", "tile_epilogue.h", "wvn_internal.h", os.path.join("..", "..", "include", "wvn_hip.h")]
+HEADERS = ["common.h", "operand.h", "mlp_device.h", "mlp_tile_device.h", "mlp_train_device.h", "rnvp_device.h", "simple_gcn_device.h", "split_operand.h", "tile_epilogue.h", "wvn_internal.h", "jpeg_host.h", os.path.join("..", "..", "include", "wvn_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mcode-object-version=5", "-Wall",
          "-Wno-unused-function"]
 # bit-exact integer outputs need un-fused multiply/add in the k-means kernels (see stego.hip)
@@ -103,13 +107,24 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if force or _stale(obj, [src] + hdrs) or _cmd_changed(obj, cmd):
             jobs.append((o, cmd))
 
+    host_objs = set()
+    for s in HOST_SOURCES:
+        src = os.path.join(HERE, s)
+        o = s.replace(".cpp", ".o")
+        obj = os.path.join(OBJ, o)
+        cmd = [hipcc] + HOST_FLAGS + ["-c", src, "-o", obj]
+        units.append((s, o, []))
+        host_objs.add(o)
+        if force or _stale(obj, [src] + hdrs) or _cmd_changed(obj, cmd):
+            jobs.append((o, cmd))
+
     screen = _hazard_scanner()
 
     def run(job):
         name, cmd = job
         r = subprocess.run(cmd, capture_output=True, text=True)
         log = r.stdout + r.stderr
-        if r.returncode == 0 and screen is not None:
+        if r.returncode == 0 and screen is not None and name not in host_objs:   # (a host unit has no ISA to screen)
             # the gfx950 hazards LLVM does not pad (common.h: wvn_store_b128_guarded; hand-issued scalar loads) are
             # screened on the ISA of EVERY unit that is recompiled, and a hit fails the build -- not only tests/test_isa_hazards.py
             asm = cmd[-1] + ".s"
@@ -143,7 +158,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
                     raise RuntimeError(f"hipcc failed on {name}:\n{log}")
     objs = [os.path.join(OBJ, o) for _, o, _ in units]
     if force or jobs or _stale(LIB, objs):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-o", LIB] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed:\n" + r.stdout + r.stderr)

@@ -114,6 +114,13 @@ class FeatureExtractor:
         if self._extractor is not None:
             self._extractor.change_device(device)
 
+    def decode(self, frames, **kwargs) -> torch.Tensor:
+        """Compressed camera frames (JPEG bytes, or a list of them, all of one size and sampling) -> uint8 [B,3,H,W] on the
+        extractor's device: ops.jpeg_decode with strict=True.  ``fe.predict_and_extract(fe.decode(msgs), model, cg)`` is the whole
+        image callback of a node that subscribes to a .../compressed topic."""
+        kwargs.setdefault("strict", True)
+        return ops.jpeg_decode(frames, self._device, **kwargs)[0]
+
     # ------------------------------------------------------------------------------------------ extract
     @torch.no_grad()
     def extract(self, img: torch.Tensor, **kwargs):

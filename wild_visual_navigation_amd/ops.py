@@ -1517,3 +1517,123 @@ def metric_auroc_weighted(score: torch.Tensor, pos: torch.Tensor, neg: torch.Ten
     n = neg.reshape(-1).to(torch.int64)[order].contiguous()
     check(lib().wvn_metric_auroc_weighted(ptr(s), ptr(p), ptr(n), E, ptr(scal), ptr(cnt), stream()), "wvn_metric_auroc_weighted")
     return scal, cnt
+
+
+# ---- JPEG ingest (include/wvn_hip.h: "JPEG ingest"; csrc/jpeg_host.cpp + csrc/jpeg.hip) ----
+def _jpeg_buffers(frames, who: str):
+    """bytes / bytearray / memoryview / uint8 CPU tensor, or a list of those -> [numpy uint8 views] (no copy; the views keep the bytes alive)."""
+    import numpy as np
+
+    if isinstance(frames, (bytes, bytearray, memoryview, torch.Tensor)) or hasattr(frames, "__array_interface__"):
+        frames = [frames]
+    out = []
+    for i, f in enumerate(frames):
+        if isinstance(f, torch.Tensor):
+            if f.is_cuda or f.dtype != torch.uint8 or f.dim() != 1:
+                raise _lib.WvnError(f"{who}: frame {i}: a 1-d uint8 CPU tensor of the file's bytes expected, got {f.dtype} {tuple(f.shape)} on {f.device}")
+            a = f.contiguous().numpy()
+        elif isinstance(f, (bytes, bytearray, memoryview)):
+            a = np.frombuffer(f, dtype=np.uint8)
+        elif hasattr(f, "__array_interface__"):
+            a = np.ascontiguousarray(f)
+            if a.dtype != np.uint8 or a.ndim != 1:
+                raise _lib.WvnError(f"{who}: frame {i}: a 1-d uint8 array of the file's bytes expected, got {a.dtype} {a.shape}")
+        else:
+            raise _lib.WvnError(f"{who}: frame {i}: bytes, bytearray or a uint8 CPU tensor expected, got {type(f).__name__}")
+        if a.size == 0:
+            raise _lib.WvnError(f"{who}: frame {i} is empty")
+        out.append(a)
+    if not out:
+        raise _lib.WvnError(f"{who}: no frames")
+    return out
+
+
+def jpeg_status_name(status: int) -> str:
+    return "WVN_JPEG_" + _lib.JPEG_STATUS[status] if 0 <= status < len(_lib.JPEG_STATUS) else f"status {status}"
+
+
+def _jpeg_info(a):
+    g = _lib.JpegGeometry()
+    return lib().wvn_jpeg_info(a.ctypes.data, a.size, C.byref(g)), g
+
+
+def jpeg_info(data) -> dict:
+    """Header of one JPEG stream (host only): {"width", "height", "components", "sampling": "gray" | "4:4:4" | "4:2:2" | "4:2:0",
+    "restart_interval"}.  WvnError naming the status for a stream the decoder refuses (its tables and scan header are checked too)."""
+    (a,) = _jpeg_buffers(data, "jpeg_info")
+    rc, g = _jpeg_info(a)
+    if rc != _lib.JPEG_OK:
+        raise _lib.WvnError(f"jpeg_info: {jpeg_status_name(rc)}" if rc < 1000 else "jpeg_info: bad argument")
+    return {"width": g.width, "height": g.height, "components": g.components, "sampling": _lib.JPEG_SAMPLING[g.sampling],
+            "restart_interval": g.restart_interval}
+
+
+def jpeg_coefficients(data):
+    """The host stage alone, for one frame: (status, coef int16 [blocks, 64] quantised and in natural order, component after
+    component, qtables int32 [3, 64] in natural order, geometry or None).  CPU tensors; nothing touches the GPU."""
+    (a,) = _jpeg_buffers(data, "jpeg_coefficients")
+    rc, g = _jpeg_info(a)
+    if rc != _lib.JPEG_OK:
+        return rc, None, None, None
+    n = lib().wvn_jpeg_coef_bytes(C.byref(g))
+    coef = torch.empty(n // 128, 64, dtype=torch.int16)
+    qt = torch.empty(3, 64, dtype=torch.int16)
+    rc = lib().wvn_jpeg_coefficients(a.ctypes.data, a.size, C.byref(g), coef.data_ptr(), n, qt.data_ptr())
+    if rc >= 1000:
+        check(rc, "wvn_jpeg_coefficients")
+    return rc, coef, qt.to(torch.int32) & 0xFFFF, g
+
+
+def jpeg_decode(frames, device, *, gray: bool = False, threads: int = 8, strict: bool = True):
+    """Baseline JPEG streams -> (uint8 [B,3,H,W] on `device`, status int32 [B] on the CPU), bit-identical to libjpeg's default decode
+    (Pillow, cv2.imdecode up to its BGR order): the Huffman stage on `threads` host workers (default 8, at most 16), inverse DCT,
+    fancy chroma upsampling and YCbCr -> RGB in two HIP kernels on the current stream.  ``frames``: bytes, bytearray, a uint8 CPU
+    tensor, or a list of those; all frames of a call share size, sampling and component count (WvnError before anything runs
+    otherwise).  ``gray=True``: [B,1,H,W], one-component files only.  ``strict=True`` raises WvnError naming the first failing frame and
+    its status; ``strict=False`` returns such a frame all zero with its status (jpeg_status_name), its neighbours untouched -- but a
+    batch in which NO frame has a readable header raises even then: without one geometry there is no frame size to return."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.WvnError(f"jpeg_decode: device must be a GPU (got {device}); the HIP path has no CPU fallback")
+    threads = int(threads)
+    if not 1 <= threads <= _lib.JPEG_MAX_THREADS:
+        raise _lib.WvnError(f"jpeg_decode: threads={threads} must lie in [1, {_lib.JPEG_MAX_THREADS}]")
+    bufs = _jpeg_buffers(frames, "jpeg_decode")
+    B = len(bufs)
+    if B > _lib.JPEG_MAX_BATCH:
+        raise _lib.WvnError(f"jpeg_decode: {B} frames in one call; at most {_lib.JPEG_MAX_BATCH}")
+    ptrs = (C.c_void_p * B)(*[a.ctypes.data for a in bufs])
+    sizes = (C.c_size_t * B)(*[a.size for a in bufs])
+    status = (C.c_int * B)()
+    # the geometry of every frame in one host call (markers and lengths up to SOS; the tables are built once, by the decode)
+    geos = (_lib.JpegGeometry * B)()
+    check(lib().wvn_jpeg_probe_batch(ptrs, sizes, B, geos, status), "wvn_jpeg_probe_batch")
+    geo = None
+    for i in range(B):
+        g = geos[i]
+        if status[i] != _lib.JPEG_OK:
+            if strict:
+                raise _lib.WvnError(f"jpeg_decode: frame {i}: {jpeg_status_name(status[i])}")
+            continue
+        if geo is None:
+            geo, first = g, i
+        elif (g.width, g.height, g.components, g.sampling) != (geo.width, geo.height, geo.components, geo.sampling):
+            def _d(x):
+                return f"{x.width}x{x.height} {_lib.JPEG_SAMPLING[x.sampling]}"
+            raise _lib.WvnError(f"jpeg_decode: mixed geometry in one batch: frame {first} is {_d(geo)}, frame {i} is {_d(g)}; "
+                                "group the frames and decode each group")
+    if geo is None:
+        raise _lib.WvnError("jpeg_decode: no frame of the batch has a readable header: the frame size is unknown")
+    if gray and geo.components != 1:
+        raise _lib.WvnError("jpeg_decode: gray=True needs one-component (grayscale) files")
+    with torch.cuda.device(device):
+        out = torch.empty(B, 1 if gray else 3, geo.height, geo.width, dtype=torch.uint8, device=device)
+        ws = torch.empty(lib().wvn_jpeg_workspace_bytes(C.byref(geo), B), dtype=torch.uint8, device=device)
+        check(lib().wvn_jpeg_decode_batch(ptrs, sizes, B, C.byref(geo), ptr(out), int(gray), ptr(ws), threads, status, stream()),
+              "wvn_jpeg_decode_batch")
+    st = torch.tensor(list(status), dtype=torch.int32)
+    if strict:
+        for i, rc in enumerate(status):
+            if rc != _lib.JPEG_OK:
+                raise _lib.WvnError(f"jpeg_decode: frame {i}: {jpeg_status_name(rc)}")
+    return out, st
