@@ -55,6 +55,16 @@ def conv_bn_act(x, weight, bn, stride, pad, residual=None, relu=True, dtype=torc
     return F.relu(y) if relu else y
 
 
+def conv_affine_act(x, weight, scale, shift, stride, pad, residual=None, relu=True, dtype=torch.float64):
+    """The same with the folded terms given as they are: relu(conv2d(x) * scale[c] + shift[c] + residual).  On integer inputs with
+    scale in {0.5, 1, 2, -1} every intermediate is an integer or a half: exact in float64 and, below 2^24, in fp32 too."""
+    y = F.conv2d(x.to(dtype), weight.to(dtype), stride=stride, padding=pad)
+    y = y * scale.to(dtype).view(1, -1, 1, 1) + shift.to(dtype).view(1, -1, 1, 1)
+    if residual is not None:
+        y = y + residual.to(dtype)
+    return F.relu(y) if relu else y
+
+
 def _basic_block(x, sd, name, stride, dtype):
     out = F.relu(_bn(F.conv2d(x, sd[name + ".conv1.weight"].to(dtype), stride=stride, padding=1), sd, name + ".bn1", dtype))
     out = _bn(F.conv2d(out, sd[name + ".conv2.weight"].to(dtype), stride=1, padding=1), sd, name + ".bn2", dtype)
