@@ -18,7 +18,6 @@ from typing import Optional, Tuple
 import torch
 
 from .. import _lib
-from ..distributed import allreduce_max_
 from ..model.simple_gcn import SimpleGCN
 from .trainer import TrainerState
 
@@ -26,44 +25,20 @@ from .trainer import TrainerState
 class GcnTrainer(TrainerState):
     def __init__(self, model: SimpleGCN, lr: float = 1e-3, std_factor: float = 0.5, w_trav: float = 0.03, w_reco: float = 0.5,
                  process_group=None, method: str = "latest_measurement", anomaly_balanced: bool = True):
-        if method not in _lib.CONF_METHODS:
-            raise ValueError(f"Unknown ConfidenceGenerator method {method!r} (one of {', '.join(_lib.CONF_METHODS)})")
-        self.model = model
-        self.method, self.anomaly_balanced = method, bool(anomaly_balanced)
+        super().__init__(model, lr, method, process_group)
+        self.anomaly_balanced = bool(anomaly_balanced)
         # a conf descriptor (device state) for anything but the original configuration, as in MlpTrainer
         self._conf = method != "latest_measurement" or not self.anomaly_balanced
-        self.lr, self.std_factor, self.w_trav, self.w_reco = lr, std_factor, w_trav, w_reco
-        self.group = process_group
-        self.step = 0
-        self._state_dev = None
+        self.std_factor, self.w_trav, self.w_reco = std_factor, w_trav, w_reco
         self.last_confidence: Optional[torch.Tensor] = None
-        self.comm_events = None   # set to [] to collect (start, end) CUDA-event pairs around the two all-reduces of every step
         self._ws = None
         self._saved = None        # (nodes, capacity) of the last phase A
 
-    def _state(self, dev):
-        if self._state_dev != dev:
-            n = self.model.flat_params().numel()
-            self.grads = torch.zeros(n + 2, dtype=torch.float32, device=dev)
-            if self._state_dev is not None:   # change_device in the middle of a mission: moments and statistic move with the model
-                self.m, self.v, self.conf_state = self.m.to(dev), self.v.to(dev), self.conf_state.to(dev)
-            else:
-                self.m = torch.zeros(n, dtype=torch.float32, device=dev)
-                self.v = torch.zeros(n, dtype=torch.float32, device=dev)
-                self.conf_state = self._initial_conf_state(dev)
-            self.minmax = torch.zeros(2, dtype=torch.float32, device=dev)
-            self.stats = torch.zeros(4, dtype=torch.float64, device=dev)
-            self.losses = torch.zeros(5, dtype=torch.float32, device=dev)
-            self.sync_word = torch.zeros(1, dtype=torch.int32, device=dev)   # arrival counter of phase A's last layer
-            self.bad_edges = torch.zeros(1, dtype=torch.int32, device=dev)   # edges the last phase A dropped (an endpoint outside [0, N))
-            self._ws = self._saved = None
-            self._state_dev = dev
-
-    def to(self, device) -> "GcnTrainer":
-        """Move the trainer's state after the model has moved (``TraversabilityEstimator.change_device``)."""
-        if self._state_dev is not None:
-            self._state(torch.device(device))
-        return self
+    def _alloc_extra(self, dev):
+        self.minmax = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.sync_word = torch.zeros(1, dtype=torch.int32, device=dev)   # arrival counter of phase A's last layer
+        self.bad_edges = torch.zeros(1, dtype=torch.int32, device=dev)   # edges the last phase A dropped (an endpoint outside [0, N))
+        self._ws = self._saved = None
 
     def _workspace(self, nodes: int, capacity: int) -> torch.Tensor:
         need = _lib.lib().wvn_gcn_train_workspace_bytes(C.byref(self.model.desc), nodes, capacity)
@@ -98,6 +73,18 @@ class GcnTrainer(TrainerState):
         """Phases A and B on this rank's graphs (x [N, >= D], edge_index [2, E] int64, y [N], y_valid [N]; N may be 0), with both
         all-reduces: the flat gradient of the loss over all ranks' nodes, in ``flat_params()`` order, with the two loss sums behind
         it.  No Adam step."""
+        self._phases_ab(x, edge_index, y, y_valid, want_confidence)
+        return self.grads
+
+    @torch.no_grad()
+    def train_step(self, x: torch.Tensor, edge_index: torch.Tensor, y: torch.Tensor, y_valid: torch.Tensor,
+                   want_confidence: bool = False) -> torch.Tensor:
+        """One step on this rank's graphs.  Returns the device tensor losses[5] = {total, loss_trav, loss_reco, conf_mean, conf_std}
+        (no host synchronisation here)."""
+        return self._phase_c(self._phases_ab(x, edge_index, y, y_valid, want_confidence))
+
+    def _phases_ab(self, x, edge_index, y, y_valid, want_confidence):
+        """``forward_backward``; returns the step's ConfDesc (or None) for phase C."""
         _lib.require_cuda(x, "x")
         lib, d = _lib.lib(), self.model.desc
         dev = x.device
@@ -118,52 +105,25 @@ class GcnTrainer(TrainerState):
         _lib.require_cuda(flat, "parameters")
         st = _lib.stream()
         conf = torch.empty(N, dtype=torch.float32, device=dev) if want_confidence else None
-        moving = self.method == "moving_average"
-        cd = _lib.ConfDesc(_lib.CONF_METHODS[self.method], int(self.anomaly_balanced), self.conf_state.data_ptr(), self.minmax.data_ptr())
-        cdp = C.byref(cd) if self._conf else None
-        # A rank whose shard is empty this step still takes part in both collectives, contributing zeros: every rank makes the same
-        # sequence of calls whatever its node count.
-        if N > 0:
-            cap = E + N
-            ws = self._workspace(N, cap)
+        cd = self._conf_desc()
+        cdp = None if cd is None else C.byref(cd)
+        cap = E + N
+        ws = self._workspace(N, cap) if N else None
+
+        def phase_a():
             _lib.check(lib.wvn_gcn_train_phase_a(C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), edge_index.data_ptr() if E else 0,
                                                  edge_index.stride(0), edge_index.stride(1), E, yv.data_ptr(), N, cap,
                                                  self.stats.data_ptr(), self.bad_edges.data_ptr(), ws.data_ptr(), ws.numel(),
                                                  self.sync_word.data_ptr(), cdp, st), "wvn_gcn_train_phase_a")
             self._saved = (N, cap)
-        else:
-            self.stats.zero_()
-            self.bad_edges.zero_()
-            if moving:
-                self.minmax.fill_(-float("inf"))
-        self._timed_allreduce(self.stats)
-        if moving:   # min / max of the reconstruction loss over ALL ranks' nodes (the same collective on every rank)
-            allreduce_max_(self.minmax, self.group)
-        if N > 0:
+
+        def phase_b():
             _lib.check(lib.wvn_gcn_train_phase_b(C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), y.data_ptr(), yv.data_ptr(), N, cap,
                                                  self.stats.data_ptr(), self.std_factor, self.w_trav, self.w_reco, self.grads.data_ptr(),
                                                  _lib.ptr(conf), ws.data_ptr(), ws.numel(), cdp, st), "wvn_gcn_train_phase_b")
-        else:
-            self.grads.zero_()
-        self._timed_allreduce(self.grads)
-        self.last_confidence = conf
-        return self.grads
 
-    @torch.no_grad()
-    def train_step(self, x: torch.Tensor, edge_index: torch.Tensor, y: torch.Tensor, y_valid: torch.Tensor,
-                   want_confidence: bool = False) -> torch.Tensor:
-        """One step on this rank's graphs.  Returns the device tensor losses[5] = {total, loss_trav, loss_reco, conf_mean, conf_std}
-        (no host synchronisation here)."""
-        self.forward_backward(x, edge_index, y, y_valid, want_confidence)
-        lib, d, flat, st = _lib.lib(), self.model.desc, self.model.flat_params(), _lib.stream()
-        self.step += 1
-        if self._conf:
-            cd = _lib.ConfDesc(_lib.CONF_METHODS[self.method], int(self.anomaly_balanced), self.conf_state.data_ptr(), self.minmax.data_ptr())
-            _lib.check(lib.wvn_mlp_train_phase_c_conf(C.byref(d), flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
-                                                      self.v.data_ptr(), self.step, self.lr, self.stats.data_ptr(), self.w_trav,
-                                                      self.w_reco, self.losses.data_ptr(), C.byref(cd), st), "phase_c")
-        else:
-            _lib.check(lib.wvn_mlp_train_phase_c(C.byref(d), flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                                 self.step, self.lr, self.stats.data_ptr(), self.w_trav, self.w_reco,
-                                                 self.losses.data_ptr(), st), "phase_c")
-        return self.losses
+        if N == 0:
+            self.bad_edges.zero_()
+        self._exchange(phase_a, phase_b, launch=N > 0)
+        self.last_confidence = conf
+        return cd

@@ -22,41 +22,19 @@ from .trainer import TrainerState
 
 
 class RnvpTrainer(TrainerState):
+    GRAD_TAIL = 0   # no loss sums behind the gradient: the loss is the statistic's mean
+    N_LOSSES = 3
+    _conf = True    # the confidence statistic always lives in ``conf_state`` (phase C commits it for every method)
+
     def __init__(self, model: LinearRnvp, lr: float = 1e-3, method: str = "latest_measurement", process_group=None):
-        if method not in _lib.CONF_METHODS:
-            raise ValueError(f"Unknown ConfidenceGenerator method {method!r} (one of {', '.join(_lib.CONF_METHODS)})")
-        self.model = model
-        self.method = method
-        self.lr = lr
-        self.group = process_group
-        self.step = 0
-        self._state_dev = None
-        self.comm_events = None   # set to [] to collect (start, end) CUDA-event pairs around the two all-reduces of every step
+        super().__init__(model, lr, method, process_group)
         self._ws = None
         self._tpacked = None
         self._tpacked_key = None
         self.last_score = None    # phase A's score of the last step's rows (device)
 
-    def _state(self, dev):
-        if self._state_dev != dev:
-            n = self.model.flat_params().numel()
-            self.grads = torch.zeros(n, dtype=torch.float32, device=dev)
-            if self._state_dev is not None:   # change_device in the middle of a mission: moments and statistic move with the model
-                self.m, self.v, self.conf_state = self.m.to(dev), self.v.to(dev), self.conf_state.to(dev)
-            else:
-                self.m = torch.zeros(n, dtype=torch.float32, device=dev)
-                self.v = torch.zeros(n, dtype=torch.float32, device=dev)
-                self.conf_state = self._initial_conf_state(dev)
-            self.stats = torch.zeros(4, dtype=torch.float64, device=dev)
-            self.losses = torch.zeros(3, dtype=torch.float32, device=dev)
-            self._ws = self._tpacked = self._tpacked_key = None
-            self._state_dev = dev
-
-    def to(self, device) -> "RnvpTrainer":
-        """Move the trainer's state after the model has moved (``TraversabilityEstimator.change_device``)."""
-        if self._state_dev is not None:
-            self._state(torch.device(device))
-        return self
+    def _alloc_extra(self, dev):
+        self._ws = self._tpacked = self._tpacked_key = None
 
     def _images(self):
         """(forward blob, transposed images) for the model's current parameters; the stacked masks and permutations phase C re-packs
@@ -103,15 +81,17 @@ class RnvpTrainer(TrainerState):
         packed, tpacked = self._images()
         ws, st = self._workspace(R), _lib.stream()
         score = torch.empty(R, dtype=torch.float32, device=x.device)
-        # A rank whose shard is empty this step still takes part in both collectives, contributing zeros: every rank makes
-        # the same sequence of calls whatever its row count.
-        _lib.check(lib.wvn_rnvp_train_phase_a(C.byref(model.desc), packed.data_ptr(), x.data_ptr() if R else 0, x.stride(0) if R else D,
-                                              R, score.data_ptr() if R else 0, self.stats.data_ptr(), ws.data_ptr(), ws.numel(), st),
-                   "wvn_rnvp_train_phase_a")
-        self._timed_allreduce(self.stats)
-        _lib.check(lib.wvn_rnvp_train_phase_b(C.byref(model.desc), packed.data_ptr(), tpacked.data_ptr(), R, self.stats.data_ptr(),
-                                              self.grads.data_ptr(), ws.data_ptr(), ws.numel(), st), "wvn_rnvp_train_phase_b")
-        self._timed_allreduce(self.grads)
+
+        def phase_a():
+            _lib.check(lib.wvn_rnvp_train_phase_a(C.byref(model.desc), packed.data_ptr(), x.data_ptr() if R else 0, x.stride(0) if R else D,
+                                                  R, score.data_ptr() if R else 0, self.stats.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                       "wvn_rnvp_train_phase_a")
+
+        def phase_b():
+            _lib.check(lib.wvn_rnvp_train_phase_b(C.byref(model.desc), packed.data_ptr(), tpacked.data_ptr(), R, self.stats.data_ptr(),
+                                                  self.grads.data_ptr(), ws.data_ptr(), ws.numel(), st), "wvn_rnvp_train_phase_b")
+
+        self._exchange(phase_a, phase_b, launch=True)   # the entry points take an empty shard (R = 0) themselves
         self.last_score = score
         return self.grads
 

@@ -27,10 +27,47 @@ from ..model.simple_mlp import SimpleMLP
 
 
 class TrainerState:
-    """What the fused trainers (MlpTrainer, RnvpTrainer, GcnTrainer) keep alike: the confidence statistic's device state and its exchange with a
-    ConfidenceGenerator, the Adam moments in ``torch.optim.Adam.state_dict()`` shape, the timed all-reduce.  A subclass provides
-    ``model`` (``flat_params()``, ``_params_in_order()``), ``_state(dev)`` (which creates ``m``, ``v``, ``conf_state``), ``step``,
-    ``lr``, ``group``, ``comm_events`` and ``_state_dev``."""
+    """What the fused trainers (MlpTrainer, GcnTrainer, RnvpTrainer) share: the device buffers of a step, the confidence statistic's
+    device state and its exchange with a ConfidenceGenerator, the Adam moments in ``torch.optim.Adam.state_dict()`` shape, and the
+    data-parallel skeleton of the step (``_exchange``: phases A and B with the collectives between them; ``_phase_c`` for the two
+    trainers of TraversabilityLoss).  A subclass provides the phase calls and, in ``_alloc_extra``, the buffers only it has."""
+
+    GRAD_TAIL = 2     # floats behind the gradient in ``grads``: the two loss sums (RnvpTrainer: 0)
+    N_LOSSES = 5      # {total, loss_trav, loss_reco, conf_mean, conf_std} (RnvpTrainer: {loss, conf_mean, conf_std})
+    minmax = None     # {max, -min} of the reconstruction loss, exchanged for moving_average by the trainers that allocate it
+
+    def __init__(self, model, lr: float, method: str, process_group):
+        if method not in _lib.CONF_METHODS:
+            raise ValueError(f"Unknown ConfidenceGenerator method {method!r} (one of {', '.join(_lib.CONF_METHODS)})")
+        self.model, self.lr, self.method, self.group = model, lr, method, process_group
+        self.step = 0
+        self._state_dev = None
+        self.comm_events = None   # set to [] to collect (start, end) CUDA-event pairs around the two sum all-reduces of every step
+
+    def _state(self, dev) -> None:
+        if self._state_dev == dev:
+            return
+        n = self.model.flat_params().numel()
+        self.grads = torch.zeros(n + self.GRAD_TAIL, dtype=torch.float32, device=dev)
+        if self._state_dev is not None:   # change_device in the middle of a mission: moments and statistic move with the model
+            self.m, self.v, self.conf_state = self.m.to(dev), self.v.to(dev), self.conf_state.to(dev)
+        else:
+            self.m = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.v = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.conf_state = self._initial_conf_state(dev)
+        self.stats = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.losses = torch.zeros(self.N_LOSSES, dtype=torch.float32, device=dev)
+        self._alloc_extra(dev)
+        self._state_dev = dev
+
+    def _alloc_extra(self, dev) -> None:
+        """Allocate or reset what only the subclass keeps on ``dev`` (called when the state is created or has moved)."""
+
+    def to(self, device) -> "TrainerState":
+        """Move the trainer's state after the model has moved (``TraversabilityEstimator.change_device``)."""
+        if self._state_dev is not None:
+            self._state(torch.device(device))
+        return self
 
     @staticmethod
     def _initial_conf_state(dev) -> torch.Tensor:
@@ -116,45 +153,69 @@ class TrainerState:
         b.record()
         self.comm_events.append((a, b))
 
+    def _exchange(self, phase_a, phase_b, launch: bool) -> None:
+        """Phases A and B of one step (two callables that enqueue them) with the collectives of the step, in their one order:
+
+            phase A -> SUM of ``stats`` (timed) -> for moving_average MAX of ``minmax`` (untimed) -> phase B -> SUM of ``grads`` (timed)
+
+        Every rank makes this same sequence of collective calls whatever its row count; a rank that made another would leave
+        the others hanging in RCCL.  So a rank whose shard is empty this step (ragged frame sharding) takes part in all of them:
+        with ``launch`` False it skips both phases and contributes their neutral elements instead (zeros; -inf for the extremes),
+        with ``launch`` True its phases are entry points that take zero rows themselves (RnvpTrainer)."""
+        moving = self.minmax is not None and self.method == "moving_average"
+        if launch:
+            phase_a()
+        else:
+            self.stats.zero_()
+            if moving:
+                self.minmax.fill_(-float("inf"))
+        self._timed_allreduce(self.stats)
+        if moving:   # min / max of the reconstruction loss over ALL ranks' rows
+            allreduce_max_(self.minmax, self.group)
+        if launch:
+            phase_b()
+        else:
+            self.grads.zero_()
+        self._timed_allreduce(self.grads)
+
+    def _conf_desc(self) -> Optional[_lib.ConfDesc]:
+        """The ConfDesc that phases A, B and C of one MlpTrainer / GcnTrainer step share; None for the original configuration
+        (latest_measurement, anomaly_balanced), which keeps its own entry points and no device state."""
+        if not self._conf:
+            return None
+        return _lib.ConfDesc(_lib.CONF_METHODS[self.method], int(self.anomaly_balanced), self.conf_state.data_ptr(),
+                             self.minmax.data_ptr())
+
+    def _phase_c(self, cd: Optional[_lib.ConfDesc]) -> torch.Tensor:
+        """Adam, the losses and (with a ConfDesc) the commit of the confidence statistic: phase C of MlpTrainer and GcnTrainer."""
+        lib, st = _lib.lib(), _lib.stream()
+        self.step += 1
+        args = (C.byref(self.model.desc), self.model.flat_params().data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
+                self.v.data_ptr(), self.step, self.lr, self.stats.data_ptr(), self.w_trav, self.w_reco, self.losses.data_ptr())
+        if cd is None:
+            _lib.check(lib.wvn_mlp_train_phase_c(*args, st), "phase_c")
+        else:
+            _lib.check(lib.wvn_mlp_train_phase_c_conf(*args, C.byref(cd), st), "phase_c")
+        return self.losses
+
 
 class MlpTrainer(TrainerState):
     def __init__(self, model: SimpleMLP, lr: float = 1e-3, std_factor: float = 0.5, w_trav: float = 0.03,
                  w_reco: float = 0.5, process_group=None, fused: bool = True, method: str = "latest_measurement",
                  anomaly_balanced: bool = True):
-        if method not in _lib.CONF_METHODS:
-            raise ValueError(f"Unknown ConfidenceGenerator method {method!r} (one of {', '.join(_lib.CONF_METHODS)})")
-        self.model = model
-        self.method, self.anomaly_balanced = method, bool(anomaly_balanced)
+        super().__init__(model, lr, method, process_group)
+        self.anomaly_balanced = bool(anomaly_balanced)
         # the *_conf entry points (device state) for anything but the original configuration, which keeps its entry points
         self._conf = method != "latest_measurement" or not self.anomaly_balanced
-        self.lr, self.std_factor, self.w_trav, self.w_reco = lr, std_factor, w_trav, w_reco
-        self.group = process_group
-        self.step = 0
-        self._state_dev = None
+        self.std_factor, self.w_trav, self.w_reco = std_factor, w_trav, w_reco
         self.last_confidence: Optional[torch.Tensor] = None
-        self.comm_events = None   # set to [] to collect (start, end) CUDA-event pairs around the two all-reduces of every step
         # True: the four-launch step of csrc/mlp_train.hip where its geometry applies (256 / 32 hidden units, <= 2048 rows);
         # False: the general path (one kernel per stage, 17-20 launches).  Same arithmetic, other summation orders.
         self.fused = fused
 
-    def _state(self, dev):
-        if self._state_dev != dev:
-            n = self.model.flat_params().numel()
-            self.grads = torch.zeros(n + 2, dtype=torch.float32, device=dev)
-            if self._state_dev is not None:   # change_device in the middle of a mission: the Adam moments move with the model
-                self.m, self.v = self.m.to(dev), self.v.to(dev)
-            else:
-                self.m = torch.zeros(n, dtype=torch.float32, device=dev)
-                self.v = torch.zeros(n, dtype=torch.float32, device=dev)
-            if self._state_dev is not None:   # (the confidence statistic's memory moves too)
-                self.conf_state = self.conf_state.to(dev)
-            else:
-                self.conf_state = self._initial_conf_state(dev)
-            self.minmax = torch.zeros(2, dtype=torch.float32, device=dev)
-            self.stats = torch.zeros(4, dtype=torch.float64, device=dev)
-            self.losses = torch.zeros(5, dtype=torch.float32, device=dev)
-            self.sync_word = torch.zeros(1, dtype=torch.int32, device=dev)   # arrival counter of the fused forward (zero between steps)
-            self._state_dev = dev
+    def _alloc_extra(self, dev):
+        self.minmax = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.sync_word = torch.zeros(1, dtype=torch.int32, device=dev)   # arrival counter of the fused forward (zero between steps)
 
     @torch.no_grad()
     def train_step(self, x: torch.Tensor, y: torch.Tensor, y_valid: torch.Tensor,
@@ -178,62 +239,22 @@ class MlpTrainer(TrainerState):
         ws = self.model._workspace(max(R, 1))
         st = _lib.stream()
         conf = torch.empty(R, dtype=torch.float32, device=dev) if want_confidence else None
-
-        # A rank whose shard is empty this step (ragged frame sharding) still takes part in both collectives, contributing
-        # zeros: every rank makes the same sequence of RCCL calls whatever its row count.
         rd = _lib.ptr(rows_dev)
-        if self._conf:
-            return self._train_step_conf(x, y, yv, R, rd, conf)
-        if R > 0:
-            _lib.check(lib.wvn_mlp_train_phase_a_rows(C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), yv.data_ptr(), R, rd,
-                                                      self.stats.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                      self.sync_word.data_ptr() if self.fused else 0, st), "phase_a")
-        else:
-            self.stats.zero_()
-        self._timed_allreduce(self.stats)
-        if R > 0:
-            _lib.check(lib.wvn_mlp_train_phase_b_rows(C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), y.data_ptr(),
-                                                      yv.data_ptr(), R, rd, self.stats.data_ptr(), self.std_factor, self.w_trav,
-                                                      self.w_reco, self.grads.data_ptr(), _lib.ptr(conf), ws.data_ptr(),
-                                                      ws.numel(), int(self.fused), st), "phase_b")
-        else:
-            self.grads.zero_()
-        self._timed_allreduce(self.grads)
-        self.step += 1
-        _lib.check(lib.wvn_mlp_train_phase_c(C.byref(d), flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
-                                             self.v.data_ptr(), self.step, self.lr, self.stats.data_ptr(), self.w_trav,
-                                             self.w_reco, self.losses.data_ptr(), st), "phase_c")
-        self.last_confidence = conf
-        return self.losses
+        # one step, two entry-point families: *_conf takes the ConfDesc before the stream, *_rows / phase_c do not know it
+        cd = self._conf_desc()
+        family, cda = ("_rows", ()) if cd is None else ("_conf", (C.byref(cd),))
 
-    def _train_step_conf(self, x, y, yv, R, rd, conf):
-        lib, d, flat, st = _lib.lib(), self.model.desc, self.model.flat_params(), _lib.stream()
-        ws = self.model._workspace(max(R, 1))
-        moving = self.method == "moving_average"
-        cd = _lib.ConfDesc(_lib.CONF_METHODS[self.method], int(self.anomaly_balanced), self.conf_state.data_ptr(),
-                           self.minmax.data_ptr())
-        if R > 0:
-            _lib.check(lib.wvn_mlp_train_phase_a_conf(C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), yv.data_ptr(), R, rd,
-                                                      self.stats.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                      self.sync_word.data_ptr() if self.fused else 0, C.byref(cd), st), "phase_a")
-        else:
-            self.stats.zero_()
-            if moving:
-                self.minmax.fill_(-float("inf"))
-        self._timed_allreduce(self.stats)
-        if moving:   # min / max of the reconstruction loss over ALL ranks' rows (the same collective on every rank)
-            allreduce_max_(self.minmax, self.group)
-        if R > 0:
-            _lib.check(lib.wvn_mlp_train_phase_b_conf(C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), y.data_ptr(),
-                                                      yv.data_ptr(), R, rd, self.stats.data_ptr(), self.std_factor, self.w_trav,
-                                                      self.w_reco, self.grads.data_ptr(), _lib.ptr(conf), ws.data_ptr(),
-                                                      ws.numel(), int(self.fused), C.byref(cd), st), "phase_b")
-        else:
-            self.grads.zero_()
-        self._timed_allreduce(self.grads)
-        self.step += 1
-        _lib.check(lib.wvn_mlp_train_phase_c_conf(C.byref(d), flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
-                                                  self.v.data_ptr(), self.step, self.lr, self.stats.data_ptr(), self.w_trav,
-                                                  self.w_reco, self.losses.data_ptr(), C.byref(cd), st), "phase_c")
+        def phase_a():
+            _lib.check(getattr(lib, "wvn_mlp_train_phase_a" + family)(
+                C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), yv.data_ptr(), R, rd, self.stats.data_ptr(), ws.data_ptr(),
+                ws.numel(), self.sync_word.data_ptr() if self.fused else 0, *cda, st), "phase_a")
+
+        def phase_b():
+            _lib.check(getattr(lib, "wvn_mlp_train_phase_b" + family)(
+                C.byref(d), flat.data_ptr(), x.data_ptr(), x.stride(0), y.data_ptr(), yv.data_ptr(), R, rd, self.stats.data_ptr(),
+                self.std_factor, self.w_trav, self.w_reco, self.grads.data_ptr(), _lib.ptr(conf), ws.data_ptr(), ws.numel(),
+                int(self.fused), *cda, st), "phase_b")
+
+        self._exchange(phase_a, phase_b, launch=R > 0)
         self.last_confidence = conf
-        return self.losses
+        return self._phase_c(cd)

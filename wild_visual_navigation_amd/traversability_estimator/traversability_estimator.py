@@ -16,7 +16,10 @@ rnvp_trainer.py, data-parallel like the MLP step.  On ``device="cpu"`` it runs o
 ``params.model.name == "SimpleGCN"``: inference runs the model's HIP graph kernels; on a GPU device a training step runs the whole
 ``Batch`` (x, edge_index, y, y_valid) through the fused HIP phases of gcn_trainer.py, data-parallel like the MLP step (every rank
 trains on its own graphs).  On ``device="cpu"`` it runs through the model's torch statement, ``TraversabilityLoss``, backward and
-``torch.optim.Adam`` on one rank (``_train_graph``).
+``torch.optim.Adam`` on one rank.
+
+Every fused mode steps through ``_fused_step`` (the hand-off with the ConfidenceGenerator), both CPU modes through
+``_autograd_step``, and all of them end in ``_finish_step`` (the step's print, counter and dict).
 """
 import os
 from threading import Lock
@@ -32,7 +35,7 @@ from .gcn_trainer import GcnTrainer
 from .graphs import BaseGraph, DistanceWindowGraph, MaxElementsGraph
 from .nodes import MissionNode, SupervisionNode
 from .rnvp_trainer import RnvpTrainer
-from .trainer import MlpTrainer
+from .trainer import MlpTrainer, TrainerState
 
 
 def _get(cfg, key):
@@ -139,7 +142,7 @@ class TraversabilityEstimator:
         self._mission_graph.change_device(device)
         self._model = self._model.to(device)
         self._traversability_loss = self._traversability_loss.to(device)
-        if isinstance(self._optimizer, (RnvpTrainer, GcnTrainer)):
+        if isinstance(self._optimizer, TrainerState):
             self._optimizer.to(self._device)
 
     def update_visualization_node(self):
@@ -269,125 +272,69 @@ class TraversabilityEstimator:
         if all_ranks_ready(graph is not None, self._device):
             if graph is not None:
                 if self._anomaly_detection:
-                    return self._train_anomaly(graph, return_dict)
-                if self._graph_model:
-                    return self._train_graph(graph, return_dict)
-                with self._learning_lock:
-                    losses = self.train_on_batch(graph.x, graph.y, graph.y_valid)
-                log_step = (self._step % 20) == 0
-                vals = losses.tolist()  # the one host sync per step (the reference does three .item() calls)
-                if log_step:
-                    print(f"step: {self._step} | loss: {vals[0]:5f} | loss_trav: {vals[1]:5f} | loss_reco: {vals[2]:5f}")
-                self._step += 1
-                return_dict["loss_total"], return_dict["loss_trav"], return_dict["loss_reco"] = vals[0], vals[1], vals[2]
-                return return_dict
+                    keys = ("x",)
+                elif self._graph_model:
+                    keys = ("x", "edge_index", "y", "y_valid")
+                else:
+                    keys = ("x", "y", "y_valid")
+                if isinstance(self._optimizer, TrainerState):
+                    with self._learning_lock:
+                        losses = self._fused_step(*(getattr(graph, k) for k in keys))
+                    vals = losses.tolist()   # the one host read of the step (the reference does three .item() calls)
+                else:
+                    vals = self._autograd_step(graph, keys)
+                if self._anomaly_detection:   # AnomalyLoss reports no traversability or reconstruction loss
+                    vals = [vals[0], 0.0, 0.0]
+                return self._finish_step(vals, return_dict)
         return_dict["loss_total"] = -1
         return return_dict
 
-    def _train_anomaly(self, graph, return_dict):
-        """traversability_estimator.py:464-495 in the anomaly-detection mode: forward (the model's torch statement), AnomalyLoss,
-        backward, ``torch.optim.Adam`` step."""
-        log_step = (self._step % 20) == 0
-        if isinstance(self._optimizer, RnvpTrainer):
-            return self._train_anomaly_fused(graph, return_dict, log_step)
-        with self._learning_lock:
-            graph.x = graph.x.to(self._device)
-            res = self._model(graph)
-            self._loss, loss_aux, _ = self._traversability_loss(graph, res, step=self._step, log_step=log_step)
-            self._optimizer.zero_grad()
-            self._loss.backward()
-            self._optimizer.step()
-        total = self._loss.item()
-        if log_step:
-            print(f"step: {self._step} | loss: {total:5f} | loss_trav: {loss_aux['loss_trav'].item():5f} | "
-                  f"loss_reco: {loss_aux['loss_reco'].item():5f}")
+    def _finish_step(self, vals, return_dict):
+        """The tail of every route of ``train``: the print every 20 steps, the step counter, the reference's dict."""
+        if self._step % 20 == 0:
+            print(f"step: {self._step} | loss: {vals[0]:5f} | loss_trav: {vals[1]:5f} | loss_reco: {vals[2]:5f}")
         self._step += 1
-        return_dict["loss_total"] = total
-        return_dict["loss_trav"], return_dict["loss_reco"] = loss_aux["loss_trav"].item(), loss_aux["loss_reco"].item()
+        return_dict["loss_total"], return_dict["loss_trav"], return_dict["loss_reco"] = vals[0], vals[1], vals[2]
         return return_dict
 
-    def _train_graph(self, graph, return_dict):
-        """traversability_estimator.py:464-495 for the graph model: the Batch (x, edge_index, y, y_valid) through ``model(graph)``
-        (SimpleGCN's torch statement under autograd), TraversabilityLoss, backward, ``torch.optim.Adam`` step; on a GPU device the
-        fused step (``_train_graph_fused``)."""
-        log_step = (self._step % 20) == 0
-        if isinstance(self._optimizer, GcnTrainer):
-            return self._train_graph_fused(graph, return_dict, log_step)
+    def _autograd_step(self, graph, keys):
+        """traversability_estimator.py:464-495 on ``device="cpu"`` (SimpleGCN, anomaly detection): the Batch attributes ``keys`` to
+        the device, ``model(graph)`` (the model's torch statement under autograd), the loss module, backward, ``torch.optim.Adam``
+        step.  Returns [loss, loss_trav, loss_reco] as floats."""
         with self._learning_lock:
-            for k in ("x", "edge_index", "y", "y_valid"):
+            for k in keys:
                 setattr(graph, k, getattr(graph, k).to(self._device))
             res = self._model(graph)
-            self._loss, loss_aux, _ = self._traversability_loss(graph, res, step=self._step, log_step=log_step)
+            self._loss, loss_aux, _ = self._traversability_loss(graph, res, step=self._step, log_step=(self._step % 20) == 0)
             self._optimizer.zero_grad()
             self._loss.backward()
             self._optimizer.step()
-        vals = torch.stack([self._loss.detach().reshape(()), loss_aux["loss_trav"].detach(), loss_aux["loss_reco"].detach()]).tolist()
-        if log_step:
-            print(f"step: {self._step} | loss: {vals[0]:5f} | loss_trav: {vals[1]:5f} | loss_reco: {vals[2]:5f}")
-        self._step += 1
-        return_dict["loss_total"], return_dict["loss_trav"], return_dict["loss_reco"] = vals[0], vals[1], vals[2]
-        return return_dict
+        return [float(self._loss), float(loss_aux["loss_trav"]), float(loss_aux["loss_reco"])]
 
-    def _train_graph_fused(self, graph, return_dict, log_step):
-        """The same step on the HIP phases (GcnTrainer): forward, loss, gradient, Adam and the confidence statistic on the device,
-        with ``train_on_batch``'s hand-off to the ConfidenceGenerator; one host read."""
-        cg = self._traversability_loss._confidence_generator
-        tr = self._optimizer
-        with self._learning_lock:
-            if tr._conf and self._cg_version != cg._version:   # constructed, loaded, reset or updated on the host since the last step
-                tr.load_confidence_state(cg)
-                self._cg_version = cg._version
-            losses = tr.train_step(*(getattr(graph, k).to(self._device) for k in ("x", "edge_index", "y", "y_valid")))
-            with torch.no_grad():
-                if tr._conf:   # mean / var / std (and the running sums) of the step's method
-                    tr.store_confidence_state(cg)
-                else:
-                    cg.mean.copy_(losses[3:4])
-                    cg.std.copy_(losses[4:5])
-            self._loss = losses[0:1]
-        vals = losses.tolist()   # the one host read of the step
-        if log_step:
-            print(f"step: {self._step} | loss: {vals[0]:5f} | loss_trav: {vals[1]:5f} | loss_reco: {vals[2]:5f}")
-        self._step += 1
-        return_dict["loss_total"], return_dict["loss_trav"], return_dict["loss_reco"] = vals[0], vals[1], vals[2]
-        return return_dict
-
-    def _train_anomaly_fused(self, graph, return_dict, log_step):
-        """The same step on the HIP phases (RnvpTrainer): loss, gradient, Adam and the confidence statistic on the device; the
-        AnomalyLoss module's ConfidenceGenerator is refreshed from the device state; one host read."""
-        cg = self._traversability_loss._confidence_generator
-        tr = self._optimizer
-        with self._learning_lock:
-            if self._cg_version != cg._version:   # constructed, loaded, reset or updated on the host since the last step
-                tr.load_confidence_state(cg)
-                self._cg_version = cg._version
-            losses = tr.train_step(graph.x.to(self._device))
-            tr.store_confidence_state(cg)
-            self._loss = losses[0:1]
-        total = losses[0].item()   # the one host read of the step
-        if log_step:
-            print(f"step: {self._step} | loss: {total:5f} | loss_trav: {0.0:5f} | loss_reco: {0.0:5f}")
-        self._step += 1
-        return_dict["loss_total"], return_dict["loss_trav"], return_dict["loss_reco"] = total, 0.0, 0.0
-        return return_dict
-
-    def train_on_batch(self, x: torch.Tensor, y: torch.Tensor, y_valid: torch.Tensor) -> torch.Tensor:
-        """Fused forward + loss + backward + Adam on this rank's rows; updates the confidence statistic.
-        Returns the device tensor {total, trav, reco, conf_mean, conf_std} without synchronising."""
+    def _fused_step(self, *tensors) -> torch.Tensor:
+        """One step of the fused trainer (MlpTrainer, GcnTrainer, RnvpTrainer) on this rank's tensors, with the hand-off to the loss
+        module's ConfidenceGenerator: forward, loss, gradient, Adam and the confidence statistic run on the device; the generator
+        is loaded into the trainer's device state when it changed on the host, and refreshed from it after the step.  Returns the
+        trainer's device tensor of losses without synchronising."""
         cg = self._traversability_loss._confidence_generator
         tr = self._optimizer
         if tr._conf and self._cg_version != cg._version:   # constructed, loaded, reset or updated on the host since the last step
             tr.load_confidence_state(cg)
             self._cg_version = cg._version
-        losses = tr.train_step(x.to(self._device), y.to(self._device), y_valid.to(self._device))
+        losses = tr.train_step(*(t.to(self._device) for t in tensors))
         with torch.no_grad():
             if tr._conf:   # mean / var / std (and the running sums) of the step's method
                 tr.store_confidence_state(cg)
-            else:
+            else:          # the original MLP / GCN configuration keeps no device state: the step's losses carry mean and std
                 cg.mean.copy_(losses[3:4])
                 cg.std.copy_(losses[4:5])
         self._loss = losses[0:1]
         return losses
+
+    def train_on_batch(self, x: torch.Tensor, y: torch.Tensor, y_valid: torch.Tensor) -> torch.Tensor:
+        """Fused forward + loss + backward + Adam on this rank's rows; updates the confidence statistic.
+        Returns the device tensor {total, trav, reco, conf_mean, conf_std} without synchronising."""
+        return self._fused_step(x, y, y_valid)
 
     def plot_mission_node_prediction(self, node: MissionNode):
         """traversability_estimator.py:500-501: (traversability picture, confidence picture) of a node, np.uint8 HWC each."""
