@@ -1356,6 +1356,55 @@ int wvn_jpeg_device_stage(const wvn_jpeg_geometry* g, int B, void* workspace, vo
 int wvn_jpeg_decode_batch(const void* const* data, const size_t* sizes, int B, const wvn_jpeg_geometry* g, void* out_u8, int gray_out,
                           void* workspace, int threads, int* status, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Raw camera ingest (the sensor_msgs/Image branch of the reference's ros_image_to_torch, ros_converter.py:113-126, and the debayer +
+ * undistortion its launch files hand to image_proc_cuda_ros): a frame as the camera driver publishes it -> planar uint8 frames in
+ * device memory, at full resolution (wvn_unpack_frames) or rectified through a fixed-point map (wvn_rectify_frames).  Integers only;
+ * tests/rectify_ref.py states both in numpy and the result is that statement BIT FOR BIT.  The rules aim at cv2.cvtColor(Bayer),
+ * cv2.initUndistortRectifyMap / cv2.fisheye and cv2.remap(INTER_LINEAR, BORDER_CONSTANT 0); that parity is NOT pinned.
+ *
+ * Source: uint8, B frames `frame_stride` bytes apart, each H rows (WVN_SRC_PLANAR: 3 H rows, plane after plane: what
+ * wvn_jpeg_decode_batch writes, step = W) of `step` >= W bytes_per_pixel bytes; the padding of a row is never read.  Kinds:
+ * WVN_SRC_MONO8; WVN_SRC_RGB8 / WVN_SRC_BGR8 (packed, 3 bytes per pixel); WVN_SRC_PLANAR (R, G, B planes); the four mosaics, named by
+ * their 2 x 2 tile row by row: RGGB = R G / G B, BGGR = B G / G R, GBRG = G B / R G, GRBG = G R / B G.
+ *
+ * Demosaic (bilinear): at an interior site the site's own colour is the raw byte; at an R or B site G = (N + S + E + W + 2) >> 2 and
+ * the opposite colour = (NW + NE + SW + SE + 2) >> 2; at a G site the colour of its horizontal neighbours = (W + E + 1) >> 1, that of
+ * its vertical neighbours = (N + S + 1) >> 1.  The one-pixel ring: columns 0 and W - 1 take the result of columns 1 and W - 2, then
+ * rows 0 and H - 1 those of rows 1 and H - 2.  H, W >= 3, odd sizes included.
+ *
+ * Map: two int32 [h][w] planes in device memory, the source coordinates of every output pixel in Q5 (x 32, OpenCV's INTER_BITS),
+ * computed by the caller once per camera geometry (ops.rectify_map: float64 on the host).  Sampling: ix = qx >> 5 (arithmetic),
+ * ax = qx & 31, likewise y; p00, p01, p10, p11 the source values at (iy, ix), (iy, ix + 1), (iy + 1, ix), (iy + 1, ix + 1), a tap
+ * outside the frame 0; out = ((32 - ax)(32 - ay) p00 + ax (32 - ay) p01 + (32 - ax) ay p10 + ax ay p11 + 512) >> 10 per channel.
+ * Any int32 is a valid map entry: every tap is bounds-checked.  For a mosaic the source value of a channel is the demosaic above,
+ * ring included, so the one launch equals wvn_unpack_frames followed by wvn_rectify_frames on its planar result.
+ *
+ * Output: out_u8 [B][3][rows][cols] planar, R, G, B with WVN_ORDER_RGB and B, G, R with WVN_ORDER_BGR; a WVN_SRC_MONO8 source gives the
+ * plane three times, or [B][1][rows][cols] with WVN_ORDER_GRAY (mono8 only).  One launch on `stream`, no atomics, no host
+ * synchronisation, no workspace.  One thread writes four adjacent pixels of a row as one dword per plane; a group cut by the end of
+ * the row or not dword aligned is stored byte by byte.
+ * WVN_ERR_ARG before any launch: a null pointer, B < 1 or B > 65535, H or W < 3 for a mosaic and < 1 otherwise, h or w < 1, a side above
+ * WVN_FRAME_MAX_DIM, step < W bytes_per_pixel, frame_stride smaller than the bytes read of one frame, an unknown kind or order,
+ * WVN_ORDER_GRAY on a colour source, and sizes whose byte counts (B frame_stride, the output, one map plane) leave 31 bits.
+ * ------------------------------------------------------------------------------------------- */
+#define WVN_SRC_MONO8 0
+#define WVN_SRC_RGB8 1
+#define WVN_SRC_BGR8 2
+#define WVN_SRC_PLANAR 3
+#define WVN_SRC_BAYER_RGGB8 4
+#define WVN_SRC_BAYER_BGGR8 5
+#define WVN_SRC_BAYER_GBRG8 6
+#define WVN_SRC_BAYER_GRBG8 7
+#define WVN_ORDER_RGB 0
+#define WVN_ORDER_BGR 1
+#define WVN_ORDER_GRAY 2
+#define WVN_FRAME_MAX_DIM 65535
+int wvn_unpack_frames(const void* src, int kind, int B, int H, int W, long long step, long long frame_stride, void* out_u8, int order,
+                      void* stream);
+int wvn_rectify_frames(const void* src, int kind, int B, int H, int W, long long step, long long frame_stride, const int* map_qx,
+                       const int* map_qy, int h, int w, void* out_u8, int order, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

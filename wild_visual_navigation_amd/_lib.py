@@ -127,6 +127,10 @@ JPEG_STATUS = ("OK", "TRUNCATED", "BAD_MARKER", "BAD_TABLE", "BAD_HUFFMAN", "BAD
 JPEG_SAMPLING = ("gray", "4:4:4", "4:2:2", "4:2:0")
 JPEG_MAX_THREADS = 16
 JPEG_MAX_BATCH = 4096
+# include/wvn_hip.h: WVN_SRC_* source kinds and WVN_ORDER_* output orders of the raw camera ingest (the names are ROS's encodings)
+SRC_KINDS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "planar": 3, "bayer_rggb8": 4, "bayer_bggr8": 5, "bayer_gbrg8": 6, "bayer_grbg8": 7}
+ORDER_RGB, ORDER_BGR, ORDER_GRAY = 0, 1, 2
+FRAME_MAX_DIM = 65535
 METRIC_MAX_T, METRIC_STATE_TAIL = 8192, 8
 METRIC_DENSE, METRIC_PER_SEGMENT = 0, 1
 METRIC_U8, METRIC_I32, METRIC_F32 = 0, 1, 2
@@ -320,6 +324,8 @@ _SIGNATURES = {
     "wvn_jpeg_coefficients_batch": ([_p, _p, _i, _p, _p, _sz, _p, _i, _p], _i),
     "wvn_jpeg_device_stage": ([_p, _i, _p, _p, _i, _p], _i),
     "wvn_jpeg_decode_batch": ([_p, _p, _i, _p, _p, _i, _p, _i, _p, _p], _i),
+    "wvn_unpack_frames": ([_p, _i, _i, _i, _i, _ll, _ll, _p, _i, _p], _i),
+    "wvn_rectify_frames": ([_p, _i, _i, _i, _i, _ll, _ll, _p, _p, _i, _i, _p, _i, _p], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -22,7 +22,7 @@ SOURCES = [
     "attention_x3.hip", "attention_f32.hip",
     "segments.hip", "stego.hip", "stego_linear.hip", "mlp.hip", "mlp_train.hip", "double_mlp.hip", "pixel_mlp.hip", "rnvp.hip", "rnvp_train.hip", "segment_predict.hip", "simple_gcn.hip", "simple_gcn_train.hip", "supervision.hip", "slic.hip", "slic_connectivity.hip", "wire.hip", "random_pixels.hip", "dense_sift.hip",
     "dense_crf.hip", "dense_crf_permutohedral.hip", "overlay.hip", "draw.hip", "resnet.hip", "pyramid_pool.hip", "metrics.hip",
-    "jpeg.hip",
+    "jpeg.hip", "rectify.hip",
 ]
 # plain C++ without device code (the host stage of the JPEG ingest: parser + Huffman decoder), compiled by the same driver as C++
 HOST_SOURCES = ["jpeg_host.cpp"]

@@ -114,12 +114,28 @@ class FeatureExtractor:
         if self._extractor is not None:
             self._extractor.change_device(device)
 
-    def decode(self, frames, **kwargs) -> torch.Tensor:
+    def decode(self, frames, rectify=None, **kwargs) -> torch.Tensor:
         """Compressed camera frames (JPEG bytes, or a list of them, all of one size and sampling) -> uint8 [B,3,H,W] on the
         extractor's device: ops.jpeg_decode with strict=True.  ``fe.predict_and_extract(fe.decode(msgs), model, cg)`` is the whole
-        image callback of a node that subscribes to a .../compressed topic."""
+        image callback of a node that subscribes to a .../compressed topic.  ``rectify``: a RectifyMap (ops.rectify_map) -- the
+        decoded frames are undistorted, [B,3,h,w] at the map's output size."""
         kwargs.setdefault("strict", True)
-        return ops.jpeg_decode(frames, self._device, **kwargs)[0]
+        rgb = ops.jpeg_decode(frames, self._device, **kwargs)[0]
+        return rgb if rectify is None else ops.rectify(rgb, rectify, "planar")
+
+    def decode_raw(self, frames, encoding: str, height: int, width: int, step=None, rectify=None) -> torch.Tensor:
+        """Raw camera frames of ONE camera (``msg.data`` of sensor_msgs/Image messages, or a list of them; ``encoding``, ``height``,
+        ``width``, ``step`` are the messages' fields) -> uint8 [B,3,H,W] RGB on the extractor's device: one upload, one launch
+        (mono8, rgb8, bgr8, bayer_*8; utils.image_to_torch is the single-message form).  ``rectify``: a RectifyMap -- [B,3,h,w],
+        demosaiced and undistorted in that launch.  ``fe.predict_and_extract(fe.decode_raw(msgs, "bayer_gbrg8", 1080, 1440,
+        rectify=m), model, cg)`` is the whole image callback for the camera driver's own topic."""
+        from ..utils.image_io import check_raw_geometry
+
+        step = check_raw_geometry(encoding, height, width, step, rectify, "decode_raw")
+        raw = ops.upload_raw_frames(frames, height * step, self._device, "decode_raw").view(-1, height, step)
+        if rectify is None:
+            return ops.unpack_frames(raw, encoding, step=step, width=width, channels=3)
+        return ops.rectify(raw, rectify, encoding, step=step, width=width, channels=3)
 
     # ------------------------------------------------------------------------------------------ extract
     @torch.no_grad()

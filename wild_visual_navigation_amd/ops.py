@@ -1637,3 +1637,265 @@ def jpeg_decode(frames, device, *, gray: bool = False, threads: int = 8, strict:
             if rc != _lib.JPEG_OK:
                 raise _lib.WvnError(f"jpeg_decode: frame {i}: {jpeg_status_name(rc)}")
     return out, st
+
+
+# ---- Raw camera ingest (include/wvn_hip.h: "Raw camera ingest"; csrc/rectify.hip; the definition: tests/rectify_ref.py) ----
+DISTORTION_MODELS = ("plumb_bob", "equidistant")
+_RECTIFY_Q = 32   # Q5, OpenCV's INTER_BITS
+
+
+class RectifyMap:
+    """The rectification of one camera geometry: ``qx``, ``qy`` int32 [h,w] on the device (Q5 source coordinates of every output
+    pixel), ``src_size`` (H, W), ``out_size`` (h, w) and ``K_new`` (3 x 3 float64 numpy), the pinhole matrix of the RECTIFIED frames:
+    the one ImageProjector must be given, not the sensor's K.  ``K_tensor`` is K_new as ros_cam_info_to_tensors shapes it."""
+
+    def __init__(self, qx: torch.Tensor, qy: torch.Tensor, src_size, out_size, K_new):
+        self.qx, self.qy, self.src_size, self.out_size, self.K_new = qx, qy, tuple(src_size), tuple(out_size), K_new
+
+    @property
+    def K_tensor(self) -> torch.Tensor:
+        """[1,4,4] fp32 on the map's device (ros_converter.py:86-92)."""
+        K = torch.eye(4, dtype=torch.float32)
+        K[:3, :3] = torch.from_numpy(self.K_new).to(torch.float32)
+        return K.unsqueeze(0).to(self.qx.device)
+
+
+_RECTIFY_CACHE = {}
+
+
+def _rectify_map_host(K, D, model: str, src_size, out_size, new_K, Rm):
+    """The map in float64 numpy, operation by operation as tests/rectify_ref.py states it -> (qx, qy) int32 [h,w]."""
+    import numpy as np
+
+    (H, W), (h, w) = src_size, out_size
+    u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+    with np.errstate(all="ignore"):
+        M = Rm.T @ np.linalg.inv(new_K)
+        X, Y, Z = (M[i, 0] * u + M[i, 1] * v + M[i, 2] for i in range(3))
+        x, y = X / Z, Y / Z
+        if model == "plumb_bob":
+            k1, k2, p1, p2, k3 = D
+            r2 = x * x + y * y
+            rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
+            xd = x * rad + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+            yd = y * rad + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        else:
+            k1, k2, k3, k4 = D
+            r = np.sqrt(x * x + y * y)
+            t = np.arctan(r)
+            t2 = t * t
+            td = t * (1 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+            s = np.where(r == 0, 1.0, td / np.where(r == 0, 1.0, r))
+            xd, yd = x * s, y * s
+        sx = K[0, 0] * xd + K[0, 2]
+        sy = K[1, 1] * yd + K[1, 2]
+        # bounded, so that the stored integers are: anything at or beyond -2 / W + 1 has all four taps outside anyway
+        sx = np.clip(np.where(np.isfinite(sx), sx, -2.0), -2, W + 1)
+        sy = np.clip(np.where(np.isfinite(sy), sy, -2.0), -2, H + 1)
+    return np.rint(_RECTIFY_Q * sx).astype(np.int32), np.rint(_RECTIFY_Q * sy).astype(np.int32)
+
+
+def _size2(size, what: str):
+    try:
+        a, b = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise _lib.WvnError(f"rectify_map: {what} must be (height, width), got {size!r}") from None
+    if not (1 <= a <= _lib.FRAME_MAX_DIM and 1 <= b <= _lib.FRAME_MAX_DIM):
+        raise _lib.WvnError(f"rectify_map: {what}={(a, b)}: each side must lie in [1, {_lib.FRAME_MAX_DIM}]")
+    return a, b
+
+
+def _mat3(M, what: str):
+    import numpy as np
+
+    try:
+        a = np.array(M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else M, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise _lib.WvnError(f"rectify_map: {what} must hold 9 numbers") from None
+    if a.size != 9 or not np.isfinite(a).all():
+        raise _lib.WvnError(f"rectify_map: {what} must hold 9 finite numbers, got shape {a.shape}")
+    return a.reshape(3, 3)
+
+
+def rectify_map(K, D, model: str, src_size, out_size=None, new_K=None, R=None, device="cuda") -> RectifyMap:
+    """The rectification map of one camera: sensor matrix ``K`` (3 x 3), distortion ``D`` of ``model`` "plumb_bob" (k1, k2, p1, p2[,
+    k3]) or "equidistant" (k1..k4, the fisheye model), source size (H, W) -> RectifyMap for output size ``out_size`` (default: the
+    source's) under the pinhole matrix ``new_K`` (default: K scaled to the output size by the width and height ratios, image_proc's
+    P = K) and the rectifying rotation ``R`` (default identity).  Computed once per geometry on the host in float64 and cached."""
+    import numpy as np
+
+    if model not in DISTORTION_MODELS:
+        raise _lib.WvnError(f"rectify_map: distortion model {model!r} is not supported; the models are {', '.join(DISTORTION_MODELS)}")
+    try:
+        Dv = [float(d) for d in D]
+    except (TypeError, ValueError):
+        raise _lib.WvnError("rectify_map: D must be a sequence of numbers") from None
+    if model == "plumb_bob" and len(Dv) == 4:
+        Dv.append(0.0)
+    want = 5 if model == "plumb_bob" else 4
+    if len(Dv) != want or not all(np.isfinite(Dv)):
+        raise _lib.WvnError(f"rectify_map: {model} takes {'4 or 5' if want == 5 else '4'} finite coefficients, got {len(list(D))}")
+    src = _size2(src_size, "src_size")
+    out = src if out_size is None else _size2(out_size, "out_size")
+    Km = _mat3(K, "K")
+    Kn = np.diag([out[1] / src[1], out[0] / src[0], 1.0]) @ Km if new_K is None else _mat3(new_K, "new_K")
+    Rm = np.eye(3) if R is None else _mat3(R, "R")
+    if abs(np.linalg.det(Kn)) < 1e-300:
+        raise _lib.WvnError("rectify_map: new_K is singular")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.WvnError(f"rectify_map: device must be a GPU (got {device}); the HIP path has no CPU fallback")
+    key = (Km.tobytes(), tuple(Dv), model, src, out, Kn.tobytes(), Rm.tobytes(), str(device))
+    m = _RECTIFY_CACHE.get(key)
+    if m is None:
+        qx, qy = _rectify_map_host(Km, Dv, model, src, out, Kn, Rm)
+        m = RectifyMap(torch.from_numpy(qx).to(device), torch.from_numpy(qy).to(device), src, out, Kn)
+        _RECTIFY_CACHE[key] = m
+    return m
+
+
+def rectify_map_from_camera_info(height, width, distortion_model, D, K, R, P, out_size=None, device="cuda") -> RectifyMap:
+    """rectify_map from the fields of a sensor_msgs/CameraInfo, as plain sequences: K_new is the left 3 x 3 of ``P`` (scaled by the
+    width and height ratios when ``out_size`` differs from (height, width); K itself where P is all zero, an uncalibrated message).  An
+    empty model name or an all-zero (or empty) D is the identity distortion; any other model than plumb_bob / equidistant is refused."""
+    import numpy as np
+
+    Dv = [float(d) for d in D]
+    model = distortion_model
+    if model == "" or not any(Dv):
+        if model not in ("",) + DISTORTION_MODELS:
+            raise _lib.WvnError(f"rectify_map: distortion model {model!r} is not supported; the models are {', '.join(DISTORTION_MODELS)}")
+        model, Dv = "plumb_bob", [0.0] * 5
+    Pm = np.array(P, dtype=np.float64)
+    if Pm.size != 12:
+        raise _lib.WvnError(f"rectify_map: P must hold 12 numbers, got {Pm.size}")
+    Kn = Pm.reshape(3, 4)[:, :3] if Pm.any() else _mat3(K, "K")
+    src = _size2((height, width), "(height, width)")
+    out = src if out_size is None else _size2(out_size, "out_size")
+    Kn = np.diag([out[1] / src[1], out[0] / src[0], 1.0]) @ Kn
+    return rectify_map(K, Dv, model, src, out, Kn, R if len(R) else None, device)
+
+
+def _bytes_per_pixel(encoding: str) -> int:
+    return 3 if encoding in ("rgb8", "bgr8") else 1
+
+
+def _frame_source(frames: torch.Tensor, encoding: str, step, width, channels, who: str):
+    """-> (contiguous uint8 tensor, kind, B, H, W, step, frame_stride); refusals raise before the device is looked at."""
+    if encoding not in _lib.SRC_KINDS:
+        raise _lib.WvnError(f"{who}: encoding {encoding!r} is not supported; the source kinds are {', '.join(_lib.SRC_KINDS)}")
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise _lib.WvnError(f"{who}: a uint8 tensor expected, got {getattr(frames, 'dtype', type(frames).__name__)}")
+    bpp = _bytes_per_pixel(encoding)
+    packed, planar = bpp == 3, encoding == "planar"
+    if step is not None:
+        # rows of `step` bytes as the message carries them: [B,H,step] or [H,step], the width given apart
+        if planar:
+            raise _lib.WvnError(f"{who}: step applies to the camera encodings, not to planar frames")
+        if width is None:
+            raise _lib.WvnError(f"{who}: step needs width (the rows are [.., H, step] bytes)")
+        if frames.dim() == 2:
+            frames = frames[None]
+        if frames.dim() != 3:
+            raise _lib.WvnError(f"{who}: with step, frames are [B,H,step] or [H,step] bytes, got {tuple(frames.shape)}")
+        B, H, got = frames.shape
+        W, step = int(width), int(step)
+        if got != step:
+            raise _lib.WvnError(f"{who}: rows of {got} bytes, but step={step}")
+        if W < 1 or step < W * bpp:
+            raise _lib.WvnError(f"{who}: step={step} is smaller than a row of {W} pixels ({W * bpp} bytes)")
+    else:
+        nd = 3 + int(packed or planar)
+        if frames.dim() == nd - 1:
+            frames = frames[None]
+        if frames.dim() != nd or (packed and frames.shape[3] != 3) or (planar and frames.shape[1] != 3):
+            shape = "[B,H,W,3]" if packed else "[B,3,H,W]" if planar else "[B,H,W]"
+            raise _lib.WvnError(f"{who}: {encoding} frames are {shape} (or one frame without B), got {tuple(frames.shape)}")
+        B, H, W = (frames.shape[0], frames.shape[2], frames.shape[3]) if planar else frames.shape[:3]
+        step = W * bpp
+    least = 3 if encoding.startswith("bayer") else 1
+    if B < 1 or H < least or W < least:
+        raise _lib.WvnError(f"{who}: {encoding} frames need B >= 1 and H, W >= {least}, got B={B}, {H} x {W}")
+    _out_order(encoding, False, channels, who)
+    require_cuda(frames, "frames")
+    return frames.contiguous(), _lib.SRC_KINDS[encoding], B, H, W, step, (3 if planar else 1) * H * step
+
+
+def _out_order(encoding: str, bgr: bool, channels, who: str):
+    if channels not in (None, 1, 3) or (channels == 1 and encoding != "mono8"):
+        raise _lib.WvnError(f"{who}: channels={channels!r}: None or 3, or 1 for mono8")
+    if encoding == "mono8" and channels != 3:
+        return 1, _lib.ORDER_GRAY
+    return 3, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB
+
+
+def unpack_frames(frames: torch.Tensor, encoding: str, *, step=None, width=None, bgr: bool = False, channels=None) -> torch.Tensor:
+    """Camera frames -> planar uint8 [B,C,H,W] at full resolution in one launch: the bilinear demosaic of the four 8-bit Bayer
+    encodings, the HWC -> planar unpack of rgb8 / bgr8, mono8 (C = 1; ``channels=3`` replicates the plane), "planar" (a copy, or the
+    R <-> B exchange).  ``frames``: uint8 on the GPU, [B,H,W] (mono8, bayer_*8), [B,H,W,3] (rgb8, bgr8) or [B,3,H,W] (planar), B
+    optional; or, with ``step`` and ``width``, the padded rows of the message, [B,H,step].  C = 3 is R,G,B, or B,G,R with ``bgr``."""
+    src, kind, B, H, W, step, stride = _frame_source(frames, encoding, step, width, channels, "unpack_frames")
+    C_, order = _out_order(encoding, bgr, channels, "unpack_frames")
+    out = torch.empty(B, C_, H, W, dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        check(lib().wvn_unpack_frames(ptr(src), kind, B, H, W, step, stride, ptr(out), order, stream()), "wvn_unpack_frames")
+    return out
+
+
+def debayer(raw: torch.Tensor, pattern: str) -> torch.Tensor:
+    """uint8 [B,H,W] (or [H,W]) mosaics -> uint8 [B,3,H,W] RGB: unpack_frames for ``pattern`` "rggb", "bggr", "gbrg", "grbg" (or the
+    encoding's full name, "bayer_gbrg8")."""
+    enc = pattern if pattern.startswith("bayer_") else f"bayer_{pattern}8"
+    if not enc.startswith("bayer_") or enc not in _lib.SRC_KINDS:
+        raise _lib.WvnError(f"debayer: pattern {pattern!r} is not one of rggb, bggr, gbrg, grbg")
+    return unpack_frames(raw, enc)
+
+
+# ops.rectify on a mosaic: "fused" demosaics at the taps in the one launch; "two_step" is unpack_frames + a planar rectify.  The fused
+# kernel is the faster one at every measured shape (profiles/rectify.md: 1.7 - 1.9x at full resolution, 2.1 - 3.1x at the 448 x 448 crop), so it is
+# the default at every output size; "two_step" stays selectable for the comparison.
+RECTIFY_MOSAIC_ROUTES = ("fused", "two_step")
+
+
+def rectify(frames: torch.Tensor, rmap: RectifyMap, encoding: str = "planar", *, step=None, width=None, bgr: bool = False,
+            channels=None, route=None) -> torch.Tensor:
+    """Camera frames of any kind unpack_frames takes (default: planar [B,3,H,W], what jpeg_decode returns) -> rectified planar uint8
+    [B,C,h,w] through ``rmap``: bilinear with 5-bit weights, taps outside the frame are 0.  For a mosaic the demosaic happens at the
+    taps of the same launch and no full-resolution RGB frame is written (``route="two_step"`` forces debayer + rectify, the same
+    bytes; None is "fused", the faster one at every measured output size: profiles/rectify.md)."""
+    if not isinstance(rmap, RectifyMap):
+        raise _lib.WvnError(f"rectify: rmap must be a RectifyMap (ops.rectify_map), got {type(rmap).__name__}")
+    if route not in (None,) + RECTIFY_MOSAIC_ROUTES:
+        raise _lib.WvnError(f"rectify: route={route!r}: None or one of {RECTIFY_MOSAIC_ROUTES}")
+    as_given = {"step": step, "width": width}
+    src, kind, B, H, W, step, stride = _frame_source(frames, encoding, step, width, channels, "rectify")
+    C_, order = _out_order(encoding, bgr, channels, "rectify")
+    if (H, W) != rmap.src_size:
+        raise _lib.WvnError(f"rectify: the map is for {rmap.src_size[0]} x {rmap.src_size[1]} frames, these are {H} x {W}")
+    if rmap.qx.device != src.device:
+        raise _lib.WvnError(f"rectify: the map lives on {rmap.qx.device}, the frames on {src.device}")
+    h, w = rmap.out_size
+    if encoding.startswith("bayer") and route == "two_step":
+        return rectify(unpack_frames(src, encoding, **as_given), rmap, "planar", bgr=bgr)
+    out = torch.empty(B, C_, h, w, dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        check(lib().wvn_rectify_frames(ptr(src), kind, B, H, W, step, stride, ptr(rmap.qx), ptr(rmap.qy), h, w, ptr(out), order,
+                                       stream()), "wvn_rectify_frames")
+    return out
+
+
+def upload_raw_frames(frames, nbytes: int, device, who: str = "upload_raw_frames") -> torch.Tensor:
+    """The ``data`` of raw camera messages of one size (bytes, bytearray, a 1-d uint8 CPU tensor, or a list of those) -> uint8
+    [B,nbytes] on ``device`` in ONE upload; a message shorter than ``nbytes`` raises."""
+    bufs = _jpeg_buffers(frames, who)
+    for i, a in enumerate(bufs):
+        if a.size < nbytes:
+            raise _lib.WvnError(f"{who}: frame {i} holds {a.size} bytes; height * step = {nbytes}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.WvnError(f"{who}: device must be a GPU (got {device}); the HIP path has no CPU fallback")
+    host = torch.empty(len(bufs), nbytes, dtype=torch.uint8)
+    view = host.numpy()
+    for i, a in enumerate(bufs):
+        view[i] = a[:nbytes]
+    return host.to(device)
