@@ -762,7 +762,9 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
 //   * a period = one slice = four regions of 2 fp16 MFMAs (k-steps 2 r, 2 r + 1) + 1 scaled MFMA (64-k step mm = r >> 1; r even: W_l8 x
 //     a_h8, r odd: W_h8 x a_l8) = 128 matrix-pipe cycles; region r + 1's four fragment reads are requested before region r's MFMAs (two
 //     register sets);
-//   * no second accumulator set: the tile's epilogue (16 values per lane) runs serially behind its third period;
+//   * no second accumulator set: the tile's epilogue (16 values per lane) runs serially behind its third period, and stores from the registers (q | k after
+//     one exchange between the half-waves, v^T as it stands): the first build took every q | k | v^T tile through a wave-private LDS image and formed q's
+//     rounding residue for k tiles and one-plane q tiles as well -- 0.85 -> 0.82 ms (two-plane q), 0.81 -> 0.755 ms (one plane) per 128 frame-passes;
 //   * resident: 24 fp16 fragments + 6 l8 operands (144 registers) + 16 accumulators + 2 x 16 of W fragments + a_h8 (8).
 constexpr int S2_BN = 32;                    // columns per tile
 constexpr int S2_NSL = 3;                    // slices (of 128 k) per column tile
@@ -770,7 +772,6 @@ constexpr int S2_NS = 3;
 constexpr int S2_SLICE = 16384;
 constexpr int S2_RING = S2_NS * S2_SLICE;    // 48 KB
 constexpr int S2_PIECES = S2_SLICE / 1024 / 4;   // 4 per wave and slice: one per region
-constexpr int S2_STG = 5120;                 // per wave (QKV): two fp16 images of a tile [32][80 B] (q | k: the plane and its residue), or one V^T tile [32 n][80 B]
 static_assert(S2_PIECES == 4, "one DMA piece per region");
 
 template <int EPI, bool TIMING = false>
@@ -787,9 +788,7 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
   const long long U = (long long)NRB * NT;
   const int u_begin = (int)(U * blockIdx.x / gridDim.x), u_end = (int)(U * (blockIdx.x + 1) / gridDim.x);
   const int total = (u_end - u_begin) * S2_NSL;
-  constexpr int STG_OFF2 = S2_RING;
-  constexpr int BIAS_OFF2 = STG_OFF2 + (IS_QKV ? 4 * S2_STG : 0);
-  unsigned char* stg = smem + STG_OFF2 + wave * S2_STG;
+  constexpr int BIAS_OFF2 = S2_RING;   // (no staging area: every epilogue stores from registers)
   const float* bias_l = (const float*)(smem + BIAS_OFF2);
   const float* gam_l = (const float*)(smem + BIAS_OFF2 + p.N * 4);
   int m0w = 0;
@@ -879,25 +878,31 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
   // ---- epilogue addressing ----
   constexpr unsigned OOB = 0x80000000u;
   const int nqk = IS_QKV ? 4 * p.heads : (1 << 30);      // QKV: the 32-column tiles below nqk are q | k (half a head each), the rest v^T
-  unsigned voff[2] = {0, 0};
-  unsigned vt_off = 0;
+  unsigned qk_off = 0;           // q | k: the lane's own token row m0w + l31, plus the half-wave's 16 bytes of every 32
+  const unsigned vt_lane = IS_QKV ? (unsigned)(l31 * p.npad + 8 * hi) * 2u : 0u;   // v^T: the lane's own row l31 of the tile and its 8 tokens of every 16;
+  unsigned vt_so[2] = {0, 0};                                                      // the token groups m0w and m0w + 16 themselves are wave-uniform: scalar
+  bool vt_in[2] = {false, false};                                                  // offsets, and a group at or past M is skipped
   const unsigned c_bytes = IS_QKV ? 0u : (unsigned)((size_t)((p.M + 31) / 32 * 32) * p.ldc * 2);
   const __amdgpu_buffer_rsrc_t rs_c = IS_QKV ? __builtin_amdgcn_make_buffer_rsrc(p.qkv_base, 0, p.qkv_bytes, 0x00020000)
                                              : __builtin_amdgcn_make_buffer_rsrc(p.C, 0, c_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_c2 = IS_QKV ? __builtin_amdgcn_make_buffer_rsrc(p.qkv_base_lo ? p.qkv_base_lo : p.qkv_base, 0, p.qkv_bytes, 0x00020000)
                                               : __builtin_amdgcn_make_buffer_rsrc(p.C_lo ? p.C_lo : p.C, 0, c_bytes / 2, 0x00020000);
   auto qkv_offsets = [&]() __attribute__((always_inline)) {
-    // q | k tile images: a row = 32 columns = 64 B = four lanes; a store instruction covers 16 rows
+    // per row block: the wave's 32 rows start at token r0 of frame b0 -- ONE division, of wave-uniform values; M % 16 == ntok_s % 16 == 0 and m0w % 32 == 0
+    const int b0 = __builtin_amdgcn_readfirstlane(m0w / p.ntok_s), r0 = m0w - b0 * p.ntok_s;
+    {   // q | k: the lane's row l31; 32 rows cross at most two frame boundaries (ntok_s >= 16).  Rows at or past M: an offset outside the descriptor, dropped
+      int b = b0, tk = r0 + l31;
 #pragma unroll
-    for (int hblk = 0; hblk < 2; ++hblk) {
-      const int m = m0w + hblk * 16 + (lane >> 2);
-      const int b = m / p.ntok_s, tk = m - b * p.ntok_s;
-      voff[hblk] = m < p.M ? (unsigned)((((size_t)b * p.heads * p.npad + tk) * 64 + (lane & 3) * 8) * 2) : OOB;
+      for (int i = 0; i < 2; ++i)
+        if (tk >= p.ntok_s) { tk -= p.ntok_s; ++b; }
+      qk_off = m0w + l31 < p.M ? ((unsigned)(b * p.heads * p.npad + tk) * 128u + hi * 16) : OOB;
     }
-    {
-      const int m = m0w + (lane & 3) * 8;
-      const int b = m / p.ntok_s, tk = m - b * p.ntok_s;
-      vt_off = m < p.M ? (unsigned)((((size_t)b * p.heads * 64 + (lane >> 2)) * p.npad + tk) * 2) : OOB;
+#pragma unroll
+    for (int gg = 0; gg < 2; ++gg) {   // v^T: a group of 16 tokens never straddles a frame or M, so its frame and token are wave-uniform
+      const bool wrap = r0 + 16 * gg >= p.ntok_s;
+      const int b = b0 + wrap, tk = r0 + 16 * gg - (wrap ? p.ntok_s : 0);
+      vt_so[gg] = __builtin_amdgcn_readfirstlane((unsigned)(b * p.heads * 64 * p.npad + tk) * 2u);
+      vt_in[gg] = m0w + 16 * gg < p.M;
     }
   };
 
@@ -992,52 +997,56 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
       const unsigned so8 = __builtin_amdgcn_readfirstlane((((m0w >> 5) * (p.N >> 6)) + jp) * 2048 + t * 1024);
       wvn_store_b128_guarded(frag8l, rs_c2, l16, so8);
     } else if constexpr (TR) {
-      // a q | k tile = half a head's dims of 32 tokens: an fp16 image [32 tokens][32 dims] (rows of 80 B) and the image of the rounding residues behind it; q
-      // pre-scaled.  Then 16 bytes per lane: 4 lanes per token row, 16 rows per store
+      // a q | k tile = half a head's dims (64 B) of 32 tokens.  Lane (token row l31, half hi) holds dims 8 g + 4 hi + e, that is words 4 g + 2 hi + {0, 1} of
+      // its row.  One exchange between the half-waves (v_permlane32_swap: the g-odd words of the lower half against the g-even words of the upper one) leaves
+      // every lane with bytes [16 hi, +16) and [32 + 16 hi, +16) of its own row: two 16-byte stores per plane, no LDS.  q is pre-scaled; its rounding residue
+      // (the second plane) is formed only where it is stored, and k is not multiplied at all: three bodies behind wave-uniform branches (the epilogue is serial)
       const int D = p.heads * 64;
       const int which = n0 / D, head = (n0 - which * D) >> 6, t = (n0 >> 5) & 1;
-      const float qs = which == 0 ? p.q_scale : 1.f;
-      const bool keep_lo = which == 0 && p.q_lo_f16;
       const unsigned so = __builtin_amdgcn_readfirstlane((which == 0 ? p.q_off : p.k_off) + head * p.npad * 64 * 2 + t * 64);
+      auto put = [&](uint32_t (&w)[8], auto lo_tag) __attribute__((always_inline)) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int h2 = 0; h2 < 4; h2 += 2) {
-          uint32_t h, l;
-          wvn_split2_f16(acc[4 * g + h2] * qs, acc[4 * g + h2 + 1] * qs, h, l);
-          const int c = 8 * g + 4 * hi + h2;
-          *(uint32_t*)(stg + l31 * 80 + c * 2) = h;
-          *(uint32_t*)(stg + 2560 + l31 * 80 + c * 2) = l;
-          __builtin_amdgcn_sched_barrier(0);
+        for (int pr = 0; pr < 2; ++pr) {
+          const auto r0 = __builtin_amdgcn_permlane32_swap(w[4 * pr], w[4 * pr + 2], false, false);
+          const auto r1 = __builtin_amdgcn_permlane32_swap(w[4 * pr + 1], w[4 * pr + 3], false, false);
+          const u32x4_t val = {r0[0], r1[0], r0[1], r1[1]};
+          if constexpr (decltype(lo_tag)::value) wvn_store_b128_guarded(val, rs_c2, qk_off, so + pr * 32);
+          else wvn_store_b128_guarded(val, rs_c, qk_off, so + pr * 32);
         }
+      };
+      auto body = [&](auto scale_tag, auto lo_tag, float qs) __attribute__((always_inline)) {
+        constexpr bool SCALE = decltype(scale_tag)::value, LO = decltype(lo_tag)::value;
+        typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
+        uint32_t h[8];
+        [[maybe_unused]] uint32_t l[8];
 #pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const u32x4_t val = *(const u32x4_t*)(stg + ((lane >> 2) + it * 16) * 80 + (lane & 3) * 16);
-        wvn_store_b128_guarded(val, rs_c, voff[it], so);
-      }
-      if (keep_lo) {
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-          const u32x4_t val = *(const u32x4_t*)(stg + 2560 + ((lane >> 2) + it * 16) * 80 + (lane & 3) * 16);
-          wvn_store_b128_guarded(val, rs_c2, voff[it], so);
+        for (int w = 0; w < 8; ++w) {   // word w = 2 g + (h2 >> 1) of the lane: accumulators 2 w, 2 w + 1
+          const float a = acc[2 * w], b = acc[2 * w + 1];
+          h[w] = SCALE ? pack_f16x2(a * qs, b * qs) : pack_f16x2(a, b);
+          if constexpr (LO) {   // what the rounding of the plane left of the UNROUNDED product (one fma: the form this residue has always had)
+            const h2_t hh = __builtin_bit_cast(h2_t, h[w]);
+            l[w] = pack_f16x2(__builtin_fmaf(a, qs, -(float)hh[0]), __builtin_fmaf(b, qs, -(float)hh[1]));
+          }
         }
-      }
+        put(h, std::false_type{});
+        if constexpr (LO) put(l, std::true_type{});
+      };
+      using T = std::true_type; using F = std::false_type;
+      if (which != 0) body(F{}, F{}, 1.f);
+      else if (p.q_lo_f16) body(T{}, T{}, p.q_scale);
+      else body(T{}, F{}, p.q_scale);
     } else {
-      // V^T: lane (row n = l31 of the tile, half hi) holds tokens 8 g + 4 hi + e; image [32 n][32 tokens] with bits 2 and 3 of the token index swapped inside
-      // aligned groups of 16 (the attention kernel's V^T fragment order), rows of 80 B; 4 lanes per row, 16 rows per store
+      // V^T: lane (row n = l31 of the tile, half hi) holds tokens 8 g + 4 hi + e.  The attention kernel's V^T fragment order swaps bits 2 and 3 of the token
+      // index inside aligned groups of 16, so token 8 g + 4 hi + e sits at 16 (g >> 1) + 8 hi + 4 (g & 1) + e of the row: accumulators 8 gg .. 8 gg + 7 ARE the
+      // eight tokens at 16 gg + 8 hi, in order -- one 16-byte store per group of 16 tokens, straight from the registers
       const int nv = n0 - 2 * p.heads * 64;     // row of V^T = head * 64 + dim
+      const unsigned so = __builtin_amdgcn_readfirstlane(p.v_off + nv * p.npad * 2);
 #pragma unroll
-      for (int g = 0; g < 4; ++g)
+      for (int gg = 0; gg < 2; ++gg) {
+        u32x4_t val;
 #pragma unroll
-        for (int h2 = 0; h2 < 4; h2 += 2) {
-          const int mloc = 16 * (g >> 1) + 8 * hi + 4 * (g & 1) + h2;
-          *(uint32_t*)(stg + l31 * 80 + mloc * 2) = pack_f16x2(acc[4 * g + h2], acc[4 * g + h2 + 1]);
-        }
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const u32x4_t val = *(const u32x4_t*)(stg + ((lane >> 2) + it * 16) * 80 + (lane & 3) * 16);
-        const unsigned so = __builtin_amdgcn_readfirstlane(p.v_off + (nv + it * 16) * p.npad * 2);
-        wvn_store_b128_guarded(val, rs_c, vt_off, so);
+        for (int c = 0; c < 4; ++c) val[c] = pack_f16x2(acc[8 * gg + 2 * c], acc[8 * gg + 2 * c + 1]);
+        if (vt_in[gg]) wvn_store_b128_guarded(val, rs_c, vt_lane, so + vt_so[gg]);
       }
     }
   };
@@ -1161,7 +1170,7 @@ template <int EPI>
 int launch_mx2(X384Params p, hipStream_t st) {
   if (!p.ln_x || !p.ln_stats || !p.ln_g || !p.ln_b || (p.ln_ldx % 4) || ((uintptr_t)p.ln_x & 15) || ((uintptr_t)p.ln_stats & 7)) return WVN_ERR_ARG;
   p.W = (const bf16_t*)((const unsigned char*)p.W + (size_t)p.N * KD * 4);
-  const int lds = S2_RING + (EPI == X_QKV_F16 ? 4 * S2_STG : 0) + p.N * 4 + 2 * KD * 4;
+  const int lds = S2_RING + p.N * 4 + 2 * KD * 4;   // the ring, the bias, the LayerNorm gain and shift: 57 KB (fc1) / 55.5 KB (q | k | v^T)
   if (lds > 80 * 1024) return WVN_ERR_ARG;
   static LdsOptIn lds_opt_in;
   if (const int rc = lds_opt_in(80 * 1024, (const void*)gemm_a384_mx2_kernel<EPI>, (const void*)gemm_a384_mx2_kernel<EPI, true>)) return rc;
