@@ -1405,6 +1405,58 @@ int wvn_unpack_frames(const void* src, int kind, int B, int H, int W, long long 
 int wvn_rectify_frames(const void* src, int kind, int B, int H, int W, long long step, long long frame_stride, const int* map_qx,
                        const int* map_qy, int h, int w, void* out_u8, int order, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Traversability grid map: what the reference hands to elevation_mapping_cupy (the sem_wvn_*_traversability image subscribers with
+ * image_channel_fusions: exponential, anymal_sensor_parameter.yaml / anymal_parameters.yaml) and to smart_carrot.py.  Three launches,
+ * each on `stream`, without atomics, workspace or host synchronisation; tests/grid_map_ref.py states them in numpy and the results are
+ * that statement BIT FOR BIT (fp32, every operation rounded on its own, in the order csrc/grid_map.hip writes out).  Parity with
+ * elevation_mapping_cupy's own kernels and with cv2.circle's rasterisation is NOT pinned: neither package is available.
+ *
+ * Grid: square, N x N (N <= WVN_GRID_MAX_N), axis 0 = map x, axis 1 = map y, row-major fp32 layers, NaN = unknown; cell (i, j) is
+ * centred at (cx + (i - N/2) r, cy + (j - N/2) r)  (smart_carrot.py:145-150).
+ *
+ * wvn_grid_fuse_images: maps [B][C][H][W] fp32 (C <= 4, B <= WVN_GRID_MAX_CAMERAS), per camera the scaled 4 x 4 intrinsics and
+ * pose_cam_in_world (device, [B][4][4]); `layers`: a HOST array of C device pointers, the target layers, updated in place; `hits`
+ * int32 [N][N].  One thread owns a cell and applies the cameras in order b = 0 .. B-1: the cell (x, y, elevation) is projected
+ * (rigid inverse + pinhole), the camera is skipped unless the depth is > min_depth, the nearest pixel (floor(u + 0.5), floor(v + 0.5))
+ * lies inside the image and the horizontal distance to the camera is <= max_range (INFINITY: no limit); the ray to the camera is walked
+ * in steps of one resolution in the xy-plane and the cell is hidden when a cell under the ray is finite and higher than the ray by more
+ * than occlusion_margin; each channel whose sample is not NaN is fused, new = old is NaN ? value : old (1 - alpha) + alpha value, and
+ * hits counts the cameras that fused.  Cells with NaN elevation and cells no camera reaches are not written.
+ *
+ * wvn_grid_sdf: exact Euclidean signed distance field of the set {layer < threshold}; unknown cells (NaN) count as obstacle, free or
+ * neither (WVN_GRID_UNKNOWN_*).  d2 int32 [N][N]: squared distance in cells to the nearest cell of the other set, > 0 free, < 0
+ * obstacle, 0 for a cell in neither set, +-INT32_MAX where the other set is empty; sdf fp32 = +-(resolution * sqrtf(float(|d2|))), NaN
+ * for a cell in neither set, +-inf where the other set is empty.
+ *
+ * wvn_grid_carrot: smart_carrot.py:53-94, 126-150.  score = sdf (+ distance force if its factor > 0) (- centre force if its factor > 0);
+ * -inf outside the discs, where the 3 x 3 neighbourhood holds a NaN elevation, and where the score is NaN; arg-max, ties to the lowest
+ * row-major index.  `discs`: a HOST array of n_discs (distance, radius) pairs in cells (n_discs <= WVN_GRID_MAX_DISCS; the reference's
+ * are (30, 15), (55, 20), (90, 25) on its 200-cell map); disc d is (i - ci)^2 + (j - cj)^2 <= radius^2 with ci = int(N/2 + cos_yaw
+ * distance), cj = int(N/2 + sin_yaw distance), computed on the host in double; the kernel uses cos_yaw and sin_yaw rounded to fp32.
+ * Out (device): goal_cell int32 [3] = {i, j, found}, goal fp32 [3] = {score, x, y} with x = (i - N/2) r + cx; masked [N][N] (may be
+ * NULL): the masked score layer.
+ *
+ * WVN_ERR_ARG before any launch: a null pointer (masked excepted), N < 1 or above WVN_GRID_MAX_N, B, C, H, W, n_discs out of range, a
+ * resolution that is not positive and finite, alpha outside [0, 1], a NaN parameter, |cos_yaw| or |sin_yaw| > 1, a negative or
+ * oversized disc entry, an unknown `unknown` mode.
+ * ------------------------------------------------------------------------------------------- */
+#define WVN_GRID_MAX_N 4096
+#define WVN_GRID_MAX_CHANNELS 4
+#define WVN_GRID_MAX_CAMERAS 64
+#define WVN_GRID_MAX_DISCS 8
+#define WVN_GRID_MAX_DISC_DISTANCE 1048576
+#define WVN_GRID_UNKNOWN_OBSTACLE 0
+#define WVN_GRID_UNKNOWN_FREE 1
+#define WVN_GRID_UNKNOWN_NEITHER 2
+int wvn_grid_fuse_images(const float* maps, int B, int C, int H, int W, const float* intrinsics, const float* poses,
+                         const float* elevation, int N, float cx, float cy, float resolution, float* const* layers, int* hits,
+                         float alpha, float min_depth, float max_range, float occlusion_margin, void* stream);
+int wvn_grid_sdf(const float* layer, int N, float threshold, int unknown, float resolution, int* d2, float* sdf, void* stream);
+int wvn_grid_carrot(const float* sdf, const float* elevation, int N, double cos_yaw, double sin_yaw, float distance_force_factor,
+                    float center_force_factor, const int* discs, int n_discs, float cx, float cy, float resolution, int* goal_cell,
+                    float* goal, float* masked, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

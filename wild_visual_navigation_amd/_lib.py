@@ -138,6 +138,9 @@ OVERLAY_MAX_COLOURS, OVERLAY_MAX_MAPS = 1024, 4
 OVERLAY_VALUES, OVERLAY_LABELS, OVERLAY_SEGMENTS = 0, 1, 2
 DRAW_MAX_PRIMITIVES = 65536
 DRAW_LINE, DRAW_LINE2, DRAW_DISC = 0, 1, 2
+# include/wvn_hip.h: WVN_GRID_* limits and the `unknown` modes of wvn_grid_sdf
+GRID_MAX_N, GRID_MAX_CHANNELS, GRID_MAX_CAMERAS, GRID_MAX_DISCS = 4096, 4, 64, 8
+GRID_UNKNOWN = {"obstacle": 0, "free": 1, "neither": 2}
 MLP_KIND_DOUBLE = 1   # include/wvn_hip.h: WVN_MLP_KIND_DOUBLE (MlpDesc.reserved)
 
 
@@ -326,6 +329,9 @@ _SIGNATURES = {
     "wvn_jpeg_decode_batch": ([_p, _p, _i, _p, _p, _i, _p, _i, _p, _p], _i),
     "wvn_unpack_frames": ([_p, _i, _i, _i, _i, _ll, _ll, _p, _i, _p], _i),
     "wvn_rectify_frames": ([_p, _i, _i, _i, _i, _ll, _ll, _p, _p, _i, _i, _p, _i, _p], _i),
+    "wvn_grid_fuse_images": ([_p, _i, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _p, _p, _f, _f, _f, _f, _p], _i),
+    "wvn_grid_sdf": ([_p, _i, _f, _i, _f, _p, _p, _p], _i),
+    "wvn_grid_carrot": ([_p, _p, _i, C.c_double, C.c_double, _f, _f, _p, _i, _f, _f, _f, _p, _p, _p, _p], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

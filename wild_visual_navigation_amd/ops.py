@@ -1,6 +1,7 @@
 """Functional wrappers (torch tensors in / out) around the C-ABI kernels of libwvn_hip.so.
 Allocation and stream selection happen here; arithmetic happens in HIP.  No fallbacks."""
 import ctypes as C
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -1899,3 +1900,90 @@ def upload_raw_frames(frames, nbytes: int, device, who: str = "upload_raw_frames
     for i, a in enumerate(bufs):
         view[i] = a[:nbytes]
     return host.to(device)
+
+
+# ------------------------------------------------------------------------------------------------------------- traversability grid map
+GRID_DEFAULT_DISCS = ((30, 15), (55, 20), (90, 25))   # smart_carrot.py:74-85: (distance, radius = thickness / 2) in cells of its 200-cell map
+
+
+def _grid_layer(t: torch.Tensor, name: str, who: str, dtype=torch.float32, N=None) -> int:
+    require_cuda(t, name)
+    if t.dtype != dtype or t.dim() != 2 or t.shape[0] != t.shape[1] or not t.is_contiguous() or (N is not None and t.shape[0] != N):
+        raise _lib.WvnError(f"{who}: {name} must be a contiguous {dtype} [N,N] layer" + (f" with N = {N}" if N is not None else "") +
+                            f" (got {t.dtype} {tuple(t.shape)})")
+    return t.shape[0]
+
+
+def grid_fuse_images(maps: torch.Tensor, intrinsics: torch.Tensor, pose_cam_in_world: torch.Tensor, elevation: torch.Tensor, layers,
+                     hits: torch.Tensor, center, resolution: float, alpha: float = 0.5, min_depth: float = 0.1, max_range=None,
+                     occlusion_margin: float = 0.05) -> None:
+    """Paint camera images onto grid layers, in place (include/wvn_hip.h: wvn_grid_fuse_images).  maps [B,C,H,W] fp32 (C <= 4),
+    intrinsics and pose_cam_in_world [B,4,4], elevation [N,N] (NaN = unknown), ``layers``: C fp32 [N,N] tensors, hits int32 [N,N];
+    ``center`` = (x, y) of the grid.  The cameras are applied in order; one launch, nothing is read back."""
+    who = "grid_fuse_images"
+    require_cuda(maps, "maps")
+    if maps.dtype != torch.float32 or maps.dim() != 4:
+        raise _lib.WvnError(f"{who}: maps must be fp32 [B,C,H,W] (got {maps.dtype} {tuple(maps.shape)})")
+    B, Cc, H, W = maps.shape
+    layers = list(layers)
+    if not (1 <= Cc <= _lib.GRID_MAX_CHANNELS) or len(layers) != Cc:
+        raise _lib.WvnError(f"{who}: {Cc} channels for {len(layers)} layers; 1 to {_lib.GRID_MAX_CHANNELS} channels, one layer each")
+    N = _grid_layer(elevation, "elevation", who)
+    for k, t in enumerate(layers):
+        _grid_layer(t, f"layers[{k}]", who, N=N)
+    _grid_layer(hits, "hits", who, torch.int32, N)
+    mats = []
+    for name, m in (("intrinsics", intrinsics), ("pose_cam_in_world", pose_cam_in_world)):
+        require_cuda(m, name)
+        if tuple(m.shape) != (B, 4, 4):
+            raise _lib.WvnError(f"{who}: {name} must be [{B},4,4] (got {tuple(m.shape)})")
+        mats.append(m.to(torch.float32).contiguous())
+    maps = maps.contiguous()
+    table = (C.c_void_p * Cc)(*[ptr(t) for t in layers])
+    with torch.cuda.device(maps.device):
+        check(lib().wvn_grid_fuse_images(ptr(maps), B, Cc, H, W, ptr(mats[0]), ptr(mats[1]), ptr(elevation), N, float(center[0]),
+                                         float(center[1]), float(resolution), table, ptr(hits), float(alpha), float(min_depth),
+                                         float("inf") if max_range is None else float(max_range), float(occlusion_margin), stream()),
+              "wvn_grid_fuse_images")
+
+
+def grid_sdf(layer: torch.Tensor, threshold: float, resolution: float, unknown: str = "obstacle", out=None):
+    """Exact Euclidean signed distance field of {layer < threshold} (include/wvn_hip.h: wvn_grid_sdf) -> (sdf fp32 [N,N] in metres,
+    d2 int32 [N,N] in squared cells); positive = free.  ``unknown``: what a NaN cell counts as, "obstacle", "free" or "neither" (NaN out).
+    ``out`` = (sdf, d2) to write into existing tensors."""
+    who = "grid_sdf"
+    N = _grid_layer(layer, "layer", who)
+    if unknown not in _lib.GRID_UNKNOWN:
+        raise _lib.WvnError(f"{who}: unknown={unknown!r} is not one of {tuple(_lib.GRID_UNKNOWN)}")
+    if out is None:
+        sdf = torch.empty(N, N, dtype=torch.float32, device=layer.device)
+        d2 = torch.empty(N, N, dtype=torch.int32, device=layer.device)
+    else:
+        sdf, d2 = out
+        _grid_layer(sdf, "out[0]", who, N=N)
+        _grid_layer(d2, "out[1]", who, torch.int32, N)
+    with torch.cuda.device(layer.device):
+        check(lib().wvn_grid_sdf(ptr(layer), N, float(threshold), _lib.GRID_UNKNOWN[unknown], float(resolution), ptr(d2), ptr(sdf), stream()),
+              "wvn_grid_sdf")
+    return sdf, d2
+
+
+def grid_carrot(sdf: torch.Tensor, elevation: torch.Tensor, yaw: float, center, resolution: float, distance_force_factor: float = 0.0,
+                center_force_factor: float = 0.0, discs=GRID_DEFAULT_DISCS, want_masked: bool = False):
+    """The goal selection of smart_carrot.py in one launch (include/wvn_hip.h: wvn_grid_carrot) -> (cell int32 [3] = (i, j, found),
+    goal fp32 [3] = (score, x, y), masked score layer or None), all on the device.  ``discs``: (distance, radius) pairs in cells."""
+    who = "grid_carrot"
+    N = _grid_layer(sdf, "sdf", who)
+    _grid_layer(elevation, "elevation", who, N=N)
+    discs = [(int(d), int(r)) for d, r in discs]
+    if not (1 <= len(discs) <= _lib.GRID_MAX_DISCS):
+        raise _lib.WvnError(f"{who}: {len(discs)} discs; 1 to {_lib.GRID_MAX_DISCS}")
+    table = (C.c_int * (2 * len(discs)))(*[v for d in discs for v in d])
+    cell = torch.empty(3, dtype=torch.int32, device=sdf.device)
+    goal = torch.empty(3, dtype=torch.float32, device=sdf.device)
+    masked = torch.empty(N, N, dtype=torch.float32, device=sdf.device) if want_masked else None
+    with torch.cuda.device(sdf.device):
+        check(lib().wvn_grid_carrot(ptr(sdf), ptr(elevation), N, math.cos(yaw), math.sin(yaw), float(distance_force_factor),
+                                    float(center_force_factor), table, len(discs), float(center[0]), float(center[1]), float(resolution),
+                                    ptr(cell), ptr(goal), ptr(masked), stream()), "wvn_grid_carrot")
+    return cell, goal, masked
