@@ -438,7 +438,7 @@ int wvn_dense_sift_segpool(const void* img, int img_is_u8, const int* seg, float
  * updated IN PLACE (inside the projected polygon: fmin(old, value); elsewhere untouched = fmin(old, NaN)), projected [npts][2]
  * + depth [npts] (optional outs; the polygon itself is drawn with the behind-the-camera vertices set to NaN, :180).  points: [npts][3] world coordinates shared by all nodes, or
  * [n][npts][3] when points_batched.  value = colour * traversability, read from value_dev[0] if non-NULL (no host sync when
- * the traversability lives on the GPU).  npts: any count whose vertex arrays fit the 64 KB of LDS beside the 2*H row limits (H = 448: 7700; the
+ * the traversability lives on the GPU).  npts: any count whose vertex arrays fit the 64 KB of LDS beside the 2*H row limits (npts <= 8191 - H; H = 448: 7743; the
  * untraversable plane of SupervisionNode.make_footprint_with_node has 1000).  Scan lines touched by a NaN edge stay unfilled (torch min / max).  Arithmetic order: csrc/supervision.hip header.
  * ------------------------------------------------------------------------------------------- */
 typedef struct wvn_render_node {

@@ -406,8 +406,29 @@ def project_render_fmin(Ks, poses, masks, points: torch.Tensor, value, want_proj
     """ImageProjector.project_and_render + torch.fmin merge for n nodes in one launch (csrc/supervision.hip).
     Ks / poses: lists of [4,4] fp32 CUDA tensors (scaled camera matrix, pose_cam_in_world); masks: list of contiguous
     [C,H,W] fp32 CUDA tensors, UPDATED IN PLACE; points [N,3] (shared) or [n,N,3]; value: float or 1-element CUDA tensor
-    (colour * traversability).  ``want_projected``: returns (projected [n,N,2] raw pinhole coordinates, depth [n,N] camera-frame z)."""
+    (colour * traversability).  ``want_projected``: returns (projected [n,N,2] raw pinhole coordinates, depth [n,N] camera-frame z).
+    Refused before anything is launched: no mask, a mask that is not [C,H,W] or lives on the CPU, len(Ks) or len(poses) != n, a K or
+    pose that is not [4,4], points that are not [N,3] or [n,N,3] with N >= 2, a value tensor with more than one element."""
+    who = "project_render_fmin"
     n = len(masks)
+    if n < 1 or any(not isinstance(m, torch.Tensor) or m.dim() != 3 for m in masks):
+        raise _lib.WvnError(f"{who}: masks must be a non-empty list of [C,H,W] tensors")
+    if len(Ks) != n or len(poses) != n:
+        raise _lib.WvnError(f"{who}: {len(Ks)} camera matrices and {len(poses)} poses for {n} masks")
+    for name, ts in (("K", Ks), ("pose", poses)):
+        for t in ts:
+            if tuple(t.shape) != (4, 4):
+                raise _lib.WvnError(f"{who}: every {name} must be [4,4], not {tuple(t.shape)}")
+    if points.dim() not in (2, 3) or points.shape[-1] != 3:
+        raise _lib.WvnError(f"{who}: points must be [N,3] or [n,N,3], not {tuple(points.shape)}")
+    if points.dim() == 3 and points.shape[0] != n:
+        raise _lib.WvnError(f"{who}: batched points {tuple(points.shape)} for {n} masks: the leading dimension must be {n}")
+    if points.shape[-2] < 2:
+        raise _lib.WvnError(f"{who}: a polygon needs at least 2 points, not {points.shape[-2]}")
+    if isinstance(value, torch.Tensor) and value.numel() != 1:
+        raise _lib.WvnError(f"{who}: value must be a float or a 1-element tensor, not {tuple(value.shape)}")
+    for m in masks:
+        require_cuda(m, "mask")
     dev = masks[0].device
     Cc, H, W = masks[0].shape
     points = points.to(dev, torch.float32).contiguous()
