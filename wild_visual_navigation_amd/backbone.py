@@ -189,7 +189,7 @@ def mx_unfragments(h: torch.Tensor, l8: torch.Tensor, M: int, K: int):
 def mx_matmul_reference(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """float64 statement of what an MX kernel computes for a [M][K] x w [N][K]^T (the operand roundings exactly, the sums in float64)."""
     ah, al8, _ = mx_split(a)
-    ah8 = _e5m2_bytes(ah.float())                      # the activation's h8 operand is derived from its fp16 image in registers (gemm_n384_x3.hip: derive_h8)
+    ah8 = _e5m2_bytes(ah.float())                      # the activation's h8 operand is derived from its fp16 image in registers (mx_operand.h: mx_e5m2_of_f16)
     wh, wl8, wh8 = mx_split(w)
     f = lambda b: b.view(torch.float8_e5m2).double()   # noqa: E731
     return ah.double() @ wh.double().T + (f(ah8) @ f(wl8).T + f(al8) @ f(wh8).T) / MX_RES_SCALE

@@ -14,6 +14,20 @@
     if (rc__ != WVN_OK) return rc__; \
   } while (0)
 
+int wvn_num_cus() {   // (common.h)
+  static std::atomic<int> count[64];   // per device ordinal; 0: not asked yet (two host threads racing here ask twice and store the same number)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  std::atomic<int>& c = count[dev & 63];
+  int n = c.load(std::memory_order_relaxed);
+  if (n == 0) {
+    hipDeviceProp_t prop;
+    n = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    c.store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
 extern "C" {
 
 int wvn_version(void) { return 103; }   // 103: wvn_debug_slic_lab; 102: wvn_gcn_train_*; 101: wvn_flip_average takes the source row stride; wvn_vit_forward_frames_head

@@ -45,6 +45,7 @@
 
 #include <type_traits>
 
+#include "mx_operand.h"
 #include "operand.h"
 #include "wvn_internal.h"
 
@@ -138,7 +139,6 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   // reference's real 448^2 frame q alone accounts for the 1.0e-3 token error of single-plane attention (split: 7.6e-5; k split: no
   // change; profiles/r04d_error_budget_real_frame.md)
   opx8_t ql[4];
-  typedef __attribute__((ext_vector_type(8))) int i32x8_t;
   i32x8_t ql8 = {0, 0, 0, 0, 0, 0, 0, 0};
   if constexpr (QSPLIT != 0) {
     const op16_t* qlg = q_lo + ((size_t)bh * npad + q0 + l31) * DH + hi * 8;
@@ -149,22 +149,11 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   }
 #if WVN_OPERAND_F16
   if constexpr (QSPLIT == 2) {   // byte (s, j) of the lane's 32 = e5m2(q_lo[16 s + 8 hi + j] * 2^12): the order the K fragments' top bytes are gathered in below
-    typedef __attribute__((ext_vector_type(2))) short s16x2_t;
-    typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
+    u32x4_t raw[4], half[2];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const u32x4_t raw = __builtin_bit_cast(u32x4_t, ql[s]);
-      uint32_t d[2] = {0, 0};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const uint32_t pr = raw[e];   // (scalar copy: clang's bit_cast of a vector element reads element 0)
-        const s16x2_t o = __builtin_bit_cast(s16x2_t, d[e >> 1]);
-        d[e >> 1] = __builtin_bit_cast(uint32_t, (e & 1) ? __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(o, __builtin_bit_cast(h2_t, pr), 1.0f / 4096.0f, true)
-                                                         : __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(o, __builtin_bit_cast(h2_t, pr), 1.0f / 4096.0f, false));
-      }
-      ql8[2 * s] = (int)d[0];
-      ql8[2 * s + 1] = (int)d[1];
-    }
+    for (int s = 0; s < 4; ++s) raw[s] = __builtin_bit_cast(u32x4_t, ql[s]);
+    mx_e5m2_of_f16(raw, half, MX_RES_INV);
+    ql8 = mx_pack(half[0], half[1]);
     asm volatile("" : "+v"(ql8));
   }
 #endif
@@ -372,7 +361,7 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
             }
           }
 #if WVN_OPERAND_F16
-          if constexpr (QSPLIT == 2) st[t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(k8, ql8, st[t], 1, 1, 0, 0x7f7f7f7f, 0, 0x73737373);
+          if constexpr (QSPLIT == 2) st[t] = mx_correction<true>(k8, ql8, st[t], 1);   // k_h8 x q_l8 (carries 2^12)
 #endif
         }
       if (MAYBE_TAIL && kv0 + KVB > ntok) {
@@ -527,8 +516,8 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
             const int d = 2 * u + (e >> 1);
             // (the old value travels as a SCALAR: clang's bit_cast of a vector element reads element 0)
             const uint32_t ol8 = o8l[d];
-            if (e & 1) o8l[d] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(__builtin_bit_cast(s16x2_t, ol8), a - (float)hh[0], c - (float)hh[1], 1.0f / 4096.0f, true));
-            else o8l[d] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(__builtin_bit_cast(s16x2_t, ol8), a - (float)hh[0], c - (float)hh[1], 1.0f / 4096.0f, false));
+            if (e & 1) o8l[d] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(__builtin_bit_cast(s16x2_t, ol8), a - (float)hh[0], c - (float)hh[1], MX_RES_INV, true));
+            else o8l[d] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(__builtin_bit_cast(s16x2_t, ol8), a - (float)hh[0], c - (float)hh[1], MX_RES_INV, false));
           }
           *(u32x4_t*)(fb + (2 * dt + u) * 512) = oh;
         }

@@ -419,24 +419,14 @@ __global__ __launch_bounds__(512, 2) void gemm_a384_kernel(A384Params p) {
 
 constexpr int A384_LDS_MAX = 160 * 1024;
 
-int a384_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 template <int EPI, bool TIMING>
 int launch_k(const A384Params& p, int lds, hipStream_t st) {
   static LdsOptIn lds_opt_in;   // per device (common.h)
   if (const int rc = lds_opt_in(A384_LDS_MAX, (const void*)gemm_a384_kernel<EPI, TIMING>)) return rc;
   // one persistent workgroup per CU (144 KB of LDS each), never more workgroups than (row block, column tile) units
   const long long units = (long long)ceil_div(p.M, BM) * (p.N / BNT);
-  const int grid = (int)(units < a384_num_cus() ? units : a384_num_cus());
+  const int ncu = wvn_num_cus();
+  const int grid = (int)(units < ncu ? units : ncu);
   hipLaunchKernelGGL((gemm_a384_kernel<EPI, TIMING>), dim3(grid), dim3(512), lds, st, p);
   WVN_LAUNCH_CHECK();
   return WVN_OK;

@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mx_operand.h"
 #include "wvn_internal.h"
 
 namespace {
@@ -84,26 +85,16 @@ __device__ inline void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
   lo = pack_bf16x2(a - ah, b - bh);
 }
 
-// MX (round 6; LNA only, X_GELU_FRAG / X_QKV_F16): the operand representation of gemm_n384_x3.hip's MX kernel -- h = fp16(v), l8 = e5m2((v - h) * 2^12),
+// MX (round 6; LNA only, X_GELU_FRAG / X_QKV_F16): the operand form of mx_operand.h -- h = fp16(v), l8 = e5m2((v - h) * 2^12),
 // h8 = e5m2(v) -- for both operands: per k-step region TWO fp16 MFMAs (hi * hi of the two column halves) and ONE scaled e5m2 MFMA of K = 64 (one of
 // the slice's eight correction products: 2 column halves x 2 64-k steps x {a_h8 w_l8, a_l8 w_h8}) = 128 matrix-pipe cycles instead of 192, the same
 // four ds_read_b128.  W: plane 0 = fp16 [N][384]; plane 1 = bytes [N][768] in the chunk order the kernel reads them (backbone.pack_a384_mx).
 // The row block's operands stay resident: 24 fp16 fragments + 6 eight-register l8 operands = 144 registers; a_h8 = e5m2(a_h) is derived from the fp16 fragments once per
 // (slice, 64-k step) -- 16 conversions for two regions -- which is also what the row-panel consumer does with ITS activations (one definition of h8 for activations: e5m2(fp16(v))).
-typedef __attribute__((ext_vector_type(8))) int i32x8_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-typedef __attribute__((ext_vector_type(2))) short s16x2_t;
-constexpr int MX_SC_ONE = 0x7f7f7f7f, MX_SC_RES = 0x73737373;   // E8M0 scale bytes 2^0 / 2^-12 (every byte alike)
-constexpr float MX_RES_INV = 1.0f / 4096.0f;
 #ifndef WVN_MXG
 #define WVN_MXG 12
 #endif
-constexpr int MXG = WVN_MXG;   // k-steps of fp32 rows requested at a time by the MX LayerNorm-on-load prologue (12: two HBM round trips per row block)                    // v_cvt_scalef32_* DIVIDES by its scale operand (scripts/ubench/mx_formats.hip)
-__device__ inline uint32_t mx_pk8(uint32_t old, float a, float b, float inv_scale, bool hi_word) {
-  const s16x2_t o = __builtin_bit_cast(s16x2_t, old);
-  return __builtin_bit_cast(uint32_t, hi_word ? __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(o, a, b, inv_scale, true)
-                                              : __builtin_amdgcn_cvt_scalef32_pk_bf8_f32(o, a, b, inv_scale, false));
-}
+constexpr int MXG = WVN_MXG;   // k-steps of fp32 rows requested at a time by the MX LayerNorm-on-load prologue (12: two HBM round trips per row block)
 
 constexpr int X384_LDS_MAX = 160 * 1024;
 
@@ -352,26 +343,10 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
     if constexpr (MX) {
       const int mm = s >> 2, which = (s >> 1) & 1, t8 = s & 1;
       const f16x8_t af = __builtin_bit_cast(f16x8_t, mh[ks * 8 + s]);
-      if (which == 0 && t8 == 0) {   // e5m2 of the fp16 image (what the row-panel consumer derives for ITS activations too), once per (slice, 64-k step): two regions use it
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-#pragma unroll
-        for (int sfr = 0; sfr < 4; ++sfr) {
-          uint32_t d[2] = {0, 0};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const uint32_t pr = mh[ks * 8 + 4 * mm + sfr][e];   // (scalar copy before the bit_cast)
-            const s16x2_t o = __builtin_bit_cast(s16x2_t, d[e >> 1]);
-            d[e >> 1] = __builtin_bit_cast(uint32_t, (e & 1) ? __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(o, __builtin_bit_cast(h2_t, pr), 1.0f, true)
-                                                             : __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(o, __builtin_bit_cast(h2_t, pr), 1.0f, false));
-          }
-          dh8[sfr >> 1][2 * (sfr & 1)] = d[0];
-          dh8[sfr >> 1][2 * (sfr & 1) + 1] = d[1];
-        }
-      }
-      const u32x4_t a0 = which ? m8[ks * 2 + mm][0] : dh8[0], a1 = which ? m8[ks * 2 + mm][1] : dh8[1];
-      const i32x8_t av = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
-      const u32x4_t w0 = w8[cur][0], w1 = w8[cur][1];
-      const i32x8_t wv = {(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3], (int)w1[0], (int)w1[1], (int)w1[2], (int)w1[3]};
+      // e5m2 of the fp16 image (what the row-panel consumer derives for ITS activations too), once per (slice, 64-k step): two regions use it
+      if (which == 0 && t8 == 0) mx_e5m2_of_f16(&mh[ks * 8 + 4 * mm], dh8);
+      const i32x8_t av = which ? mx_pack(m8[ks * 2 + mm][0], m8[ks * 2 + mm][1]) : mx_pack(dh8[0], dh8[1]);
+      const i32x8_t wv = mx_pack(w8[cur][0], w8[cur][1]);
       // accumulators alternate: even regions 0, 1, 0 -- odd regions 1, 0, 1 (the scaled MFMA goes to column half t8 = s & 1)
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
@@ -380,9 +355,7 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
         if constexpr (TR) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, af, acc[t], 0, 0, 0);
         else acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, wf, acc[t], 0, 0, 0);
       }
-      // which 0: W_l8 (carries 2^12) x a_h8;  which 1: W_h8 x a_l8 (carries 2^12)
-      if constexpr (TR) acc[t8] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wv, av, acc[t8], 1, 1, 0, which ? MX_SC_ONE : MX_SC_RES, 0, which ? MX_SC_RES : MX_SC_ONE);
-      else acc[t8] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, wv, acc[t8], 1, 1, 0, which ? MX_SC_RES : MX_SC_ONE, 0, which ? MX_SC_ONE : MX_SC_RES);
+      acc[t8] = mx_correction<TR>(wv, av, acc[t8], which);
       return;
     }
     const bf16x8_t ah = xh[ks * 8 + s], al = xl[ks * 8 + s];
@@ -423,7 +396,7 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
           const uint32_t h = pack_f16x2(v0, v1);
           const h2_t hh = __builtin_bit_cast(h2_t, h);
           fragh[2 * (g & 1) + (h2 >> 1)] = h;
-          // (no h8 plane: the consumer derives e5m2(h) from the fp16 fragments in registers -- gemm_n384_x3.hip: derive_h8)
+          // (no h8 plane: the consumer derives e5m2(h) from the fp16 fragments in registers -- mx_operand.h: mx_e5m2_of_f16)
           {
             typedef __attribute__((ext_vector_type(2))) float f2_t;
             const f2_t res = f2_t{v0, v1} - f2_t{(float)hh[0], (float)hh[1]};   // one v_pk_add_f32 for the two residues
@@ -915,22 +888,6 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
 #pragma unroll
     for (int x = 0; x < 2; ++x) w8[par][x] = *(const u32x4_t*)(base + 8192 + (8 * (r >> 1) + 4 * (r & 1) + 2 * x) * 512);
   };
-  auto derive_h8 = [&](int c) __attribute__((always_inline)) {   // a_h8 = e5m2 of the fp16 image of 64-k step c (what the row-panel consumer derives for its activations too)
-    typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-#pragma unroll
-    for (int sfr = 0; sfr < 4; ++sfr) {
-      uint32_t d[2] = {0, 0};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const uint32_t pr = mh[c * 4 + sfr][e];
-        const s16x2_t o = __builtin_bit_cast(s16x2_t, d[e >> 1]);
-        d[e >> 1] = __builtin_bit_cast(uint32_t, (e & 1) ? __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(o, __builtin_bit_cast(h2_t, pr), 1.0f, true)
-                                                         : __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(o, __builtin_bit_cast(h2_t, pr), 1.0f, false));
-      }
-      dh8[sfr >> 1][2 * (sfr & 1)] = d[0];
-      dh8[sfr >> 1][2 * (sfr & 1) + 1] = d[1];
-    }
-  };
   auto mfma_region = [&](int ks, int r, int par, auto tr_tag) __attribute__((always_inline)) {
     constexpr bool TR = decltype(tr_tag)::value;
     const int c = 2 * ks + (r >> 1), which = r & 1;   // the 64-k step; 0: W_l8 (carries 2^12) x a_h8, 1: W_h8 x a_l8 (carries 2^12)
@@ -941,12 +898,8 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
       if constexpr (TR) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, af, acc, 0, 0, 0);
       else acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, wf, acc, 0, 0, 0);
     }
-    const u32x4_t a0 = which ? m8[c][0] : dh8[0], a1 = which ? m8[c][1] : dh8[1];
-    const i32x8_t av = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
-    const u32x4_t w0 = w8[par][0], w1 = w8[par][1];
-    const i32x8_t wv = {(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3], (int)w1[0], (int)w1[1], (int)w1[2], (int)w1[3]};
-    if constexpr (TR) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wv, av, acc, 1, 1, 0, which ? MX_SC_ONE : MX_SC_RES, 0, which ? MX_SC_RES : MX_SC_ONE);
-    else acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, wv, acc, 1, 1, 0, which ? MX_SC_RES : MX_SC_ONE, 0, which ? MX_SC_ONE : MX_SC_RES);
+    const i32x8_t av = which ? mx_pack(m8[c][0], m8[c][1]) : mx_pack(dh8[0], dh8[1]);
+    acc = mx_correction<TR>(mx_pack(w8[par][0], w8[par][1]), av, acc, which);
   };
 
   auto init_acc = [&](int j, auto tr_tag) __attribute__((always_inline)) {
@@ -1068,7 +1021,8 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
     for (int r = 0; r < 4; ++r) {
       if (r + 1 < 4) frag_read(i % S2_NS, r + 1, (r & 1) ^ 1);
       issue_piece(i + S2_NS - 1, r);
-      if ((r & 1) == 0) derive_h8(2 * ks + (r >> 1));
+      // a_h8 = e5m2 of the fp16 image of this 64-k step (what the row-panel consumer derives for its activations too)
+      if ((r & 1) == 0) mx_e5m2_of_f16(&mh[(2 * ks + (r >> 1)) * 4], dh8);
       __builtin_amdgcn_sched_barrier(0);
       mfma_region(ks, r, r & 1, tr_tag);
       __builtin_amdgcn_sched_barrier(0);
@@ -1130,15 +1084,10 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
 
 bool g_x384_split_qkv = getenv("WVN_X384_SPLIT_QKV") != nullptr;   // A/B: q | k and v^T as two launches (the form before the merged kernel)
 
-int x384_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
+// persistent grid: per_cu workgroups per CU, never more than there are (row block, column tile) units
+int x384_grid(long long units, int per_cu = 1) {
+  const long long cap = (long long)per_cu * wvn_num_cus();
+  return (int)(units < cap ? units : cap);
 }
 
 template <int EPI>
@@ -1149,7 +1098,7 @@ int launch_mx(const X384Params& p, hipStream_t st) {
   static LdsOptIn lds_opt_in;
   if (const int rc = lds_opt_in(X384_LDS_MAX, (const void*)gemm_a384_x3_kernel<EPI, false, true, true>, (const void*)gemm_a384_x3_kernel<EPI, true, true, true>)) return rc;
   const long long units = (long long)ceil_div(p.M, BM) * (p.N / BNT);
-  const int grid = (int)(units < x384_num_cus() ? units : x384_num_cus());
+  const int grid = x384_grid(units);
   static const bool burst = getenv("WVN_A384_MX_BURST") != nullptr;
   if (burst) {
     static LdsOptIn lds_opt_in_b;
@@ -1176,8 +1125,7 @@ int launch_mx2(X384Params p, hipStream_t st) {
   if (const int rc = lds_opt_in(80 * 1024, (const void*)gemm_a384_mx2_kernel<EPI>, (const void*)gemm_a384_mx2_kernel<EPI, true>)) return rc;
   const long long units = (long long)ceil_div(p.M, BM) * (p.N / S2_BN);
   static const bool one_per_cu = getenv("WVN_A384_MX2_ONE") != nullptr;   // (experiment: one workgroup per CU -- what a wave does when it has its SIMD to itself)
-  const int cap = (one_per_cu ? 1 : 2) * x384_num_cus();
-  const int grid = (int)(units < cap ? units : cap);
+  const int grid = x384_grid(units, one_per_cu ? 1 : 2);
   if (p.dbg) hipLaunchKernelGGL((gemm_a384_mx2_kernel<EPI, true>), dim3(grid), dim3(256), lds, st, p);   // (dbg: 2 x CUs x 4 waves x 4 counters)
   else hipLaunchKernelGGL((gemm_a384_mx2_kernel<EPI>), dim3(grid), dim3(256), lds, st, p);
   WVN_LAUNCH_CHECK();
@@ -1197,7 +1145,7 @@ int launch(const X384Params& p, hipStream_t st) {
   static LdsOptIn lds_opt_in;
   if (const int rc = lds_opt_in(X384_LDS_MAX, (const void*)gemm_a384_x3_kernel<EPI>, (const void*)gemm_a384_x3_kernel<EPI, true>)) return rc;
   const long long units = (long long)ceil_div(p.M, BM) * (p.N / BNT);
-  const int grid = (int)(units < x384_num_cus() ? units : x384_num_cus());
+  const int grid = x384_grid(units);
   if constexpr (CAN_LNA) {
     if (lna) {
       static LdsOptIn lds_opt_in_lna;
@@ -1299,7 +1247,7 @@ int wvn_gemm_a384_head_launch(const float* x, int ldx, const float* stats, const
   static LdsOptIn lds_opt_in;
   if (const int rc = lds_opt_in(X384_LDS_MAX, (const void*)gemm_a384_x3_kernel<X_HEAD, false, true>)) return rc;
   const long long units = (long long)ceil_div(p.M, BM) * (N / BNT);
-  const int grid = (int)(units < x384_num_cus() ? units : x384_num_cus());
+  const int grid = x384_grid(units);
   hipLaunchKernelGGL((gemm_a384_x3_kernel<X_HEAD, false, true>), dim3(grid), dim3(256), lds, st, p);
   WVN_LAUNCH_CHECK();
   return WVN_OK;

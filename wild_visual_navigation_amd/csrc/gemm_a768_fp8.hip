@@ -394,22 +394,11 @@ __global__ __launch_bounds__(256, 2) void gemm_a768_fp8_kernel(A768Params p) {
   }
 }
 
-int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 template <int EPI>
 int launch(const A768Params& p, hipStream_t st) {
   const long long units = (long long)ceil_div(p.M, BM) * (p.N / BN);
   static const int per_cu = [] { const char* e = getenv("WVN_A768_WG_PER_CU"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 2 ? v : 2; }();
-  const long long cap = (long long)per_cu * num_cus();
+  const long long cap = (long long)per_cu * wvn_num_cus();
   const int grid = (int)(units < cap ? units : cap);
   const int lds = LDS_BYTES;
   static LdsOptIn lds_opt_in;

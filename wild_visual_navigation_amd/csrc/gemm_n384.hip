@@ -164,17 +164,6 @@ __global__ __launch_bounds__(512, 2) void gemm_n384_kernel(N384Params p) {
   }
 }
 
-int n384_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace
 
 // Eligibility: N == 384, K % 32 == 0, residual epilogue, 16-byte aligned operands, 32-bit byte offsets;
@@ -191,7 +180,7 @@ int WVN_OPSYM(wvn_gemm_n384_launch)(const GemmBf16Params& g, int epi, hipStream_
   // Row blocks are dealt round-robin to one persistent workgroup per CU; a last round that would occupy less than a
   // quarter of the CUs is left to the caller's tiled kernel instead (rows are independent): 786 row blocks on 256 CUs
   // are 3 full rounds here + 18 row blocks there, not 4 rounds.
-  const int ncu = n384_num_cus();
+  const int ncu = wvn_num_cus();
   int nrb_all = ceil_div(g.M, BM), m_here = g.M;
   // One workgroup owns 256 rows x all 384 columns, so M / 256 workgroups is all the parallelism there is: below about three
   // quarters of a round the tiled kernel (3 column tiles per row block) is faster (measured: 1-8 frames of 3152 rows 0.33 /

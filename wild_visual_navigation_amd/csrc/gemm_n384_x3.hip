@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mx_operand.h"
 #include "wvn_internal.h"
 
 namespace {
@@ -136,6 +137,43 @@ __device__ inline void n384_epilogue(const f32x16_t (&acc)[NTILE], unsigned char
   }
 }
 
+// ---- what the persistent kernels below share ----
+template <int NT>
+__device__ __forceinline__ void n384_zero(f32x16_t (&acc)[NT]) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+}
+
+// TIMING builds: {wait + barrier, k-steps, epilogue, total} shader cycles of row group rg of this workgroup (N384X3Params::dbg)
+__device__ __forceinline__ void n384_write_cycles(long long* dbg, int rg, long long t_wait, long long t_steps, long long t_epi, long long t_start) {
+  long long* d = dbg + ((size_t)blockIdx.x * 4 + rg) * 4;
+  d[0] = t_wait; d[1] = t_steps; d[2] = t_epi; d[3] = (long long)__builtin_amdgcn_s_memtime() - t_start;
+}
+
+// The tile pair (2 pr, 2 pr + 1) of a bf16 x 3 k-step: hi*lo, lo*hi, hi*hi of the two tiles alternate (a filler between two MFMAs on the SAME
+// accumulator costs ~43 cycles, between different ones ~6), and behind each of the six goes one LDS read, one VMEM request and two VALU
+// instructions of what the caller has written in front of the pair (the next pair's fragments, the DMA pieces that ride as fillers).
+template <int NT>
+__device__ __forceinline__ void n384_x3_tile_pair(f32x16_t (&acc)[NT], int pr, const bf16x8_t (&wh)[2], const bf16x8_t (&wl)[2], bf16x8_t ah, bf16x8_t al) {
+#pragma unroll
+  for (int term = 0; term < 3; ++term)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const bf16x8_t w = term == 1 ? wl[t] : wh[t];
+      const bf16x8_t a = term == 0 ? al : ah;          // hi*lo, lo*hi, hi*hi
+      acc[2 * pr + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, a, acc[2 * pr + t], 0, 0, 0);
+    }
+#pragma unroll
+  for (int n = 0; n < 6; ++n) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+  }
+}
+
 template <bool TIMING>
 __global__ __launch_bounds__(256, 1) void gemm_n384_x3_kernel(N384X3Params p) {
   wvn_fp16_saturate();
@@ -199,10 +237,7 @@ __global__ __launch_bounds__(256, 1) void gemm_n384_x3_kernel(N384X3Params p) {
       }
 
     f32x16_t acc[NTILE];
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    n384_zero(acc);
 
     for (int i = 0; i < nk; ++i) {
       long long c0 = 0, c1 = 0;
@@ -237,21 +272,7 @@ __global__ __launch_bounds__(256, 1) void gemm_n384_x3_kernel(N384X3Params p) {
               wl[nx][t] = *(const bf16x8_t*)(st + rdw + W_PLANE + (2 * pr + 2 + t) * 1024);
             }
           }
-#pragma unroll
-          for (int term = 0; term < 3; ++term)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-              const bf16x8_t w = term == 1 ? wl[cur][t] : wh[cur][t];
-              const bf16x8_t a = term == 0 ? al : ah;          // hi*lo, lo*hi, hi*hi
-              acc[2 * pr + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, a, acc[2 * pr + t], 0, 0, 0);
-            }
-#pragma unroll
-          for (int n = 0; n < 6; ++n) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-          }
+          n384_x3_tile_pair(acc, pr, wh[cur], wl[cur], ah, al);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -265,10 +286,7 @@ __global__ __launch_bounds__(256, 1) void gemm_n384_x3_kernel(N384X3Params p) {
     if constexpr (TIMING) t_epi += (long long)__builtin_amdgcn_s_memtime() - e0;
   }
   if constexpr (TIMING) {
-    if (lane == 0 && p.dbg) {
-      long long* d = p.dbg + ((size_t)blockIdx.x * 4 + wave) * 4;
-      d[0] = t_wait; d[1] = t_steps; d[2] = t_epi; d[3] = (long long)__builtin_amdgcn_s_memtime() - t_start;
-    }
+    if (lane == 0 && p.dbg) n384_write_cycles(p.dbg, wave, t_wait, t_steps, t_epi, t_start);
   }
 }
 
@@ -283,6 +301,21 @@ constexpr int FW = 6;                            // W DMA pieces per wave and k-
 constexpr int FSTAGE = 2 * W_PLANE;              // 24 KB
 constexpr int FNS = 5;                           // ring depth (120 KB)
 static_assert(FNS * FSTAGE <= RING_BYTES, "the fragment form's ring must fit in front of the bias table");
+
+// piece u of this wave's PIECES of packed-W stage i (wv0: wave * PIECES * 1024 + lane * 16) into its slot of the NSTAGES-deep ring
+template <int NSTAGES, int PIECES>
+__device__ __forceinline__ void n384_w_piece(unsigned char* smem, __amdgpu_buffer_rsrc_t rs_w, int wave, unsigned wv0, int i, int u) {
+  unsigned char* st = smem + (i % NSTAGES) * FSTAGE;
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(st + (wave * PIECES + u) * 1024), 16, wv0 + u * 1024,
+                                           __builtin_amdgcn_readfirstlane((unsigned)i * FSTAGE), 0, 0);
+}
+
+// the hi and lo bf16 fragments of k-step i of the wave's row group (a_base: its fragment 0 in the hi plane)
+__device__ __forceinline__ void n384_load_a_pair(__amdgpu_buffer_rsrc_t rs_a, int lane, unsigned a_base, unsigned a_lo_off, int i, u32x4_t& h, u32x4_t& l) {
+  const unsigned so = __builtin_amdgcn_readfirstlane(a_base + (unsigned)i * 1024);
+  h = __builtin_amdgcn_raw_buffer_load_b128(rs_a, lane * 16, so, 0);
+  l = __builtin_amdgcn_raw_buffer_load_b128(rs_a, lane * 16, so + a_lo_off, 0);
+}
 
 template <bool TIMING>
 __global__ __launch_bounds__(256, 1) void gemm_n384_x3_frag_kernel(N384X3Params p) {
@@ -312,17 +345,9 @@ __global__ __launch_bounds__(256, 1) void gemm_n384_x3_frag_kernel(N384X3Params 
   for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
     const int m0w = rb * BM + wave * 32;
     const unsigned a_base = __builtin_amdgcn_readfirstlane((unsigned)((size_t)(m0w >> 5) * nk * 1024));   // fragment (R, 0) of the hi plane
-    auto piece_w = [&](int i, int u) {
-      unsigned char* st = smem + (i % FNS) * FSTAGE;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(st + (wave * FW + u) * 1024), 16, wv0 + u * 1024,
-                                               __builtin_amdgcn_readfirstlane((unsigned)i * FSTAGE), 0, 0);
-    };
+    auto piece_w = [&](int i, int u) { n384_w_piece<FNS, FW>(smem, rs_w, wave, wv0, i, u); };
     u32x4_t afh[PD], afl[PD];
-    auto load_a = [&](int i, int slot) {
-      const unsigned so = __builtin_amdgcn_readfirstlane(a_base + (unsigned)i * 1024);
-      afh[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, lane * 16, so, 0);
-      afl[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, lane * 16, so + a_lo_off, 0);
-    };
+    auto load_a = [&](int i, int slot) { n384_load_a_pair(rs_a, lane, a_base, a_lo_off, i, afh[slot], afl[slot]); };
     __syncthreads();  // the previous row block's staging reads are done (and the bias table is visible) before DMA reuses the LDS
     // VM queue order: the A fragments of k-steps 0 .. PD - 1 first, then the W slices 0 .. FNS - 2
 #pragma unroll
@@ -335,10 +360,7 @@ __global__ __launch_bounds__(256, 1) void gemm_n384_x3_frag_kernel(N384X3Params 
       }
 
     f32x16_t acc[NTILE];
-#pragma unroll
-    for (int t = 0; t < NTILE; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    n384_zero(acc);
 
     for (int ib = 0; ib < nk; ib += PD) {
 #pragma unroll
@@ -373,21 +395,7 @@ __global__ __launch_bounds__(256, 1) void gemm_n384_x3_frag_kernel(N384X3Params 
               wl[nx][t] = *(const bf16x8_t*)(st + rdw + W_PLANE + (2 * pr + 2 + t) * 1024);
             }
           }
-#pragma unroll
-          for (int term = 0; term < 3; ++term)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-              const bf16x8_t w = term == 1 ? wl[cur][t] : wh[cur][t];
-              const bf16x8_t a = term == 0 ? al : ah;          // hi*lo, lo*hi, hi*hi
-              acc[2 * pr + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, a, acc[2 * pr + t], 0, 0, 0);
-            }
-#pragma unroll
-          for (int n = 0; n < 6; ++n) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-          }
+          n384_x3_tile_pair(acc, pr, wh[cur], wl[cur], ah, al);
           __builtin_amdgcn_sched_barrier(0);
         }
         if (i + PD < nk) load_a(i + PD, jj);   // (after the last MFMA that reads the slot)
@@ -402,10 +410,7 @@ __global__ __launch_bounds__(256, 1) void gemm_n384_x3_frag_kernel(N384X3Params 
     if constexpr (TIMING) t_epi += (long long)__builtin_amdgcn_s_memtime() - e0;
   }
   if constexpr (TIMING) {
-    if (lane == 0 && p.dbg) {
-      long long* d = p.dbg + ((size_t)blockIdx.x * 4 + wave) * 4;
-      d[0] = t_wait; d[1] = t_steps; d[2] = t_epi; d[3] = (long long)__builtin_amdgcn_s_memtime() - t_start;
-    }
+    if (lane == 0 && p.dbg) n384_write_cycles(p.dbg, wave, t_wait, t_steps, t_epi, t_start);
   }
 }
 
@@ -533,17 +538,9 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_x3_frag_pair_kernel(N384X3Pa
   for (int rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
     const int m0w = rb * BM + rg * 32;
     const unsigned a_base = __builtin_amdgcn_readfirstlane((unsigned)((size_t)(m0w >> 5) * nk * 1024));   // fragment (R, 0) of the hi plane
-    auto piece_w = [&](int i, int u) {
-      unsigned char* st = smem + (i % PNS) * FSTAGE;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(st + (wave * PFW + u) * 1024), 16, wv0 + u * 1024,
-                                               __builtin_amdgcn_readfirstlane((unsigned)i * FSTAGE), 0, 0);
-    };
+    auto piece_w = [&](int i, int u) { n384_w_piece<PNS, PFW>(smem, rs_w, wave, wv0, i, u); };
     u32x4_t afh[PD], afl[PD];
-    auto load_a = [&](int i, int slot) {
-      const unsigned so = __builtin_amdgcn_readfirstlane(a_base + (unsigned)i * 1024);
-      afh[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, lane * 16, so, 0);
-      afl[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, lane * 16, so + a_lo_off, 0);
-    };
+    auto load_a = [&](int i, int slot) { n384_load_a_pair(rs_a, lane, a_base, a_lo_off, i, afh[slot], afl[slot]); };
     __syncthreads();  // the previous row block's staging / statistics reads are done (and the bias table is visible) before DMA reuses the LDS
 #pragma unroll
     for (int j = 0; j < PD; ++j) load_a(j, j);
@@ -555,10 +552,7 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_x3_frag_pair_kernel(N384X3Pa
       }
 
     f32x16_t acc[NTILE / 2];
-#pragma unroll
-    for (int t = 0; t < NTILE / 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    n384_zero(acc);
 
     // slice 0 landed (younger: the pieces of slices 1 .. PNS - 2), every wave's part of it: its first tile pair into slot 0
     bf16x8_t wh[2][2], wl[2][2];   // [slot][tile of the pair]; the first pair of k-step i sits in slot i & 1 (three pairs per k-step: the slots alternate)
@@ -602,21 +596,7 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_x3_frag_pair_kernel(N384X3Pa
               wl[nx][t] = *(const bf16x8_t*)(st1 + rdw + W_PLANE + t * 1024);
             }
           }
-#pragma unroll
-          for (int term = 0; term < 3; ++term)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-              const bf16x8_t w = term == 1 ? wl[cur][t] : wh[cur][t];
-              const bf16x8_t a = term == 0 ? al : ah;          // hi*lo, lo*hi, hi*hi
-              acc[2 * pr + t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, a, acc[2 * pr + t], 0, 0, 0);
-            }
-#pragma unroll
-          for (int n = 0; n < 6; ++n) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-          }
+          n384_x3_tile_pair(acc, pr, wh[cur], wl[cur], ah, al);
           __builtin_amdgcn_sched_barrier(0);
         }
         if (i + PD < nk) load_a(i + PD, jj);   // (after the last MFMA that reads the slot)
@@ -631,10 +611,7 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_x3_frag_pair_kernel(N384X3Pa
     if constexpr (TIMING) t_epi += (long long)__builtin_amdgcn_s_memtime() - e0;
   }
   if constexpr (TIMING) {
-    if (lane == 0 && p.dbg && ch == 0) {
-      long long* d = p.dbg + ((size_t)blockIdx.x * 4 + rg) * 4;
-      d[0] = t_wait; d[1] = t_steps; d[2] = t_epi; d[3] = (long long)__builtin_amdgcn_s_memtime() - t_start;
-    }
+    if (lane == 0 && p.dbg && ch == 0) n384_write_cycles(p.dbg, rg, t_wait, t_steps, t_epi, t_start);
   }
 }
 
@@ -658,10 +635,8 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_x3_frag_pair_kernel(N384X3Pa
 // DMA pieces.  A: fragment-major again, per row group R and 64-k step c four 1 KB fp16 fragments (hi plane, as EPI_GELU_FRAG) and two 1 KB
 // halves in each of the two 8-bit planes: lane (row, h) holds bytes (s', j) = k-step s' of the four, element j of its eight -- the order the
 // producers' accumulators hold them; two 64-k steps in flight (64 registers).
-typedef __attribute__((ext_vector_type(8))) int i32x8_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+// The form itself -- the conversions, the scale bytes, the correction product -- is stated in mx_operand.h.
 constexpr int MXD = 2;                            // 64-k steps of A in flight
-constexpr int MX_SC_ONE = 0x7f7f7f7f, MX_SC_RES = 0x73737373;   // E8M0 scale bytes: 2^0, 2^-12 (all four bytes alike: op_sel never matters)
 
 struct N384MXExtra { unsigned a_l8_off; };   // byte offset of the l8 plane behind the fp16 plane (one buffer descriptor)
 
@@ -676,7 +651,6 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_mx_pair_kernel(N384X3Params 
   const int rg = wave & 3, ch = wave >> 2;
   const int l31 = lane & 31, hi = lane >> 5;
   const int nk = p.K / BKS;                      // stages: four per 64 k; a multiple of 8 (launcher)
-  const int nmac = p.K / 64;
   const float* bias_l = (const float*)(smem + PBIAS_OFF);
   const float* ls_l = (const float*)(smem + PLS_OFF);
   for (int i = tid; i < NN; i += 512) {
@@ -697,41 +671,21 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_mx_pair_kernel(N384X3Params 
     const int m0w = rb * BM + rg * 32;
     const unsigned a_base = __builtin_amdgcn_readfirstlane((unsigned)((size_t)(m0w >> 5) * p.K * 64));    // fragment (R, 0) of the fp16 plane
     const unsigned a8_base = __builtin_amdgcn_readfirstlane((unsigned)((size_t)(m0w >> 5) * p.K * 32));   // (R, 0) of an 8-bit plane
-    auto piece_w = [&](int i, int u) {
-      unsigned char* st = smem + (i % PNS) * FSTAGE;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(st + (wave * PFW + u) * 1024), 16, wv0 + u * 1024,
-                                               __builtin_amdgcn_readfirstlane((unsigned)i * FSTAGE), 0, 0);
-    };
+    auto piece_w = [&](int i, int u) { n384_w_piece<PNS, PFW>(smem, rs_w, wave, wv0, i, u); };
     u32x4_t ah[MXD][4], a8[MXD][2][2];   // a8[slot][0 = h8 | 1 = l8][half]
     auto load_ah = [&](int c, int slot) {
 #pragma unroll
       for (int s = 0; s < 4; ++s)
         ah[slot][s] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, lane * 16, __builtin_amdgcn_readfirstlane(a_base + (unsigned)(c * 4 + s) * 1024), 0);
     };
-    auto load_a8 = [&](int c, int slot) {   // the l8 plane (the h8 operand is derived from the fp16 fragments: derive_h8)
+    auto load_a8 = [&](int c, int slot) {   // the l8 plane (the h8 operand is derived from the fp16 fragments: mx_e5m2_of_f16)
 #pragma unroll
       for (int x = 0; x < 2; ++x)
         a8[slot][1][x] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, lane * 16, __builtin_amdgcn_readfirstlane(a8_base + ex.a_l8_off + (unsigned)(c * 2 + x) * 1024), 0);
     };
-    // a_h8 = e5m2(a_h): sixteen v_cvt_scalef32_pk_bf8_f16 per 64 k and lane, in VALU slots this kernel does not use otherwise -- instead of a third plane
-    // in HBM (a quarter of the A stream, which is what the stage waits for: profiles/r06_mx_kernels.md) and a conversion + two stores per tile in the producers
-    auto derive_h8 = [&](int slot) {
-      typedef __attribute__((ext_vector_type(2))) short s16x2_t;
-      typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-#pragma unroll
-      for (int sfr = 0; sfr < 4; ++sfr) {
-        uint32_t d[2] = {0, 0};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const uint32_t pr = ah[slot][sfr][e];   // (scalar copy: clang's bit_cast of a vector element reads element 0)
-          const s16x2_t o = __builtin_bit_cast(s16x2_t, d[e >> 1]);
-          d[e >> 1] = __builtin_bit_cast(uint32_t, (e & 1) ? __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(o, __builtin_bit_cast(h2_t, pr), 1.0f, true)
-                                                           : __builtin_amdgcn_cvt_scalef32_pk_bf8_f16(o, __builtin_bit_cast(h2_t, pr), 1.0f, false));
-        }
-        a8[slot][0][sfr >> 1][2 * (sfr & 1)] = d[0];
-        a8[slot][0][sfr >> 1][2 * (sfr & 1) + 1] = d[1];
-      }
-    };
+    // a_h8 = e5m2(a_h) (a8[slot][0], filled in the stage of kind 1): sixteen v_cvt_scalef32_pk_bf8_f16 per 64 k and lane, in VALU slots this kernel does not use otherwise
+    // -- instead of a third plane in HBM (a quarter of the A stream, which is what the stage waits for: profiles/r06_mx_kernels.md) and a conversion + two
+    // stores per tile in the producers
     __syncthreads();  // the previous row block's staging / statistics reads are done (and the bias table is visible) before DMA reuses the LDS
     // (the order is pinned: hipcc counts the operations behind a register load to size the vmcnt wait in front of its first use, and takes the
     //  minimum over the loop's two entry edges -- left to the scheduler, the operands of stage 0 were requested LAST and every trip waited for
@@ -751,10 +705,7 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_mx_pair_kernel(N384X3Params 
       }
 
     f32x16_t acc[NTILE / 2];
-#pragma unroll
-    for (int t = 0; t < NTILE / 2; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    n384_zero(acc);
 
     u32x4_t wq[2][2][2];   // [slot][x][tile of the pair]; the first pair of stage i sits in slot i & 1 (three pairs per stage: the slots alternate)
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((PNS - 2) * PFW) : "memory");
@@ -803,7 +754,7 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_mx_pair_kernel(N384X3Params 
           for (int x = 0; x < 2; ++x)
 #pragma unroll
             for (int t = 0; t < 2; ++t) wq[nx][x][t] = *(const u32x4_t*)(src + rdw + x * W_PLANE + t * 1024);
-          if (kind == 1 && pr == 0) derive_h8(slot);   // (the fp16 fragments of this 64-k step are in: stage kind 0 has used them; VALU work beside this stage's MFMAs)
+          if (kind == 1 && pr == 0) mx_e5m2_of_f16(ah[slot], a8[slot][0]);   // (the fp16 fragments of this 64-k step are in: stage kind 0 has used them; VALU work beside this stage's MFMAs)
           if (kind < 2) {
 #pragma unroll
             for (int x = 0; x < 2; ++x)
@@ -819,16 +770,10 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_mx_pair_kernel(N384X3Params 
               __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
             }
           } else {
-            const u32x4_t a0 = a8[slot][kind - 2][0], a1 = a8[slot][kind - 2][1];
-            const i32x8_t av = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+            const i32x8_t av = mx_pack(a8[slot][kind - 2][0], a8[slot][kind - 2][1]);
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-              const u32x4_t w0 = wq[cur][0][t], w1 = wq[cur][1][t];
-              const i32x8_t wv = {(int)w0[0], (int)w0[1], (int)w0[2], (int)w0[3], (int)w1[0], (int)w1[1], (int)w1[2], (int)w1[3]};
-              // kind 2: W_l8 (carries 2^12) x a_h8;  kind 3: W_h8 x a_l8 (carries 2^12)
-              acc[2 * pr + t] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wv, av, acc[2 * pr + t], 1, 1, 0, kind == 2 ? MX_SC_RES : MX_SC_ONE, 0,
-                                                                                kind == 2 ? MX_SC_ONE : MX_SC_RES);
-            }
+            for (int t = 0; t < 2; ++t)   // kind 2: W_l8 x a_h8;  kind 3: W_h8 x a_l8
+              acc[2 * pr + t] = mx_correction<true>(mx_pack(wq[cur][0][t], wq[cur][1][t]), av, acc[2 * pr + t], kind - 2);
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
               __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -856,10 +801,7 @@ __global__ __launch_bounds__(512, 1) void gemm_n384_mx_pair_kernel(N384X3Params 
     if constexpr (TIMING) t_epi += (long long)__builtin_amdgcn_s_memtime() - e0;
   }
   if constexpr (TIMING) {
-    if (lane == 0 && p.dbg && ch == 0) {
-      long long* d = p.dbg + ((size_t)blockIdx.x * 4 + rg) * 4;
-      d[0] = t_wait; d[1] = t_steps; d[2] = t_epi; d[3] = (long long)__builtin_amdgcn_s_memtime() - t_start;
-    }
+    if (lane == 0 && p.dbg && ch == 0) n384_write_cycles(p.dbg, rg, t_wait, t_steps, t_epi, t_start);
   }
 }
 
@@ -867,15 +809,24 @@ int g_n384_mx_var = 0;   // timing experiments of the instrumented MX build (wvn
 int g_n384_pair = 1;   // 1: the wave-pair form of the fragment kernel (default since its barrier covers the NEXT slice: 1355 against 1546 cycles per k-step and
                        // SIMD, fc2 -4 % wall time), 0: one wave per SIMD (round 4; wvn_debug_n384_pair).  scripts/bench_n384_pair.py, profiles/r05_wave_pair.md
 
-int n384x3_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
+// ---- what the three launchers share ----
+// the residual update's parameter block; a_plane / w_plane: elements between an operand's hi and lo plane where the kernel reads them that way
+N384X3Params n384_params(const GemmBf16Params& g, size_t a_plane, int lda, size_t w_plane) {
+  N384X3Params p{};
+  p.A = g.A; p.a_plane = a_plane; p.lda = lda; p.W = g.W; p.w_plane = w_plane; p.ldw = g.K; p.bias = g.bias; p.ls = g.ls;
+  p.C = (float*)g.C; p.ldc = g.ldc; p.M = g.M; p.K = g.K; p.dbg = g.dbg; p.stats = g.ln_stats_out; p.eps = g.ln_eps;
+  return p;
+}
+
+// persistent: one workgroup per CU, and none without a row block; the TIMING instantiation when the caller gave a counter buffer
+template <typename... Extra>
+int n384_launch(void (*plain)(N384X3Params, Extra...), void (*timed)(N384X3Params, Extra...), int threads, int lds_bytes, hipStream_t st,
+                const N384X3Params& p, Extra... extra) {
+  const int ncu = wvn_num_cus(), nrb = ceil_div(p.M, BM);
+  const auto kernel = p.dbg ? timed : plain;
+  hipLaunchKernelGGL(kernel, dim3(nrb < ncu ? nrb : ncu), dim3(threads), lds_bytes, st, p, extra...);
+  WVN_LAUNCH_CHECK();
+  return WVN_OK;
 }
 
 }  // namespace
@@ -894,18 +845,11 @@ int wvn_gemm_n384_x3_launch(const GemmBf16Params& g, int epi, hipStream_t st) {
   const size_t c_rows = patch ? (size_t)(g.M / g.npatch) * g.ntok_s : (size_t)g.M;
   if ((a_plane + (size_t)g.M * g.lda) * 2 >= (1ull << 32) || c_rows * g.ldc * 4 >= (1ull << 32) || (w_plane + (size_t)NN * g.ldw) * 2 >= (1ull << 32))
     return WVN_ERR_ARG;
-  N384X3Params p{};
-  p.A = g.A; p.a_plane = a_plane; p.lda = g.lda; p.W = g.W; p.w_plane = w_plane; p.ldw = g.ldw; p.bias = g.bias; p.ls = g.ls;
-  p.C = (float*)g.C; p.ldc = g.ldc; p.M = g.M; p.K = g.K; p.dbg = g.dbg; p.stats = g.ln_stats_out; p.eps = g.ln_eps;
+  N384X3Params p = n384_params(g, a_plane, g.lda, w_plane);   // (ldw == K, checked above)
   if (patch) { p.pos = g.pos; p.npatch = g.npatch; p.ntok_s = g.ntok_s; p.c_rows = (int)c_rows; p.stats = nullptr; }
   static LdsOptIn lds_opt_in;
   if (const int rc = lds_opt_in(LDS_BYTES, (const void*)gemm_n384_x3_kernel<false>, (const void*)gemm_n384_x3_kernel<true>)) return rc;
-  const int ncu = n384x3_num_cus(), nrb = ceil_div(g.M, BM);
-  const int grid = nrb < ncu ? nrb : ncu;
-  if (p.dbg) hipLaunchKernelGGL(gemm_n384_x3_kernel<true>, dim3(grid), dim3(256), LDS_BYTES, st, p);
-  else hipLaunchKernelGGL(gemm_n384_x3_kernel<false>, dim3(grid), dim3(256), LDS_BYTES, st, p);
-  WVN_LAUNCH_CHECK();
-  return WVN_OK;
+  return n384_launch(gemm_n384_x3_kernel<false>, gemm_n384_x3_kernel<true>, 256, LDS_BYTES, st, p);
 }
 
 // A: fragment-major planes ([2][ceil(M / 32)][K / 16][64 lanes][8], lo plane a_plane elements behind the hi plane); W: the packed weight of
@@ -917,21 +861,12 @@ int wvn_gemm_n384_x3_frag_launch(const GemmBf16Params& g, int epi, hipStream_t s
   if (g.A_lo <= g.A) return WVN_ERR_ARG;
   const size_t a_plane = (size_t)(g.A_lo - g.A), mpad = (size_t)(g.M + 31) / 32 * 32;
   if ((a_plane + mpad * g.K) * 2 >= (1ull << 32) || (size_t)g.M * g.ldc * 4 >= (1ull << 32) || (size_t)2 * NN * g.K * 2 >= (1ull << 31)) return WVN_ERR_ARG;
-  N384X3Params p{};
-  p.A = g.A; p.a_plane = a_plane; p.lda = g.K; p.W = g.W; p.w_plane = 0; p.ldw = g.K; p.bias = g.bias; p.ls = g.ls;
-  p.C = (float*)g.C; p.ldc = g.ldc; p.M = g.M; p.K = g.K; p.dbg = g.dbg; p.stats = g.ln_stats_out; p.eps = g.ln_eps;
+  const N384X3Params p = n384_params(g, a_plane, g.K, 0);
   static LdsOptIn lds_opt_in;
   if (const int rc = lds_opt_in(PAIR_LDS_BYTES, (const void*)gemm_n384_x3_frag_kernel<false>, (const void*)gemm_n384_x3_frag_kernel<true>,
                                 (const void*)gemm_n384_x3_frag_pair_kernel<false>, (const void*)gemm_n384_x3_frag_pair_kernel<true>)) return rc;
-  const int ncu = n384x3_num_cus(), nrb = ceil_div(g.M, BM);
-  const int grid = nrb < ncu ? nrb : ncu;
-  if (g_n384_pair) {
-    if (p.dbg) hipLaunchKernelGGL(gemm_n384_x3_frag_pair_kernel<true>, dim3(grid), dim3(512), PAIR_LDS_BYTES, st, p);
-    else hipLaunchKernelGGL(gemm_n384_x3_frag_pair_kernel<false>, dim3(grid), dim3(512), PAIR_LDS_BYTES, st, p);
-  } else if (p.dbg) hipLaunchKernelGGL(gemm_n384_x3_frag_kernel<true>, dim3(grid), dim3(256), LDS_BYTES, st, p);
-  else hipLaunchKernelGGL(gemm_n384_x3_frag_kernel<false>, dim3(grid), dim3(256), LDS_BYTES, st, p);
-  WVN_LAUNCH_CHECK();
-  return WVN_OK;
+  if (g_n384_pair) return n384_launch(gemm_n384_x3_frag_pair_kernel<false>, gemm_n384_x3_frag_pair_kernel<true>, 512, PAIR_LDS_BYTES, st, p);
+  return n384_launch(gemm_n384_x3_frag_kernel<false>, gemm_n384_x3_frag_kernel<true>, 256, LDS_BYTES, st, p);
 }
 // MX form (see gemm_n384_mx_pair_kernel): A = fragment-major fp16 plane (g.A) + the l8 plane (g.A_lo, behind g.A within 4 GB; the h8 operand is derived in
 // registers); W = backbone.pack_n384_mx's stage list (4 * 384 * K bytes).  K % 128 == 0.
@@ -944,24 +879,18 @@ int wvn_gemm_n384_mx_launch(const GemmBf16Params& g, int epi, hipStream_t st) {
   if (al < a0 + mpad * g.K * 2) return WVN_ERR_ARG;
   const uintptr_t top = al + mpad * g.K;
   if (top - a0 >= (1ull << 32) || (size_t)g.M * g.ldc * 4 >= (1ull << 32) || (size_t)4 * NN * g.K >= (1ull << 31)) return WVN_ERR_ARG;
-  N384X3Params p{};
-  p.A = g.A; p.a_plane = 0; p.lda = g.K; p.W = g.W; p.w_plane = 0; p.ldw = g.K; p.bias = g.bias; p.ls = g.ls;
-  p.C = (float*)g.C; p.ldc = g.ldc; p.M = g.M; p.K = g.K; p.dbg = g.dbg; p.stats = g.ln_stats_out; p.eps = g.ln_eps;
-  N384MXExtra ex{(unsigned)(al - a0)};
+  const N384X3Params p = n384_params(g, 0, g.K, 0);
+  const N384MXExtra ex{(unsigned)(al - a0)};
   static LdsOptIn lds_opt_in;
   if (const int rc = lds_opt_in(PAIR_LDS_BYTES, (const void*)gemm_n384_mx_pair_kernel<false>, (const void*)gemm_n384_mx_pair_kernel<true>,
                                 (const void*)gemm_n384_mx_pair_kernel<true, 1>, (const void*)gemm_n384_mx_pair_kernel<true, 2>,
                                 (const void*)gemm_n384_mx_pair_kernel<true, 3>, (const void*)gemm_n384_mx_pair_kernel<true, 4>)) return rc;
-  const int ncu = n384x3_num_cus(), nrb = ceil_div(g.M, BM);
-  const int grid = nrb < ncu ? nrb : ncu;
-  if (p.dbg && g_n384_mx_var == 1) hipLaunchKernelGGL((gemm_n384_mx_pair_kernel<true, 1>), dim3(grid), dim3(512), PAIR_LDS_BYTES, st, p, ex);
-  else if (p.dbg && g_n384_mx_var == 2) hipLaunchKernelGGL((gemm_n384_mx_pair_kernel<true, 2>), dim3(grid), dim3(512), PAIR_LDS_BYTES, st, p, ex);
-  else if (p.dbg && g_n384_mx_var == 3) hipLaunchKernelGGL((gemm_n384_mx_pair_kernel<true, 3>), dim3(grid), dim3(512), PAIR_LDS_BYTES, st, p, ex);
-  else if (p.dbg && g_n384_mx_var == 4) hipLaunchKernelGGL((gemm_n384_mx_pair_kernel<true, 4>), dim3(grid), dim3(512), PAIR_LDS_BYTES, st, p, ex);
-  else if (p.dbg) hipLaunchKernelGGL(gemm_n384_mx_pair_kernel<true>, dim3(grid), dim3(512), PAIR_LDS_BYTES, st, p, ex);
-  else hipLaunchKernelGGL(gemm_n384_mx_pair_kernel<false>, dim3(grid), dim3(512), PAIR_LDS_BYTES, st, p, ex);
-  WVN_LAUNCH_CHECK();
-  return WVN_OK;
+  void (*timed)(N384X3Params, N384MXExtra) = gemm_n384_mx_pair_kernel<true>;   // or the timing experiment selected by wvn_debug_n384_pair(16 + var)
+  if (g_n384_mx_var == 1) timed = gemm_n384_mx_pair_kernel<true, 1>;
+  else if (g_n384_mx_var == 2) timed = gemm_n384_mx_pair_kernel<true, 2>;
+  else if (g_n384_mx_var == 3) timed = gemm_n384_mx_pair_kernel<true, 3>;
+  else if (g_n384_mx_var == 4) timed = gemm_n384_mx_pair_kernel<true, 4>;
+  return n384_launch(gemm_n384_mx_pair_kernel<false>, timed, 512, PAIR_LDS_BYTES, st, p, ex);
 }
 void wvn_gemm_n384_x3_set_pair(int on) {
   if (on >= 16) { g_n384_mx_var = on - 16; return; }

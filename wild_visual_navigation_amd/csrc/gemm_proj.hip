@@ -134,17 +134,6 @@ __global__ __launch_bounds__(512, 1) void proj_resid_kernel(ProjParams p) {
   }
 }
 
-int proj_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace
 
 // Eligibility: N == K == 384, 16-byte aligned operands, 32-bit byte offsets, a CU count that is a multiple of 16 (the pairing of
@@ -154,7 +143,7 @@ int WVN_OPSYM(wvn_proj_resid_launch)(const op16_t* A, int lda, const op16_t* W, 
   if (!A || !W || !x || M <= 0 || (lda % 8) != 0 || (ldx % 4) != 0) return WVN_ERR_ARG;
   if ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)x) & 15) != 0) return WVN_ERR_ARG;
   if ((size_t)M * ldx * 4 >= (1ull << 32)) return WVN_ERR_ARG;
-  const int ncu = proj_num_cus();
+  const int ncu = wvn_num_cus();
   if (ncu % 16) return WVN_ERR_ARG;
   const int lds = TAB_OFF + 2 * NH * 4;
   static LdsOptIn lds_opt_in;   // per device (common.h)

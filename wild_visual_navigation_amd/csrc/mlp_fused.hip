@@ -730,17 +730,6 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(MlpFusedParams p) {
   }
 }
 
-int mlp_fused_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace
 
 // Eligibility: D == 384, F % 64 == 0 (F * 4 + 154,112 bytes of LDS), 16-byte aligned operands, 32-bit byte offsets.
@@ -776,7 +765,7 @@ static int mlp_fused_launch_impl(const op16_t* xn, int lda, const float* ln_g, c
   p.attn = attn; p.lda_attn = lda_attn; p.bp = bp; p.ls1 = ls1;
   p.Wp = Wp;
   p.nx_g = nx_g; p.nx_b = nx_b; p.nx_eps = nx_eps; p.xn_next = xn_next;
-  const int nrb = ceil_div(M, BM), ncu = mlp_fused_num_cus();
+  const int nrb = ceil_div(M, BM), ncu = wvn_num_cus();
   const dim3 grid(nrb < ncu ? nrb : ncu);
   p.dbg = WVN_OPSYM(g_mlp_fused_dbg);
   if (nxt) hipLaunchKernelGGL((mlp_fused_kernel<true, false, true, true, true>), grid, dim3(256), lds, st, p);

@@ -364,17 +364,6 @@ auto dispatch_D(int D, Fn f) -> decltype(f(Dim<384>{})) {
 }
 bool pix_supported(int D, int h1, int h2) { return (D == 384 || D == 768 || D == 90) && h1 == H1 && h2 == H2; }
 
-int pix_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t pr;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) n = pr.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 // what the caller asks for (the entry points' common arguments)
 PixParams pix_request(int B, int G, int out_h, int out_w, float mean, float std, float std_factor, const float* conf_state,
                       float* trav, float* conf, float* loss) {
@@ -399,7 +388,7 @@ int pix_launch(const PixParams& p, hipStream_t st) {
   static LdsOptIn lds_opt_in;   // per device (common.h)
   if (const int rc = lds_opt_in(F::LDS_BYTES, (const void*)kern)) return rc;
   const int ntiles = p.B * p.nty * p.ntx;
-  const int cap = F::WGS_PER_CU * pix_num_cus();
+  const int cap = F::WGS_PER_CU * wvn_num_cus();
   hipLaunchKernelGGL(kern, dim3(ntiles < cap ? ntiles : cap), dim3(512), F::LDS_BYTES, st, p);
   WVN_LAUNCH_CHECK();
   return WVN_OK;

@@ -416,17 +416,6 @@ __global__ __launch_bounds__(256, 1) void qkv_fused_kernel(QkvFusedParams p) {
   }
 }
 
-int qkv_fused_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace
 
 // Eligibility: D == 384 (heads == 6), ntok_s % 16 == 0, M % 16 == 0, npad % 16 == 0, q / k / v^T within 2 GB of each other.
@@ -453,7 +442,7 @@ int WVN_OPSYM(wvn_qkv_fused_launch)(const float* x, int ldx, const float* ln_g, 
   p.base = (op16_t*)lo; p.q_off = (unsigned)((uintptr_t)q - lo); p.k_off = (unsigned)((uintptr_t)k - lo); p.v_off = (unsigned)((uintptr_t)vt - lo);
   p.bytes = (unsigned)(hi - lo + one);
   p.heads = heads; p.npad = npad; p.ntok_s = ntok_s; p.q_scale = q_scale != 0.f ? q_scale : 1.f; p.M = M;
-  const int nrb = ceil_div(M, BM), ncu = qkv_fused_num_cus();
+  const int nrb = ceil_div(M, BM), ncu = wvn_num_cus();
   p.dbg = WVN_OPSYM(g_qkv_fused_dbg);
   const dim3 grid(nrb < ncu ? nrb : ncu);
   if (pre && p.dbg) hipLaunchKernelGGL((qkv_fused_kernel<true, true>), grid, dim3(256), lds, st, p);

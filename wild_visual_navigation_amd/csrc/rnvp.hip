@@ -131,7 +131,7 @@ int rnvp_launch(const RnvpCall& c, hipStream_t st) {
   auto kern = rnvp_kernel<D, HB, false>;
   static LdsOptIn lds_opt_in;   // per device (common.h)
   if (const int rc = lds_opt_in(G::LDS_BYTES, (const void*)kern)) return rc;
-  static const int cus = num_cus();
+  const int cus = wvn_num_cus();
   const long long ntiles = (c.R + TILE_ROWS - 1) / TILE_ROWS;
   hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < cus ? ntiles : cus)), dim3(NTHR), G::LDS_BYTES, st, k);
   WVN_LAUNCH_CHECK();

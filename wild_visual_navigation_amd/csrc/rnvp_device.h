@@ -305,14 +305,6 @@ auto dispatch(int D, int h, Fn f) -> decltype(f(Shape<384, 7>{})) {
   return decltype(f(Shape<384, 7>{})){};
 }
 
-inline int num_cus() {
-  int dev = 0;
-  hipDeviceProp_t pr;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-    return pr.multiProcessorCount;
-  return 256;
-}
-
 // the call's fields -> kernel arguments; WVN_ERR_ARG for a pixel source whose token count does not fit an int
 inline int fill_args(const RnvpCall& c, RnvpK& k) {
   k.blob = (const unsigned char*)c.packed;

@@ -368,7 +368,7 @@ int phase_a_launch(const RnvpCall& c, double* stats, void* ws, hipStream_t st) {
     auto kern = rnvp_kernel<D, HB, true>;
     static LdsOptIn lds_opt_in;   // per device (common.h)
     if (const int rc = lds_opt_in(G::LDS_BYTES, (const void*)kern)) return rc;
-    static const int cus = num_cus();
+    const int cus = wvn_num_cus();
     const long long ntiles = (c.R + TILE_ROWS - 1) / TILE_ROWS;
     hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < cus ? ntiles : cus)), dim3(NTHR), G::LDS_BYTES, st, k);
     WVN_LAUNCH_CHECK();
@@ -389,7 +389,7 @@ int phase_b_launch(int h, const void* packed, const void* tpacked, long long R, 
   auto kern = rnvp_bwd_kernel<D, HB>;
   static LdsOptIn lds_opt_in;
   if (const int rc = lds_opt_in(LDS, (const void*)kern)) return rc;
-  static const int cus = num_cus();
+  const int cus = wvn_num_cus();
   const BwdK b{(const unsigned char*)packed, (const unsigned char*)tpacked, (float*)ws, stats, R};
   hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < cus ? ntiles : cus)), dim3(NTHR), LDS, st, b);
   WVN_LAUNCH_CHECK();
