@@ -49,9 +49,10 @@ constexpr int BM = 128;
 constexpr int PIECES = SLICE_BYTES / 1024 / 4;  // 1 KB DMA pieces per wave and slice (8)
 static_assert(PIECES == 8, "one DMA piece per k-step of a slice");
 
-enum { X_GELU = 0, X_RESID = 1, X_QK = 2, X_V = 3, X_PLANES = 4, X_GELU_FRAG = 5, X_QK_F16 = 6, X_V_F16 = 7, X_QKV = 8, X_QKV_F16 = 9, X_HEAD = 10 };   // _F16: one fp16 plane per tensor
+// (the values are the kernels' names in profiles/: the gaps are retired forms)
+enum { X_GELU = 0, X_RESID = 1, X_PLANES = 4, X_GELU_FRAG = 5, X_QKV = 8, X_QKV_F16 = 9, X_HEAD = 10 };   // _F16: one fp16 plane per tensor
 // X_QKV / X_QKV_F16: q | k | v^T in ONE launch -- the column tiles of q and k run in the TR orientation, those of v^T in the other; a row
-// block's two planes (192 registers) are loaded once instead of twice (617 MB per launch at 128 frames) and there is one prologue / tail
+// block's two planes (192 registers) are loaded once and there is one prologue / tail
 // X_HEAD (LayerNorm on load only; tokens in the fp32 LayerNorm kernel's operation order, accumulators from zero and the bias behind them: bit-identical to that kernel + the tiled gemm_x3): the two products of the STEGO head that read the final-LayerNorm tokens, in ONE launch over the residual rows.  W = [W_hid (384 rows);
 // W_lin (zero-padded to 128 rows)], N = 512: column tiles 0 - 5 leave ReLU(.) as row-major hi / lo planes (the X_PLANES store), tiles 6 - 7 fp32 rows of a code buffer with a
 // padded row stride (the X_RESID image without the read of C).  The kernel's rows are PATCH rows r; only the load maps them to residual rows (r / npatch) * ntok_s + 1 + r % npatch
@@ -62,14 +63,16 @@ struct X384Params {
   const bf16_t* W; size_t w_plane;      // [2][N][384]: lo plane w_plane elements behind the hi plane
   const float* bias;
   void* C; void* C_lo; int ldc;         // planes (bf16) or fp32 (X_RESID: in/out; C_lo unused)
-  void* C_h8;                           // MX, X_GELU_FRAG: C = fp16 fragments, C_lo = the l8 plane, C_h8 = the h8 plane (gemm_n384_x3.hip's MX operand)
+                                        // MX, X_GELU_FRAG: C = fp16 fragments, C_lo = the l8 plane (gemm_n384_x3.hip's MX operand; it derives h8 itself)
+  void* pad8_;                          // (unused, as pad4_ below: they hold the offsets of the fields behind them.  Without them hipcc groups the kernels' scalar
+                                        //  argument loads differently and allocates other SGPRs in all 24 instantiations -- thousands of changed lines each)
   int M, N;
   int heads, npad, ntok_s;
   float q_scale;
-  int f16_out;                          // X_QK / X_V: 1 = ONE fp16 plane per tensor, 0 = hi / lo bf16 planes
-  int q_lo_f16;                         // with f16_out: q leaves as TWO fp16 planes (the second at qkv_base_lo + q_off)
+  int pad4_;
+  int q_lo_f16;                         // X_QKV_F16: q leaves as TWO fp16 planes (the second at qkv_base_lo + q_off)
   bf16_t* qkv_base; unsigned q_off, k_off, v_off, qkv_bytes;   // one buffer descriptor over q / k / v^T (hi planes or the fp16 planes)
-  bf16_t* qkv_base_lo;                  // the same span of the lo planes (f16_out == 0)
+  bf16_t* qkv_base_lo;                  // the same span of the lo planes (X_QKV), or of q's second plane
   const float* ls;                      // X_RESID: optional LayerScale
   long long* dbg;                       // TIMING builds: per wave {wait + barrier, DMA issue, MFMA steps (+ epilogue chunks), total} shader cycles
   // LNA: A = LayerNorm(ln_x) formed while the row block is loaded: ln_x fp32 [M][ln_ldx], ln_stats[m] = {mean, rstd} (left by the kernel
@@ -91,14 +94,42 @@ __device__ inline void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
 // four ds_read_b128.  W: plane 0 = fp16 [N][384]; plane 1 = bytes [N][768] in the chunk order the kernel reads them (backbone.pack_a384_mx).
 // The row block's operands stay resident: 24 fp16 fragments + 6 eight-register l8 operands = 144 registers; a_h8 = e5m2(a_h) is derived from the fp16 fragments once per
 // (slice, 64-k step) -- 16 conversions for two regions -- which is also what the row-panel consumer does with ITS activations (one definition of h8 for activations: e5m2(fp16(v))).
-#ifndef WVN_MXG
-#define WVN_MXG 12
-#endif
-constexpr int MXG = WVN_MXG;   // k-steps of fp32 rows requested at a time by the MX LayerNorm-on-load prologue (12: two HBM round trips per row block)
+constexpr int MXG = 12;   // k-steps of fp32 rows requested at a time by the MX LayerNorm-on-load prologue (12: two HBM round trips per row block)
 
 constexpr int X384_LDS_MAX = 160 * 1024;
 
-template <int EPI, bool TIMING = false, bool LNA = false, bool MX = false, bool BURST = false>
+// ---- pieces both kernels of this file are made of ----
+// The persistent, unit-balanced schedule (gemm_a384.hip): (row block, column tile) units in row-block-major order; workgroup b of n owns units
+// [U b / n, U (b + 1) / n).  unit_step: the row block of unit u and its column tiles [j0, j1) inside the workgroup's range.
+struct UnitRange { int begin, end; };
+struct UnitStep { int rb, j0, j1; };
+__device__ __forceinline__ UnitRange unit_range(int M, int NT) {
+  const int NRB = (M + BM - 1) / BM;
+  const long long U = (long long)NRB * NT;
+  return {(int)(U * blockIdx.x / gridDim.x), (int)(U * (blockIdx.x + 1) / gridDim.x)};
+}
+__device__ __forceinline__ UnitStep unit_step(int u, int u_end, int NT) {
+  const int rb = u / NT, j0 = u - rb * NT;
+  return {rb, j0, min(NT, j0 + (u_end - u))};
+}
+
+// GELU -> MX fragments.  Chunk s (0 .. 7) of a 32-column half of a TR tile = the accumulator pair (v0, v1) = columns 8 (s >> 1) + 4 hi + 2 (s & 1), + 1: after
+// the GELU its fp16 pair is dword s & 3 of the fp16 fragment being assembled (complete after every fourth chunk), the e5m2 pair of its rounding residues * 2^12
+// bytes 2 s, 2 s + 1 of the lane's 16-byte l8 half (complete after the eighth).  (No h8 plane: the consumer derives e5m2(h) in registers -- mx_e5m2_of_f16.)
+__device__ __forceinline__ void mx_gelu_chunk(float v0, float v1, int s, u32x4_t& fragh, u32x4_t& frag8l) {
+  typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
+  typedef __attribute__((ext_vector_type(2))) float f2_t;
+  gelu_pair(v0, v1);
+  const uint32_t h = pack_f16x2(v0, v1);
+  const h2_t hh = __builtin_bit_cast(h2_t, h);
+  fragh[s & 3] = h;
+  const f2_t res = f2_t{v0, v1} - f2_t{(float)hh[0], (float)hh[1]};   // one v_pk_add_f32 for the two residues
+  frag8l[s >> 1] = mx_pk8(frag8l[s >> 1], res[0], res[1], MX_RES_INV, s & 1);
+}
+// byte offset in the fragment-major fp16 / bf16 planes (header comment): the 1 KB fragment of the consumer's k-step ks for the 32-row group at m0w (N / 16 per group)
+__device__ __forceinline__ unsigned frag_offset(int m0w, int N, int ks) { return __builtin_amdgcn_readfirstlane((((m0w >> 5) * (N >> 4)) + ks) * 1024); }
+
+template <int EPI, bool TIMING = false, bool LNA = false, bool MX = false>
 __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
   static_assert(!MX || (LNA && (EPI == X_GELU_FRAG || EPI == X_QKV_F16)), "the MX form exists for the LayerNorm-on-load fc1 / QKV instantiations");
   static_assert(EPI != X_HEAD || (LNA && !MX), "the STEGO head reads the residual rows: LayerNorm on load, split bf16 operands");
@@ -109,10 +140,7 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
   const int NT = p.N / BNT;
-  // persistent, unit-balanced schedule (gemm_a384.hip): (row block, column tile) units in row-block-major order
-  const int NRB = (p.M + BM - 1) / BM;
-  const long long U = (long long)NRB * NT;
-  const int u_begin = (int)(U * blockIdx.x / gridDim.x), u_end = (int)(U * (blockIdx.x + 1) / gridDim.x);
+  const auto [u_begin, u_end] = unit_range(p.M, NT);
   const int total = (u_end - u_begin) * NSL;
   int m0w = 0;
   unsigned char* stg = smem + STG_OFF + wave * STG_BYTES;
@@ -267,12 +295,9 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
 
   // ---- epilogue addressing ----
   constexpr unsigned OOB = 0x80000000u;
-  constexpr bool MERGED = EPI == X_QKV || EPI == X_QKV_F16;   // q | k tiles (TR) and v^T tiles (!TR) in one launch: the orientation is the TILE's tag
-  constexpr bool IS_QKV = EPI == X_QK || EPI == X_QK_F16 || EPI == X_V || EPI == X_V_F16 || MERGED;
-  constexpr bool IS_V_ONLY = EPI == X_V || EPI == X_V_F16;
-  constexpr bool F16OUT = EPI == X_QK_F16 || EPI == X_V_F16 || EPI == X_QKV_F16;   // (compile-time: a run-time flag leaves branches in the slice loop)
-  using TRK = std::integral_constant<bool, !IS_V_ONLY>;
-  const int nqk = MERGED ? 2 * p.heads : (1 << 30);      // MERGED: column tiles below nqk are q | k (one head each), the rest v^T
+  constexpr bool IS_QKV = EPI == X_QKV || EPI == X_QKV_F16;   // q | k tiles (TR) and v^T tiles (!TR) in one launch: the orientation is the TILE's tag
+  constexpr bool F16OUT = EPI == X_QKV_F16;                   // (compile-time: a run-time flag leaves branches in the slice loop)
+  const int nqk = 2 * p.heads;                                // X_QKV*: column tiles below nqk are q | k (one head each), the rest v^T
   unsigned voff[2] = {0, 0};
   unsigned vt_off = 0, stg_rd = 0;
   const unsigned c_bytes = IS_QKV ? 0u : (unsigned)((size_t)(EPI == X_GELU_FRAG ? (p.M + 31) / 32 * 32 : p.M) * p.ldc * (EPI == X_RESID ? 4 : 2));
@@ -388,37 +413,24 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
       float v0 = prev[t][4 * g + h2], v1 = prev[t][4 * g + h2 + 1];
       if constexpr (TR) {
         const int c = 32 * t + 8 * g + 4 * hi + h2;
-        if constexpr (EPI == X_GELU || EPI == X_GELU_FRAG) gelu_pair(v0, v1);
         if constexpr (EPI == X_GELU_FRAG && MX) {
-          // part t fills half t of the tile's (= the consumer's 64-k step jp) e5m2 operands, chunk s its bytes 2 s, 2 s + 1; every fourth chunk completes
-          // one fp16 fragment (consumer k-step 4 jp + 2 t + (g >> 1)), the eighth the 16-byte halves
-          typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-          const uint32_t h = pack_f16x2(v0, v1);
-          const h2_t hh = __builtin_bit_cast(h2_t, h);
-          fragh[2 * (g & 1) + (h2 >> 1)] = h;
-          // (no h8 plane: the consumer derives e5m2(h) from the fp16 fragments in registers -- mx_operand.h: mx_e5m2_of_f16)
-          {
-            typedef __attribute__((ext_vector_type(2))) float f2_t;
-            const f2_t res = f2_t{v0, v1} - f2_t{(float)hh[0], (float)hh[1]};   // one v_pk_add_f32 for the two residues
-            frag8l[s >> 1] = mx_pk8(frag8l[s >> 1], res[0], res[1], MX_RES_INV, s & 1);
-          }
-          if ((s & 3) == 3) {
-            const unsigned so = __builtin_amdgcn_readfirstlane((((m0w >> 5) * (p.N >> 4)) + 4 * jp + 2 * t + (g >> 1)) * 1024);
-            wvn_store_b128_guarded(fragh, rs_c, lane * 16, so);
-          }
+          // part t = half t of the tile = of the consumer's 64-k step jp; its fragments are the consumer's k-steps 4 jp + 2 t, + 1
+          mx_gelu_chunk(v0, v1, s, fragh, frag8l);
+          if ((s & 3) == 3) wvn_store_b128_guarded(fragh, rs_c, lane * 16, frag_offset(m0w, p.N, 4 * jp + 2 * t + (g >> 1)));
           if (s == 7) {
             const unsigned so8 = __builtin_amdgcn_readfirstlane((((m0w >> 5) * (p.N >> 6)) + jp) * 2048 + t * 1024);
             wvn_store_b128_guarded(frag8l, rs_c2, lane * 16, so8);
           }
           return;
         }
+        if constexpr (EPI == X_GELU || EPI == X_GELU_FRAG) gelu_pair(v0, v1);
         if constexpr (EPI == X_GELU_FRAG) {
           uint32_t h, l;
           split2(v0, v1, h, l);
           const int e = 2 * (g & 1) + (h2 >> 1);            // dword of the lane's 16 bytes: elements j = 4 (g & 1) + h2, + 1
           fragh[e] = h; fragl[e] = l;
           if ((s & 3) == 3) {                                // the fragment of the consumer's k-step 4 jp + 2 t + (g >> 1) is complete
-            const unsigned so = __builtin_amdgcn_readfirstlane((((m0w >> 5) * (p.N >> 4)) + 4 * jp + 2 * t + (g >> 1)) * 1024);
+            const unsigned so = frag_offset(m0w, p.N, 4 * jp + 2 * t + (g >> 1));
             wvn_store_b128_guarded(fragh, rs_c, lane * 16, so);
             wvn_store_b128_guarded(fragl, rs_c2, lane * 16, so);
           }
@@ -502,7 +514,7 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
     } else if constexpr (IS_QKV && !TR) {
       const int it = s & 3, pl = s >> 2;
       if (pl == 1 && F16OUT) return;
-      const int head = (MERGED ? n0 - 2 * p.heads * 64 : n0) >> 6;
+      const int head = (n0 - 2 * p.heads * 64) >> 6;
       const u32x4_t val = *(const u32x4_t*)(stg + pl * 64 * 80 + ((lane >> 2) + it * 16) * 80 + (lane & 3) * 16);
       const unsigned so = __builtin_amdgcn_readfirstlane(p.v_off + (head * 64 + it * 16) * p.npad * 2);
       if (pl == 0) wvn_store_b128_guarded(val, rs_c, vt_off, so);
@@ -550,8 +562,6 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
   // VM queue at the boundary of slice i (oldest first): DMA(i) [requested in period i - 2], then DMA(i + 1); the stores of a tile
   // epilogue are issued in a ks == 2 period AFTER that period's DMA request, so they are the youngest operations at the next
   // boundary (ks == 0) only; everywhere else a wait for "all but the 8 youngest" covers them.
-  // VM operations of one part 2 per lane -- exactly, or a LOWER bound where it depends on a run-time flag (allowing more operations to
-  // stay outstanding than were issued would let DMA(i) itself slip through the wait)
   // VM operations an epilogue period issues per lane, exactly, or a LOWER bound where it depends on a run-time flag (allowing more
   // operations to stay outstanding than were issued would let DMA(i) itself slip through the wait).  ST2: the stores (and row fetches)
   // of part 2, in a ks == 2 period; ST01: the fragment stores of X_GELU_FRAG in the ks == 0 / 1 periods.
@@ -584,11 +594,6 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
     // MFMAs' shadow (<= 5 slots per 32-cycle MFMA): inside a region the issue order is pinned to MFMA, LDS read, VALU..., and the
     // regions keep the epilogue spread evenly over the slice (one region for the whole slice: the scheduler left the epilogue behind
     // the last MFMA)
-    if constexpr (BURST) {   // (MX experiment) the slice's eight DMA pieces in one burst behind the barrier instead of one per region
-#pragma unroll
-      for (int s = 0; s < 8; ++s) issue_piece(i + NS - 1, s);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     frag_read(i % NS, 0, 0);
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -598,7 +603,7 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
         if (s + 1 < 8) frag_read(i % NS, s + 1, (s & 1) ^ 1);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if constexpr (!BURST) issue_piece(i + NS - 1, s);
+      issue_piece(i + NS - 1, s);
       mfma_step(i % NS, ks, s, mtr);
       if constexpr (do_epi) epi_chunk(ks, j - 1, s, etr);
       if constexpr (MX) {   // three MFMAs per region (32 + 32 + 64 cycles): the other instructions in three groups, the largest behind the scaled MFMA
@@ -645,7 +650,7 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
 
   __syncthreads();
   for (int u = u_begin; u < u_end;) {
-    const int rb = u / NT, j0 = u - rb * NT, j1 = min(NT, j0 + (u_end - u));
+    const auto [rb, j0, j1] = unit_step(u, u_end, NT);
     m0w = rb * BM + wave * 32;
     if constexpr (TIMING) {   // (the row block's operand load -- LayerNorm on load: two HBM round trips + the conversions -- is booked under "DMA issue")
       const long long l0 = (long long)__builtin_amdgcn_s_memtime();
@@ -656,8 +661,8 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
       load_a();
     }
     if constexpr (IS_QKV) qkv_offsets();
-    if constexpr (MERGED) {
-      using T = std::true_type; using F = std::false_type;
+    using T = std::true_type; using F = std::false_type;
+    if constexpr (IS_QKV) {
       if (j0 < nqk) init_acc(j0, T{}); else init_acc(j0, F{});
       for (int j = j0; j < j1; ++j) {   // (tile's own orientation, the previous tile's for the epilogue riding in it, the next one's for the bias)
         if (j + 1 < nqk) tile(j, j - j0, j1, T{}, T{}, T{});
@@ -677,7 +682,6 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
           for (int c = 0; c < 8; ++c) epi_chunk(part, j1 - 1, c, F{});
       }
     } else if constexpr (HEAD) {
-      using T = std::true_type; using F = std::false_type;
       constexpr int NPL = KD / BNT;   // column tiles 0 .. 5: hidden planes; 6, 7: code rows.  The epilogue riding in tile j is tile j - 1's
       init_acc(j0, T{});
       for (int j = j0; j < j1; ++j) {
@@ -695,13 +699,13 @@ __global__ __launch_bounds__(256, 1) void gemm_a384_x3_kernel(X384Params p) {
 #pragma unroll
           for (int c = 0; c < 8; ++c) epi_chunk(part, j1 - 1, c, F{});
       }
-    } else {
-      init_acc(j0, TRK{});
-      for (int j = j0; j < j1; ++j) tile(j, j - j0, j1, TRK{}, TRK{}, TRK{});
+    } else {   // every tile TR
+      init_acc(j0, T{});
+      for (int j = j0; j < j1; ++j) tile(j, j - j0, j1, T{}, T{}, T{});
 #pragma unroll
       for (int part = 0; part < 3; ++part)
 #pragma unroll
-        for (int c = 0; c < 8; ++c) epi_chunk(part, j1 - 1, c, TRK{});
+        for (int c = 0; c < 8; ++c) epi_chunk(part, j1 - 1, c, T{});
     }
     u += j1 - j0;
   }
@@ -757,9 +761,7 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
   const int NT = p.N / S2_BN;
-  const int NRB = (p.M + BM - 1) / BM;
-  const long long U = (long long)NRB * NT;
-  const int u_begin = (int)(U * blockIdx.x / gridDim.x), u_end = (int)(U * (blockIdx.x + 1) / gridDim.x);
+  const auto [u_begin, u_end] = unit_range(p.M, NT);
   const int total = (u_end - u_begin) * S2_NSL;
   constexpr int BIAS_OFF2 = S2_RING;   // (no staging area: every epilogue stores from registers)
   const float* bias_l = (const float*)(smem + BIAS_OFF2);
@@ -826,7 +828,7 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
           y[4 + e] = fmaf(fmaf(u[2 * i + 1][e], a1, a0), g1[e], b1[e]);
         }
         u32x4_t hv;
-        uint32_t d8[2] = {0, 0};
+        uint32_t d8[2] = {0, 0};   // the l8 dwords of this k-step
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
@@ -932,22 +934,14 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
       for (int gg = 0; gg < 2; ++gg) {
         u32x4_t fragh;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {   // chunk s = 4 gg + c: g = s >> 1, h2 = (s & 1) * 2
-          const int s = 4 * gg + c, g = s >> 1, h2 = (s & 1) * 2;
-          float v0 = acc[4 * g + h2], v1 = acc[4 * g + h2 + 1];
-          gelu_pair(v0, v1);
-          typedef __attribute__((ext_vector_type(2))) _Float16 h2_t;
-          typedef __attribute__((ext_vector_type(2))) float f2_t;
-          const uint32_t h = pack_f16x2(v0, v1);
-          const h2_t hh = __builtin_bit_cast(h2_t, h);
-          fragh[2 * (g & 1) + (h2 >> 1)] = h;
-          const f2_t res = f2_t{v0, v1} - f2_t{(float)hh[0], (float)hh[1]};
-          frag8l[s >> 1] = mx_pk8(frag8l[s >> 1], res[0], res[1], MX_RES_INV, s & 1);
+        for (int c = 0; c < 4; ++c) {   // chunk s = 4 gg + c: accumulators 2 s, 2 s + 1
+          const int s = 4 * gg + c;
+          mx_gelu_chunk(acc[2 * s], acc[2 * s + 1], s, fragh, frag8l);
         }
-        const unsigned so = __builtin_amdgcn_readfirstlane((((m0w >> 5) * (p.N >> 4)) + 4 * jp + 2 * t + gg) * 1024);
+        const unsigned so = __builtin_amdgcn_readfirstlane((((m0w >> 5) * (p.N >> 4)) + 4 * jp + 2 * t + gg) * 1024);   // (as frag_offset, in the association hipcc compiled before)
         wvn_store_b128_guarded(fragh, rs_c, l16, so);
       }
-      const unsigned so8 = __builtin_amdgcn_readfirstlane((((m0w >> 5) * (p.N >> 6)) + jp) * 2048 + t * 1024);
+      const unsigned so8 = __builtin_amdgcn_readfirstlane((((m0w >> 5) * (p.N >> 6)) + jp) * 2048 + t * 1024);   // half t of the 2 KB l8 block of 64-k step jp (N / 64 per group)
       wvn_store_b128_guarded(frag8l, rs_c2, l16, so8);
     } else if constexpr (TR) {
       // a q | k tile = half a head's dims (64 B) of 32 tokens.  Lane (token row l31, half hi) holds dims 8 g + 4 hi + e, that is words 4 g + 2 hi + {0, 1} of
@@ -1008,7 +1002,7 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
   // requests of slice i + 2 riding along, then the wait for this wave's pieces of slice i + 1 -- BEFORE the epilogue's stores are issued, so the queue at the
   // wait is exactly DMA(i + 1), DMA(i + 2) whatever follows (pieces are requested unconditionally; past the workgroup's last slice the cursor wraps to valid
   // rows and the data lands in a slot nobody reads again) ----
-  long long t_bar = 0, t_loop = 0, t_epi = 0, t_pro = 0;
+  long long t_bar = 0, t_loop = 0, t_pro = 0;
   const long long t_start = TIMING ? (long long)__builtin_amdgcn_s_memtime() : 0;
   auto period = [&](int i, int ks, auto tr_tag) __attribute__((always_inline)) {
     long long c0 = 0, c1 = 0, c2 = 0;
@@ -1037,15 +1031,13 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
 #pragma unroll
     for (int ks = 0; ks < S2_NSL; ++ks) period(si + ks, ks, tr_tag);
     si += S2_NSL;
-    const long long e0 = TIMING ? (long long)__builtin_amdgcn_s_memtime() : 0;
     epilogue(j, tr_tag);
     if (!last) init_acc(j + 1, next_tr);
-    if constexpr (TIMING) t_epi += (long long)__builtin_amdgcn_s_memtime() - e0;
   };
 
   __syncthreads();
   for (int u = u_begin; u < u_end;) {
-    const int rb = u / NT, j0 = u - rb * NT, j1 = min(NT, j0 + (u_end - u));
+    const auto [rb, j0, j1] = unit_step(u, u_end, NT);
     m0w = rb * BM + wave * 32;
     const long long l0 = TIMING ? (long long)__builtin_amdgcn_s_memtime() : 0;
     load_a();
@@ -1077,59 +1069,78 @@ __global__ __launch_bounds__(256, 2) void gemm_a384_mx2_kernel(X384Params p) {
     if (lane == 0 && p.dbg) {
       long long* d = p.dbg + ((size_t)blockIdx.x * 4 + wave) * 4;
       d[0] = t_bar; d[1] = t_pro; d[2] = t_loop; d[3] = (long long)__builtin_amdgcn_s_memtime() - t_start;
-      (void)t_epi;
     }
   }
 }
 
-bool g_x384_split_qkv = getenv("WVN_X384_SPLIT_QKV") != nullptr;   // A/B: q | k and v^T as two launches (the form before the merged kernel)
-
-// persistent grid: per_cu workgroups per CU, never more than there are (row block, column tile) units
-int x384_grid(long long units, int per_cu = 1) {
-  const long long cap = (long long)per_cu * wvn_num_cus();
-  return (int)(units < cap ? units : cap);
+// ---- eligibility, stated once for the launchers below ----
+// LayerNorm on load: the fp32 rows in 16-byte pieces, {mean, rstd} pairs, gamma and beta
+bool ln_on_load_ok(const X384Params& p) {
+  return p.ln_x && p.ln_stats && p.ln_g && p.ln_b && (p.ln_ldx % 4) == 0 && !((uintptr_t)p.ln_x & 15) && !((uintptr_t)p.ln_stats & 7);
+}
+// the weight as two stacked planes [2][N][384] (MX: two images), 16-byte aligned, the second behind the first, one descriptor over both
+bool w_planes_ok(const bf16_t* W, const bf16_t* W_lo, int N) {
+  return W && W_lo && !(((uintptr_t)W | (uintptr_t)W_lo) & 15) && W_lo > W && (size_t)(W_lo - W) + (size_t)N * KD < (1ull << 30);
+}
+// EPI_GELU_FRAG: two fragment-major planes of ceil(M / 32) * 32 rows, ldc == N (see the header comment)
+bool frag_out_ok(const GemmBf16Params& g) {
+  return g.C && g.C_lo && g.ldc == g.N && !(((uintptr_t)g.C | (uintptr_t)g.C_lo) & 15) && ((size_t)g.M + 32) * g.ldc * 2 < (1ull << 31);
+}
+// EPI_QKV: q | k | v^T go through ONE buffer descriptor -- base = the lowest of the three, byte offsets from it, the span to the end of the highest.
+// g.qkv_f16: one fp16 plane per tensor, and with g.q_lo a second plane of q alone, addressed at q's offset from a base of its own;
+// otherwise hi / lo bf16 planes, the lo planes at the same distances from THEIR base.  false: not eligible (p is not launched then).
+bool qkv_out_fill(X384Params& p, const GemmBf16Params& g) {
+  if (g.N != 3 * g.heads * 64 || !g.q || !g.k || !g.vt || (g.ntok_s % 16) || (g.M % 16) || (g.npad % 16)) return false;
+  if (!g.qkv_f16 && (!g.q_lo || !g.k_lo || !g.vt_lo)) return false;
+  const uintptr_t lo = std::min({(uintptr_t)g.q, (uintptr_t)g.k, (uintptr_t)g.vt});
+  const uintptr_t hi = std::max({(uintptr_t)g.q, (uintptr_t)g.k, (uintptr_t)g.vt});
+  const size_t one = (size_t)(g.M / (g.ntok_s > 0 ? g.ntok_s : 1)) * g.heads * g.npad * 64 * 2;
+  if (hi - lo + one >= (1ull << 31)) return false;
+  p.qkv_base = (bf16_t*)lo; p.q_off = (unsigned)((uintptr_t)g.q - lo); p.k_off = (unsigned)((uintptr_t)g.k - lo);
+  p.v_off = (unsigned)((uintptr_t)g.vt - lo); p.qkv_bytes = (unsigned)(hi - lo + one);
+  if (g.qkv_f16 && g.q_lo) {
+    if ((uintptr_t)g.q_lo < p.q_off) return false;
+    p.qkv_base_lo = (bf16_t*)((uintptr_t)g.q_lo - p.q_off);
+    p.q_lo_f16 = 1;
+  }
+  if (!g.qkv_f16) {
+    const uintptr_t lo2 = std::min({(uintptr_t)g.q_lo, (uintptr_t)g.k_lo, (uintptr_t)g.vt_lo});
+    if ((uintptr_t)g.q_lo - lo2 != p.q_off || (uintptr_t)g.k_lo - lo2 != p.k_off || (uintptr_t)g.vt_lo - lo2 != p.v_off) return false;
+    p.qkv_base_lo = (bf16_t*)lo2;
+  }
+  return true;
 }
 
+// One launch of a kernel pair (plain, TIMING; timed == nullptr: the pair has no TIMING instantiation and p.dbg is ignored): the pair's LDS opt-in
+// (ONE LdsOptIn per pair, the caller's), the persistent grid -- per_cu workgroups per CU, never more than there are (row block, column tile)
+// units of tile_cols columns -- and the launch.  WVN_ERR_ARG, before anything else, where the tables do not fit.
+using X384Kernel = void (*)(X384Params);
+int x384_launch(LdsOptIn& opt_in, X384Kernel plain, X384Kernel timed, int lds, int lds_max, int tile_cols, int per_cu, hipStream_t st, const X384Params& p) {
+  if (lds > lds_max) return WVN_ERR_ARG;
+  if (const int rc = timed ? opt_in(lds_max, (const void*)plain, (const void*)timed) : opt_in(lds_max, (const void*)plain)) return rc;
+  const long long units = (long long)ceil_div(p.M, BM) * (p.N / tile_cols), cap = (long long)per_cu * wvn_num_cus();
+  hipLaunchKernelGGL(p.dbg && timed ? timed : plain, dim3((int)(units < cap ? units : cap)), dim3(256), lds, st, p);
+  WVN_LAUNCH_CHECK();
+  return WVN_OK;
+}
+
+// (MX form 1: the one-wave-per-SIMD kernel)
 template <int EPI>
 int launch_mx(const X384Params& p, hipStream_t st) {
-  if (!p.ln_x || !p.ln_stats || !p.ln_g || !p.ln_b || (p.ln_ldx % 4) || ((uintptr_t)p.ln_x & 15) || ((uintptr_t)p.ln_stats & 7)) return WVN_ERR_ARG;
-  const int lds = BIAS_OFF + p.N * 4 + 2 * KD * 4;
-  if (lds > X384_LDS_MAX) return WVN_ERR_ARG;
-  static LdsOptIn lds_opt_in;
-  if (const int rc = lds_opt_in(X384_LDS_MAX, (const void*)gemm_a384_x3_kernel<EPI, false, true, true>, (const void*)gemm_a384_x3_kernel<EPI, true, true, true>)) return rc;
-  const long long units = (long long)ceil_div(p.M, BM) * (p.N / BNT);
-  const int grid = x384_grid(units);
-  static const bool burst = getenv("WVN_A384_MX_BURST") != nullptr;
-  if (burst) {
-    static LdsOptIn lds_opt_in_b;
-    if (const int rc = lds_opt_in_b(X384_LDS_MAX, (const void*)gemm_a384_x3_kernel<EPI, false, true, true, true>, (const void*)gemm_a384_x3_kernel<EPI, true, true, true, true>)) return rc;
-    if (p.dbg) hipLaunchKernelGGL((gemm_a384_x3_kernel<EPI, true, true, true, true>), dim3(grid), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((gemm_a384_x3_kernel<EPI, false, true, true, true>), dim3(grid), dim3(256), lds, st, p);
-    WVN_LAUNCH_CHECK();
-    return WVN_OK;
-  }
-  if (p.dbg) hipLaunchKernelGGL((gemm_a384_x3_kernel<EPI, true, true, true>), dim3(grid), dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((gemm_a384_x3_kernel<EPI, false, true, true>), dim3(grid), dim3(256), lds, st, p);
-  WVN_LAUNCH_CHECK();
-  return WVN_OK;
+  if (!ln_on_load_ok(p)) return WVN_ERR_ARG;
+  static LdsOptIn opt_in;
+  return x384_launch(opt_in, gemm_a384_x3_kernel<EPI, false, true, true>, gemm_a384_x3_kernel<EPI, true, true, true>, BIAS_OFF + p.N * 4 + 2 * KD * 4, X384_LDS_MAX,
+                     BNT, 1, st, p);
 }
 
-// (form 2: the two-workgroups-per-CU kernel; its weight image lies N * 1536 bytes behind the first one -- backbone.pack_a384_mx)
+// (MX form 2: the two-workgroups-per-CU kernel; its weight image lies N * 1536 bytes behind the first one -- backbone.pack_a384_mx)
 template <int EPI>
 int launch_mx2(X384Params p, hipStream_t st) {
-  if (!p.ln_x || !p.ln_stats || !p.ln_g || !p.ln_b || (p.ln_ldx % 4) || ((uintptr_t)p.ln_x & 15) || ((uintptr_t)p.ln_stats & 7)) return WVN_ERR_ARG;
+  if (!ln_on_load_ok(p)) return WVN_ERR_ARG;
   p.W = (const bf16_t*)((const unsigned char*)p.W + (size_t)p.N * KD * 4);
-  const int lds = S2_RING + p.N * 4 + 2 * KD * 4;   // the ring, the bias, the LayerNorm gain and shift: 57 KB (fc1) / 55.5 KB (q | k | v^T)
-  if (lds > 80 * 1024) return WVN_ERR_ARG;
-  static LdsOptIn lds_opt_in;
-  if (const int rc = lds_opt_in(80 * 1024, (const void*)gemm_a384_mx2_kernel<EPI>, (const void*)gemm_a384_mx2_kernel<EPI, true>)) return rc;
-  const long long units = (long long)ceil_div(p.M, BM) * (p.N / S2_BN);
-  static const bool one_per_cu = getenv("WVN_A384_MX2_ONE") != nullptr;   // (experiment: one workgroup per CU -- what a wave does when it has its SIMD to itself)
-  const int grid = x384_grid(units, one_per_cu ? 1 : 2);
-  if (p.dbg) hipLaunchKernelGGL((gemm_a384_mx2_kernel<EPI, true>), dim3(grid), dim3(256), lds, st, p);   // (dbg: 2 x CUs x 4 waves x 4 counters)
-  else hipLaunchKernelGGL((gemm_a384_mx2_kernel<EPI>), dim3(grid), dim3(256), lds, st, p);
-  WVN_LAUNCH_CHECK();
-  return WVN_OK;
+  static LdsOptIn opt_in;
+  // LDS: the ring, the bias, the LayerNorm gain and shift: 57 KB (fc1) / 55.5 KB (q | k | v^T); dbg: 2 x CUs x 4 waves x 4 counters
+  return x384_launch(opt_in, gemm_a384_mx2_kernel<EPI>, gemm_a384_mx2_kernel<EPI, true>, S2_RING + p.N * 4 + 2 * KD * 4, 80 * 1024, S2_BN, 2, st, p);
 }
 
 // 0 (default) / 2: the two-workgroups-per-CU kernel (fc1 9 %, q | k | v^T 5 - 8 % faster); 1: the one-wave-per-SIMD kernel
@@ -1139,26 +1150,23 @@ template <int EPI>
 int launch(const X384Params& p, hipStream_t st) {
   constexpr bool CAN_LNA = EPI == X_QKV || EPI == X_QKV_F16 || EPI == X_GELU_FRAG;   // (the LayerNorm-on-load form exists where the block kernels use it)
   const bool lna = p.ln_x != nullptr;
-  if (lna && (!CAN_LNA || !p.ln_stats || !p.ln_g || !p.ln_b || (p.ln_ldx % 4) || ((uintptr_t)p.ln_x & 15) || ((uintptr_t)p.ln_stats & 7))) return WVN_ERR_ARG;
+  if (lna && (!CAN_LNA || !ln_on_load_ok(p))) return WVN_ERR_ARG;
   const int lds = BIAS_OFF + p.N * 4 + (lna ? 2 * KD * 4 : 0);
-  if (lds > X384_LDS_MAX) return WVN_ERR_ARG;
-  static LdsOptIn lds_opt_in;
-  if (const int rc = lds_opt_in(X384_LDS_MAX, (const void*)gemm_a384_x3_kernel<EPI>, (const void*)gemm_a384_x3_kernel<EPI, true>)) return rc;
-  const long long units = (long long)ceil_div(p.M, BM) * (p.N / BNT);
-  const int grid = x384_grid(units);
-  if constexpr (CAN_LNA) {
-    if (lna) {
-      static LdsOptIn lds_opt_in_lna;
-      if (const int rc = lds_opt_in_lna(X384_LDS_MAX, (const void*)gemm_a384_x3_kernel<EPI, false, true>)) return rc;
-      hipLaunchKernelGGL((gemm_a384_x3_kernel<EPI, false, true>), dim3(grid), dim3(256), lds, st, p);
-      WVN_LAUNCH_CHECK();
-      return WVN_OK;
-    }
-  }
-  if (p.dbg) hipLaunchKernelGGL((gemm_a384_x3_kernel<EPI, true>), dim3(grid), dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((gemm_a384_x3_kernel<EPI>), dim3(grid), dim3(256), lds, st, p);
-  WVN_LAUNCH_CHECK();
-  return WVN_OK;
+  static LdsOptIn opt_in, opt_in_lna;
+  if constexpr (CAN_LNA)
+    if (lna) return x384_launch(opt_in_lna, gemm_a384_x3_kernel<EPI, false, true>, nullptr, lds, X384_LDS_MAX, BNT, 1, st, p);
+  return x384_launch(opt_in, gemm_a384_x3_kernel<EPI>, gemm_a384_x3_kernel<EPI, true>, lds, X384_LDS_MAX, BNT, 1, st, p);
+}
+
+// what both public launchers take over from the caller's descriptor as it stands (the output fields follow per epilogue)
+X384Params x384_params(const GemmBf16Params& g) {
+  X384Params p{};
+  p.A = g.A; p.A_lo = g.A_lo; p.lda = g.lda; p.W = g.W; p.w_plane = (size_t)(g.W_lo - g.W); p.bias = g.bias;
+  p.C = g.C; p.C_lo = g.C_lo; p.ldc = g.ldc; p.M = g.M; p.N = g.N;
+  p.heads = g.heads; p.npad = g.npad; p.ntok_s = g.ntok_s; p.q_scale = g.q_scale != 0.f ? g.q_scale : 1.f;
+  p.ls = g.ls; p.dbg = g.dbg;
+  p.ln_x = g.ln_x; p.ln_ldx = g.ln_ldx; p.ln_stats = g.ln_stats; p.ln_g = g.ln_g; p.ln_b = g.ln_b;
+  return p;
 }
 
 }  // namespace
@@ -1167,59 +1175,23 @@ int launch(const X384Params& p, hipStream_t st) {
 // WVN_ERR_ARG otherwise (the caller uses the tiled gemm_x3 kernel).  Worth it from about a chip of 128-row blocks on.
 int wvn_gemm_a384_x3_launch(const GemmBf16Params& g, int epi, hipStream_t st) {
   const bool lna = g.ln_x != nullptr;   // A = LayerNorm(ln_x) on load: the A planes are not read
-  if (g.K != KD || g.ldw != KD || (g.N % BNT) != 0 || g.M <= 0 || !g.W || !g.W_lo) return WVN_ERR_ARG;
+  if (g.K != KD || g.ldw != KD || (g.N % BNT) != 0 || g.M <= 0 || !w_planes_ok(g.W, g.W_lo, g.N)) return WVN_ERR_ARG;
   if (!lna && (!g.A || !g.A_lo || (g.lda % 8) != 0 || (((uintptr_t)g.A | (uintptr_t)g.A_lo) & 15))) return WVN_ERR_ARG;
-  if (((uintptr_t)g.W | (uintptr_t)g.W_lo) & 15) return WVN_ERR_ARG;
-  if (g.W_lo <= g.W || (size_t)(g.W_lo - g.W) + (size_t)g.N * KD >= (1ull << 30)) return WVN_ERR_ARG;   // one descriptor over both planes
-  X384Params p{};
-  p.A = g.A; p.A_lo = g.A_lo; p.lda = g.lda; p.W = g.W; p.w_plane = (size_t)(g.W_lo - g.W); p.bias = g.bias;
-  p.C = g.C; p.C_lo = g.C_lo; p.ldc = g.ldc; p.M = g.M; p.N = g.N;
-  p.heads = g.heads; p.npad = g.npad; p.ntok_s = g.ntok_s; p.q_scale = g.q_scale != 0.f ? g.q_scale : 1.f; p.f16_out = g.qkv_f16;
-  p.ls = g.ls; p.dbg = g.dbg;
-  p.ln_x = g.ln_x; p.ln_ldx = g.ln_ldx; p.ln_stats = g.ln_stats; p.ln_g = g.ln_g; p.ln_b = g.ln_b;
+  X384Params p = x384_params(g);
   switch (epi) {
     case EPI_GELU_BF16:
+    case EPI_BF16:   // row-major hi / lo planes
       if (!g.C || !g.C_lo || (g.ldc % 8) != 0 || (((uintptr_t)g.C | (uintptr_t)g.C_lo) & 15) || (size_t)g.M * g.ldc * 2 >= (1ull << 31)) return WVN_ERR_ARG;
-      return launch<X_GELU>(p, st);
-    case EPI_GELU_FRAG:   // fragment-major planes (see the header comment); C / C_lo hold ceil(M / 32) * 32 rows, ldc == N
-      if (!g.C || !g.C_lo || g.ldc != g.N || (((uintptr_t)g.C | (uintptr_t)g.C_lo) & 15) || ((size_t)g.M + 32) * g.ldc * 2 >= (1ull << 31)) return WVN_ERR_ARG;
-      return launch<X_GELU_FRAG>(p, st);
-    case EPI_BF16:
-      if (!g.C || !g.C_lo || (g.ldc % 8) != 0 || (((uintptr_t)g.C | (uintptr_t)g.C_lo) & 15) || (size_t)g.M * g.ldc * 2 >= (1ull << 31)) return WVN_ERR_ARG;
-      return launch<X_PLANES>(p, st);
+      return epi == EPI_BF16 ? launch<X_PLANES>(p, st) : launch<X_GELU>(p, st);
+    case EPI_GELU_FRAG:
+      return frag_out_ok(g) ? launch<X_GELU_FRAG>(p, st) : WVN_ERR_ARG;
     case EPI_RESID_F32:
     case EPI_ACCUM_F32:
       if (!g.C || (g.ldc % 4) != 0 || ((uintptr_t)g.C & 15) || (size_t)g.M * g.ldc * 4 >= (1ull << 31)) return WVN_ERR_ARG;
       return launch<X_RESID>(p, st);
-    case EPI_QKV: {
-      if (g.N != 3 * g.heads * 64 || !g.q || !g.k || !g.vt || (g.ntok_s % 16) || (g.M % 16) || (g.npad % 16)) return WVN_ERR_ARG;
-      if (!g.qkv_f16 && (!g.q_lo || !g.k_lo || !g.vt_lo)) return WVN_ERR_ARG;
-      const uintptr_t lo = std::min({(uintptr_t)g.q, (uintptr_t)g.k, (uintptr_t)g.vt});
-      const uintptr_t hi = std::max({(uintptr_t)g.q, (uintptr_t)g.k, (uintptr_t)g.vt});
-      const size_t one = (size_t)(g.M / (g.ntok_s > 0 ? g.ntok_s : 1)) * g.heads * g.npad * 64 * 2;
-      if (hi - lo + one >= (1ull << 31)) return WVN_ERR_ARG;
-      p.qkv_base = (bf16_t*)lo; p.q_off = (unsigned)((uintptr_t)g.q - lo); p.k_off = (unsigned)((uintptr_t)g.k - lo);
-      p.v_off = (unsigned)((uintptr_t)g.vt - lo); p.qkv_bytes = (unsigned)(hi - lo + one);
-      if (g.qkv_f16 && g.q_lo) {   // two-plane fp16 q: only q's second plane exists
-        if ((uintptr_t)g.q_lo < p.q_off) return WVN_ERR_ARG;
-        p.qkv_base_lo = (bf16_t*)((uintptr_t)g.q_lo - p.q_off);
-        p.q_lo_f16 = 1;
-      }
-      if (!g.qkv_f16) {   // the lo planes must sit at the same distances from their base
-        const uintptr_t lo2 = std::min({(uintptr_t)g.q_lo, (uintptr_t)g.k_lo, (uintptr_t)g.vt_lo});
-        if ((uintptr_t)g.q_lo - lo2 != p.q_off || (uintptr_t)g.k_lo - lo2 != p.k_off || (uintptr_t)g.vt_lo - lo2 != p.v_off) return WVN_ERR_ARG;
-        p.qkv_base_lo = (bf16_t*)lo2;
-      }
-      const int D = g.heads * 64;
-      if (!g_x384_split_qkv || lna) return g.qkv_f16 ? launch<X_QKV_F16>(p, st) : launch<X_QKV>(p, st);   // (p.N == 3 D: q | k | v^T in one launch)
-      p.N = 2 * D;
-      const int rc = g.qkv_f16 ? launch<X_QK_F16>(p, st) : launch<X_QK>(p, st);
-      if (rc != WVN_OK) return rc;
-      p.W = g.W + (size_t)2 * D * KD;
-      p.bias = g.bias ? g.bias + 2 * D : nullptr;
-      p.N = D;
-      return g.qkv_f16 ? launch<X_V_F16>(p, st) : launch<X_V>(p, st);
-    }
+    case EPI_QKV:
+      if (!qkv_out_fill(p, g)) return WVN_ERR_ARG;
+      return g.qkv_f16 ? launch<X_QKV_F16>(p, st) : launch<X_QKV>(p, st);
     default: return WVN_ERR_ARG;
   }
 }
@@ -1230,11 +1202,9 @@ int wvn_gemm_a384_x3_launch(const GemmBf16Params& g, int epi, hipStream_t st) {
 int wvn_gemm_a384_head_launch(const float* x, int ldx, const float* stats, const float* g, const float* b, const bf16_t* W, const bf16_t* W_lo, const float* bias,
                               bf16_t* hid, bf16_t* hid_lo, float* code, int ld_code, int frames, int npatch, int ntok_s, hipStream_t st) {
   constexpr int N = KD + 2 * BNT;
-  if (!x || !stats || !g || !b || !W || !W_lo || !bias || !hid || !hid_lo || !code) return WVN_ERR_ARG;
-  if (frames <= 0 || npatch <= 0 || ntok_s <= npatch || (ldx % 4) || ldx < KD || (ld_code % 4) || ld_code < 2 * BNT) return WVN_ERR_ARG;
-  if (((uintptr_t)x | (uintptr_t)W | (uintptr_t)W_lo | (uintptr_t)hid | (uintptr_t)hid_lo | (uintptr_t)code) & 15) return WVN_ERR_ARG;
-  if ((uintptr_t)stats & 7) return WVN_ERR_ARG;
-  if (W_lo <= W || (size_t)(W_lo - W) + (size_t)N * KD >= (1ull << 30)) return WVN_ERR_ARG;   // one descriptor over both planes
+  if (!w_planes_ok(W, W_lo, N) || !bias || !hid || !hid_lo || !code) return WVN_ERR_ARG;
+  if (frames <= 0 || npatch <= 0 || ntok_s <= npatch || ldx < KD || (ld_code % 4) || ld_code < 2 * BNT) return WVN_ERR_ARG;
+  if (((uintptr_t)hid | (uintptr_t)hid_lo | (uintptr_t)code) & 15) return WVN_ERR_ARG;
   const long long M = (long long)frames * npatch;
   if (M * KD * 2 >= (1ll << 31) || M * ld_code * 4 >= (1ll << 31)) return WVN_ERR_ARG;
   X384Params p{};
@@ -1242,52 +1212,29 @@ int wvn_gemm_a384_head_launch(const float* x, int ldx, const float* stats, const
   p.C = hid; p.C_lo = hid_lo; p.ldc = KD; p.M = (int)M; p.N = N; p.q_scale = 1.f;
   p.ntok_s = ntok_s; p.npatch = npatch; p.code = code; p.ld_code = ld_code;
   p.ln_x = x; p.ln_ldx = ldx; p.ln_stats = stats; p.ln_g = g; p.ln_b = b;
-  const int lds = BIAS_OFF + N * 4 + 2 * KD * 4;
+  if (!ln_on_load_ok(p)) return WVN_ERR_ARG;
   static_assert(BIAS_OFF + N * 4 + 2 * KD * 4 <= X384_LDS_MAX, "ring + staging + bias / gamma / beta tables");
-  static LdsOptIn lds_opt_in;
-  if (const int rc = lds_opt_in(X384_LDS_MAX, (const void*)gemm_a384_x3_kernel<X_HEAD, false, true>)) return rc;
-  const long long units = (long long)ceil_div(p.M, BM) * (N / BNT);
-  const int grid = x384_grid(units);
-  hipLaunchKernelGGL((gemm_a384_x3_kernel<X_HEAD, false, true>), dim3(grid), dim3(256), lds, st, p);
-  WVN_LAUNCH_CHECK();
-  return WVN_OK;
+  static LdsOptIn opt_in;
+  return x384_launch(opt_in, gemm_a384_x3_kernel<X_HEAD, false, true>, nullptr, BIAS_OFF + N * 4 + 2 * KD * 4, X384_LDS_MAX, BNT, 1, st, p);
 }
 
 void wvn_gemm_a384_mx_set_form(int form) { g_a384_mx_form = form == 1 || form == 2 ? form : 0; }
 
 // MX form (LayerNorm on load only): W = backbone.pack_a384_mx (plane 0 fp16 [N][384] at g.W, plane 1 bytes [N][768] at g.W_lo, the slice-major image of the
-// two-workgroups-per-CU kernel behind them; WVN_A384_MX_FORM=1 / wvn_gemm_a384_mx_set_form(1): the one-wave-per-SIMD kernel; a cycle-counter request takes it too); EPI_GELU_FRAG writes the
-// MX operand planes of gemm_n384_x3.hip's MX kernel (g.C fp16 fragments, g.C_lo = l8; h8 is derived by the consumer), EPI_QKV the fp16 q (| q_lo) | k | v^T planes.
+// two-workgroups-per-CU kernel behind them; WVN_A384_MX_FORM=1 / wvn_gemm_a384_mx_set_form(1): the one-wave-per-SIMD kernel; either form has its cycle-counter build);
+// EPI_GELU_FRAG writes the MX operand planes of gemm_n384_x3.hip's MX kernel (g.C fp16 fragments, g.C_lo = l8; h8 is derived by the consumer), EPI_QKV the fp16
+// q (| q_lo) | k | v^T planes.
 int wvn_gemm_a384_mx_launch(const GemmBf16Params& g, int epi, hipStream_t st) {
-  if (!g.ln_x || g.K != KD || g.ldw != KD || (g.N % BNT) != 0 || g.M <= 0 || !g.W || !g.W_lo) return WVN_ERR_ARG;
-  if (((uintptr_t)g.W | (uintptr_t)g.W_lo) & 15) return WVN_ERR_ARG;
-  if (g.W_lo <= g.W || (size_t)(g.W_lo - g.W) + (size_t)g.N * KD >= (1ull << 30)) return WVN_ERR_ARG;
-  X384Params p{};
-  p.lda = KD; p.W = g.W; p.w_plane = (size_t)(g.W_lo - g.W); p.bias = g.bias;
-  p.C = g.C; p.C_lo = g.C_lo; p.C_h8 = g.C_h8; p.ldc = g.ldc; p.M = g.M; p.N = g.N;
-  p.heads = g.heads; p.npad = g.npad; p.ntok_s = g.ntok_s; p.q_scale = g.q_scale != 0.f ? g.q_scale : 1.f; p.f16_out = 1;
-  p.dbg = g.dbg;
-  p.ln_x = g.ln_x; p.ln_ldx = g.ln_ldx; p.ln_stats = g.ln_stats; p.ln_g = g.ln_g; p.ln_b = g.ln_b;
+  if (!g.ln_x || g.K != KD || g.ldw != KD || (g.N % BNT) != 0 || g.M <= 0 || !w_planes_ok(g.W, g.W_lo, g.N)) return WVN_ERR_ARG;
+  X384Params p = x384_params(g);
   switch (epi) {
     case EPI_GELU_FRAG:
-      if (!g.C || !g.C_lo || g.ldc != g.N || (g.N % 64) || (((uintptr_t)g.C | (uintptr_t)g.C_lo) & 15) || ((size_t)g.M + 32) * g.ldc * 2 >= (1ull << 31))
-        return WVN_ERR_ARG;
+      if (!frag_out_ok(g)) return WVN_ERR_ARG;
       return g_a384_mx_form != 1 ? launch_mx2<X_GELU_FRAG>(p, st) : launch_mx<X_GELU_FRAG>(p, st);
-    case EPI_QKV: {
-      if (!g.qkv_f16 || g.N != 3 * g.heads * 64 || !g.q || !g.k || !g.vt || (g.ntok_s % 16) || (g.M % 16) || (g.npad % 16)) return WVN_ERR_ARG;
-      const uintptr_t lo = std::min({(uintptr_t)g.q, (uintptr_t)g.k, (uintptr_t)g.vt});
-      const uintptr_t hi = std::max({(uintptr_t)g.q, (uintptr_t)g.k, (uintptr_t)g.vt});
-      const size_t one = (size_t)(g.M / (g.ntok_s > 0 ? g.ntok_s : 1)) * g.heads * g.npad * 64 * 2;
-      if (hi - lo + one >= (1ull << 31)) return WVN_ERR_ARG;
-      p.qkv_base = (bf16_t*)lo; p.q_off = (unsigned)((uintptr_t)g.q - lo); p.k_off = (unsigned)((uintptr_t)g.k - lo);
-      p.v_off = (unsigned)((uintptr_t)g.vt - lo); p.qkv_bytes = (unsigned)(hi - lo + one);
-      if (g.q_lo) {
-        if ((uintptr_t)g.q_lo < p.q_off) return WVN_ERR_ARG;
-        p.qkv_base_lo = (bf16_t*)((uintptr_t)g.q_lo - p.q_off);
-        p.q_lo_f16 = 1;
-      }
+    case EPI_QKV:
+      if (!g.qkv_f16 || !qkv_out_fill(p, g)) return WVN_ERR_ARG;
       return g_a384_mx_form != 1 ? launch_mx2<X_QKV_F16>(p, st) : launch_mx<X_QKV_F16>(p, st);
-    }
     default: return WVN_ERR_ARG;
   }
 }
+
