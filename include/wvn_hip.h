@@ -962,7 +962,9 @@ int wvn_debug_slic_lab(const void* img, int img_is_u8, int npix, const int* lut_
 int wvn_debug_attention_timing(long long* dbg);
 /* which form of the pre-scaled (scale == 0) attention kernel subsequent launches use: 0 = exact per-tile row max, 1 = lazy (no
  * per-tile max; the row sums raise the alarm and the tile is redone exactly -- the default), < 0 = back to the default.  Same
- * results within the kernel's tolerance; tests/test_gpu_attention_lazy.py runs both, bench.py --attn-variant A/Bs them. */
+ * results within the kernel's tolerance; tests/test_gpu_attention_lazy.py runs both, bench.py --attn-variant A/Bs them.  Any other
+ * value below 16 selects the default lazy form, bit for bit (2 once selected a lazy form with fp32-add row sums, which is retired);
+ * 17 / 18 select the form of the two-plane q instead. */
 int wvn_debug_attention_variant(int variant);
 /* The fp16-operand attention kernel exactly as WVN_PREC_MIX's wvn_vit_forward launches it, with the form of the two-plane q as an argument
  * (no process setting is read or changed for it; form 0 runs the single-plane form wvn_debug_attention_variant selects).  q pre-scaled by softmax_scale * log2(e) (the kernel runs with scale = 0), q / q_lo / k

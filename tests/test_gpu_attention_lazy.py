@@ -16,7 +16,7 @@ def bf(t):
     return t.to(torch.bfloat16)
 
 
-def run(dev, q_in, k, v, ntok, variant):
+def run(dev, q_in, k, v, ntok, variant, dtype=torch.bfloat16):
     B, h = q_in.shape[:2]
     npad = (ntok + 127) // 128 * 128
 
@@ -27,10 +27,11 @@ def run(dev, q_in, k, v, ntok, variant):
 
     vt = pad(v, 1e3).transpose(-1, -2)[..., ops.vt_token_order(npad)].contiguous().to(dev)
     qd, kd = pad(q_in, 50.0).to(dev), pad(k, -1e3).to(dev)
-    out = torch.empty(B * ntok, h * 64, dtype=torch.bfloat16, device=dev)
+    out = torch.empty(B * ntok, h * 64, dtype=dtype, device=dev)
+    fn = lib().wvn_attention_f16 if dtype == torch.float16 else lib().wvn_attention_bf16
     lib().wvn_debug_attention_variant(variant)
     try:
-        check(lib().wvn_attention_bf16(ptr(qd), ptr(kd), ptr(vt), ptr(out), B, h, ntok, npad, 0.0, stream()))
+        check(fn(ptr(qd), ptr(kd), ptr(vt), ptr(out), B, h, ntok, npad, 0.0, stream()))
         torch.cuda.synchronize()
     finally:
         lib().wvn_debug_attention_variant(-1)
@@ -76,3 +77,23 @@ def test_lazy_uniform_v_gives_exact_ones(dev):
     k = k * torch.linspace(0.2, 5.0, ntok)[None, None, :, None]
     out = run(dev, bf(q * C), bf(k), torch.ones(B, h, ntok, 64, dtype=torch.bfloat16), ntok, 1)
     assert (out - 1.0).abs().max().item() < 1e-2
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("B", [1, 4])
+def test_unknown_variant_selects_the_lazy_form(dev, B, dtype):
+    """wvn_debug_attention_variant(2) once selected a lazy form with fp32-add row sums, which is retired: 2, like any value the
+    library does not know (7), now selects the default lazy form -- the bits of variant 1, not the exact-max form's.  One full
+    tile plus a one-key masked tile whose key carries the row's largest score; 2 (frame, head) pairs (plain block order) and 8
+    (the XCD block order)."""
+    ntok, h = 65, 2
+    gen = torch.Generator().manual_seed(11 + B)
+    q, k, v = (torch.randn(B, h, ntok, 64, generator=gen) for _ in range(3))
+    k[:, :, ntok - 1] = k[:, :, ntok - 1] * 8.0
+    q_in, k, v = ((q * C).to(dtype), k.to(dtype), v.to(dtype))
+    lazy = run(dev, q_in, k, v, ntok, 1, dtype)
+    exact = run(dev, q_in, k, v, ntok, 0, dtype)
+    print(f"variant 0 against 1: {(lazy != exact).sum().item()} of {lazy.numel()} outputs differ in their bits")
+    assert torch.isfinite(lazy).all()
+    for variant in (2, 7):
+        assert torch.equal(run(dev, q_in, k, v, ntok, variant, dtype), lazy), variant

@@ -31,47 +31,79 @@
 //                   The QKV GEMM epilogues write V^T in this order (wvn_hip.h documents it for direct callers).
 //                   -> O^T accumulator lane l holds query l&31 again, so the online-softmax rescale
 //                      and the final 1/l are per-lane scalars.
-// Softmax, two forms of the same online algorithm:
-//   raw q (scale > 0)   : exp2 with scale*log2(e) folded into one v_pk_fma per two scores;
+// Softmax, one online algorithm (row sums by v_dot2c on the packed P: the sum of the ROUNDED P, exactly what the PV MFMA multiplies):
+//   raw q (scale > 0)   : exp2 with scale*log2(e) folded into one v_pk_fma per two scores (wvn_attention_bf16 / _f16);
 //   pre-scaled q (PRE)  : q already carries scale*log2(e) (the QKV epilogue multiplies before the bf16 rounding) and the
 //                         running max enters the S^T chains as the MFMA C operand, so the accumulators come out as exp2
-//                         arguments and the per-element fma disappears.  This is the form wvn_vit_forward uses.
-// In both the O rescale is deferred and wave-uniform (it runs when some row's score outgrows the running max by 2^6,
-// i.e. almost only on the first tiles).  The kernel is bound by VALU issue, not by the matrix pipe or LDS (DESIGN.md
-// section 4): what is left of the softmax is 32 v_exp, 16 v_max3, 16 v_cvt_pk, 16 v_dot2c per 16 MFMAs.
+//                         arguments and the per-element fma disappears.  This is the form wvn_vit_forward uses, in two variants:
+//     exact max         : the row max of every tile is taken (16 v_max3 + a lane swap) and the O rescale is deferred and wave-uniform:
+//                         it runs when some row's score outgrows the running max by 2^6, i.e. almost only on the first tiles
+//                         (the raw-q form does the same);
+//     lazy max (LAZY)   : what ships.  No per-tile row max: exponentiate against the running max as it stands and let the row
+//                         sums raise the alarm; only then, and on the first tile, the tile is redone the exact way.
+//   QSPLIT (lazy only)  : q as two planes, q = q_hi + q_lo, for the mixed precision: the second plane on MFMAs of the operand
+//                         format (1) or on one scaled e5m2 MFMA per sub-tile (2, fp16 build).
+// The kernel is bound by VALU issue, not by the matrix pipe or LDS: what is left of the lazy softmax is
+// 32 v_exp, 16 v_cvt_pk, 16 v_dot2c per 16 MFMAs.
 // Keys >= ntok (tile tail / padding) are neutralised by a select on their scores (p = 0); K / V^T padding must be
 // finite (0 * finite = 0 in the PV MFMA).  The masked last tile is peeled out of the tile loop.
+// The pieces of the tile scheme that attention_x3.hip shares (block decode, DMA and read offsets, Q fragments, tail mask, row
+// max, raw-q rescale, hi / lo split) are in attention_tile.h.
 #include <stdlib.h>
 
 #include <type_traits>
 
+#include "attention_tile.h"
 #include "mx_operand.h"
 #include "operand.h"
 #include "wvn_internal.h"
 
 namespace {
 
-constexpr int QB = 128;            // queries per workgroup (4 waves x 32)
-constexpr int KVB = 64;            // keys per tile
-constexpr int DH = 64;             // head dim
-constexpr int TILE_BYTES = KVB * DH * 2;  // 8 KB (K tile; V^T tile is the same size)
-
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
-// The softmax is bounded by per-wave VALU issue, so instruction count matters: the row max uses 3-input max.
-// This file is compiled with -fno-honor-nans so that fmaxf on MFMA results needs no canonicalising v_max (scores
-// are finite; masking uses -1e30, not infinities).  NOT inline asm: hipcc pads no MFMA-result hazards for an asm
-// statement's operands (a v_max3 in asm read accumulator registers before the MFMA had written them).
-__device__ inline float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+// The scalar half of the rescale of the pre-scaled form, taken when the running max moves (exact-max form: a row outgrew it by
+// ATTN_THR; lazy form: the row sums rang the alarm; both: the first tile, unconditionally, where m_run = 0 and rows whose scores
+// are all far below 0 must not underflow).  mt = the tile's row max relative to the running max.  The caller multiplies O by
+// alpha, moves the tile's scores by delta and rewrites the C operand of the S^T chains (-m_run) in place: those three loops,
+// written inside a function, change the compiled lazy kernels (profiles/attention_refactor.md).
+struct PreRescale { float delta, alpha; };
+__device__ __forceinline__ PreRescale rescale_pre(float mt, bool& fresh, float& m_run, float& l_run, float& l_run1) {
+  const float delta = fresh ? mt : fmaxf(mt, 0.f);
+  const float alpha = fresh ? 1.f : __builtin_amdgcn_exp2f(-delta);
+  fresh = false;
+  m_run += delta;
+  l_run *= alpha;
+  l_run1 *= alpha;
+  return {delta, alpha};
+}
+
+// O^T += V^T P^T for one group of 16 keys: p = the half-wave's 8 packed probabilities of the group, fa_ks = its per-lane address
+// in the V^T tile vt_tile (the 8 keys are one 16-byte chunk there)
+__device__ __forceinline__ void pv_group(const unsigned char* vt_tile, unsigned fa_ks, u32x4_t p, f32x16_t (&ot)[2]) {
+  union { u32x4_t u; opx8_t v; } pf;
+  pf.u = p;
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt) {
+    const opx8_t vf = *(const opx8_t*)(vt_tile + fa_ks + dt * 4096);
+    ot[dt] = wvn_mfma_32x32x16(vf, pf.v, ot[dt], 0, 0, 0);
+  }
+}
+
+// element offset of a flat token row m in a FRAGMENT-MAJOR plane (attention_bf16_kernel's out_frag epilogues): 32-row group m >> 5,
+// k-step 4 head (+ 2 dt + u: 512 elements each), lane hi * 32 + (m & 31), 8 elements per lane
+__device__ __forceinline__ size_t frag_major_offset(size_t m, int nks, int head, int hi) {
+  return (((m >> 5) * nks + head * 4) * 64 + hi * 32 + (m & 31)) * 8;
+}
 
 // PRE: q arrives pre-multiplied by scale * log2(e) (the QKV GEMM epilogue does it before rounding to bf16, so no extra
 // rounding) and the running max enters the S^T MFMA chain as its C operand (a 16-register block holding -M, rewritten
 // only when the max moves): the accumulators come out as exp2 arguments and the 16 v_pk_fma per tile disappear.
-// SUM: how the row sums are formed.  0: v_dot2c_f32_bf16 on the packed P (16 per tile); 1: plain adds on the fp32 P.
+// LAZY (PRE only): no per-tile row max; the row sums raise the alarm (compute_tile_lazy below).
 // QSPLIT: 0 = one q plane; 1 = q as two planes of the operand format (eight more MFMAs per tile); 2 (round 6, fp16 build) = the second plane as ONE scaled
 // e5m2 MFMA of K = 64 per 32-key sub-tile: q_lo -> e5m2(q_lo * 2^12) once per workgroup, the keys' e5m2 image = the top bytes of the fp16 K fragments already in
 // registers (two v_perm per fragment: truncation, a 9 % shortfall of a term that is itself 2^-12 of the score) -- 64 matrix-pipe cycles per sub-tile instead of 128
-template <int NST, bool XCDMAP, int OCC, bool TIMING = false, bool PRE = false, int SUM = 0, bool LAZY = false, int QSPLIT = 0>
+template <int NST, bool XCDMAP, int OCC, bool TIMING = false, bool PRE = false, bool LAZY = false, int QSPLIT = 0>
 __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* __restrict__ q,
                                                                   const op16_t* __restrict__ k,
                                                                   const op16_t* __restrict__ vt,
@@ -84,15 +116,8 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
-  int bh, qb;
-  if constexpr (XCDMAP) {  // nbh % 8 == 0 (checked by the launcher)
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    bh = (idx / nqb) * 8 + xcd;
-    qb = idx % nqb;
-  } else {
-    bh = blockIdx.x / nqb;
-    qb = blockIdx.x - bh * nqb;
-  }
+  const AttnBlock wg = attn_block<XCDMAP>(nqb);
+  const int bh = wg.bh, qb = wg.qb;
   const int b = bh / heads, head = bh - b * heads;
   const int q0 = qb * QB + wave * 32;
 
@@ -100,23 +125,18 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   const unsigned kv_bytes = (unsigned)((size_t)nbh * npad * DH * 2);
   const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc((void*)k, 0, kv_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc((void*)vt, 0, kv_bytes, 0x00020000);
-  unsigned koff[2], voff[2];
+  AttnDmaOffset src[2];
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int row = (wave * 2 + u) * 8 + (lane >> 3);          // key (K tile) or d (V^T tile)
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);           // source chunk that lands in LDS chunk lane & 7
-    koff[u] = (unsigned)((((size_t)bh * npad + row) * DH + chunk * 8) * 2);   // + kv0 * 128
-    voff[u] = (unsigned)((((size_t)bh * DH + row) * npad + chunk * 8) * 2);   // + kv0 * 2
-  }
+  for (int u = 0; u < 2; ++u) src[u] = attn_dma_offset(bh, npad, (wave * 2 + u) * 8 + (lane >> 3), lane);
   auto issue = [&](int t) {
     unsigned char* dst = lds + (t % NST) * 2 * TILE_BYTES + wave * 2048;
     const unsigned ks = __builtin_amdgcn_readfirstlane(t * KVB * DH * 2), vs = __builtin_amdgcn_readfirstlane(t * KVB * 2);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (__attribute__((address_space(3))) void*)(dst + u * 1024), 16,
-                                               koff[u], ks, 0, 0);
+                                               src[u].k, ks, 0, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_v, (__attribute__((address_space(3))) void*)(dst + TILE_BYTES + u * 1024),
-                                               16, voff[u], vs, 0, 0);
+                                               16, src[u].v, vs, 0, 0);
     }
   };
   const int nt = (ntok + KVB - 1) / KVB;
@@ -127,12 +147,9 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   // ---- Q^T fragments (B operand): query l31, d = 16 s + 8 hi .. + 7 ------------------------------------------
   const op16_t* qg = q + ((size_t)bh * npad + q0 + l31) * DH + hi * 8;
   opx8_t qf[4];
+  attn_load_q(qg, qf);
 #pragma unroll
-  for (int s = 0; s < 4; ++s) qf[s] = *(const opx8_t*)(qg + s * 16);
-  // Make the Q fragments "used" here: otherwise hipcc places their vmcnt wait at the first use INSIDE the
-  // tile loop, where it would also drain the K/V DMA queue on every trip.
-#pragma unroll
-  for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(qf[s]));
+  for (int s = 0; s < 4; ++s) qf[s] = attn_used(qf[s]);
   // QSPLIT (WVN_PREC_MIX): q as TWO planes, q = qf + ql (ql = the rounding residue of qf in the same format): S^T = K qf^T + K ql^T, eight
   // more MFMAs per tile on the K fragments already read.  Why q and not k: a key's rounding error is independent from key to key and
   // averages out over the thousands of keys of a row; the query's error is the SAME direction against every key of its row -- on the
@@ -142,10 +159,9 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   i32x8_t ql8 = {0, 0, 0, 0, 0, 0, 0, 0};
   if constexpr (QSPLIT != 0) {
     const op16_t* qlg = q_lo + ((size_t)bh * npad + q0 + l31) * DH + hi * 8;
+    attn_load_q(qlg, ql);
 #pragma unroll
-    for (int s = 0; s < 4; ++s) ql[s] = *(const opx8_t*)(qlg + s * 16);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(ql[s]));
+    for (int s = 0; s < 4; ++s) ql[s] = attn_used(ql[s]);
   }
 #if WVN_OPERAND_F16
   if constexpr (QSPLIT == 2) {   // byte (s, j) of the lane's 32 = e5m2(q_lo[16 s + 8 hi + j] * 2^12): the order the K fragments' top bytes are gathered in below
@@ -170,12 +186,9 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   for (int r = 0; r < 16; ++r) cneg[r] = 0.f;
   bool fresh = true;                              // PRE: no tile processed yet (wave-uniform)
 
-  // per-lane read offset inside a tile: row l31 (+32 per sub-tile), chunk XOR key (row >> 1) & 7 (same for row+32)
-  const unsigned rd_row = l31 * 128;
-  const int xorc = (l31 >> 1) & 7;
   unsigned rdo[4];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) rdo[s] = rd_row + (((2 * s + hi) ^ xorc) << 4);
+  for (int s = 0; s < 4; ++s) rdo[s] = attn_read_offset(l31, hi, s);
 
   long long tm[5] = {0, 0, 0, 0, 0};  // TIMING: wait+barrier+issue, QK^T, softmax, PV, total
   auto now = [&]() -> long long {
@@ -186,17 +199,8 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   auto compute_tile = [&](int kv0, int stage, int t_issue, auto tail_tag) {
     constexpr bool MAYBE_TAIL = decltype(tail_tag)::value;
     const long long c0 = now();
-    // four per-lane addresses per tile (stage base + swizzled chunk of row l31); every fragment read below is one of them
-    // plus an immediate (K sub-tile +4096, V^T +8192, +12288).  Opaque to the optimiser, which otherwise re-derives an
-    // address per ds_read (16 v_add3_u32 per tile).
     unsigned fa[4];
-    unsigned so = (unsigned)(stage * 2 * TILE_BYTES);
-    asm volatile("" : "+s"(so));  // keep the stage offset a scalar: one v_add per address, no loop-carried vector adds
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      fa[s] = rdo[s] + so;
-      asm volatile("" : "+v"(fa[s]));
-    }
+    attn_tile_addresses(rdo, (unsigned)(stage * 2 * TILE_BYTES), fa);
 
     // ---- S^T = K Q^T : two 32-key sub-tiles (first MFMA of each chain takes a literal-zero C) ----
     f32x16_t st[2];
@@ -221,39 +225,15 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
     // ---- mask the tail of the last tile ----
     if (MAYBE_TAIL && kv0 + KVB > ntok) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kv0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          if (key >= ntok) st[t][r] = -1e30f;
-        }
+      for (int t = 0; t < 2; ++t) st[t] = attn_mask_tail(st[t], kv0 + t * 32, ntok, hi);
     }
     // ---- online softmax (lane = query, both half-waves share the running max) ----
-    // row max: 16 three-input max (two independent chains), then the other half-wave's
-    float ma = max3f(st[0][0], st[0][1], st[0][2]), mb = max3f(st[1][0], st[1][1], st[1][2]);
-    ma = max3f(ma, st[0][3], st[0][4]); mb = max3f(mb, st[1][3], st[1][4]);
-#pragma unroll
-    for (int r = 5; r < 15; r += 2) { ma = max3f(ma, st[0][r], st[0][r + 1]); mb = max3f(mb, st[1][r], st[1][r + 1]); }
-    float mt = max3f(ma, mb, st[0][15]);
-    mt = max3f(mt, st[1][15], st[1][15]);
-    {  // the other half-wave's max of the same query: v_permlane32_swap (VALU) instead of a ds_bpermute LDS round trip
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
-      mt = max3f(mt, __uint_as_float(sw[0]), __uint_as_float(sw[1]));  // one of the two is this lane's own value
-    }
-    // Deferred rescale: the running max only follows when some row's scores outgrow it by more than THR (in
-    // exp2 units).  P is then bounded by 2^THR instead of 1 -- harmless in fp32 accumulators, and P / l cancel
-    // exactly the same factor -- and the wave-uniform O rescale almost never runs after the first tiles.
-    constexpr float THR = 6.0f;
+    const float mt = attn_row_max(st);
     if constexpr (PRE) {
-      // st = c s - m_run already.  The max follows when a row outgrows it by THR, or unconditionally on the first tile
-      // (m_run = 0 there: rows whose scores are all far below 0 must not underflow).
-      if (fresh || __any(mt > THR)) {
-        const float delta = fresh ? mt : fmaxf(mt, 0.f);
-        const float alpha = fresh ? 1.f : __builtin_amdgcn_exp2f(-delta);
-        fresh = false;
-        m_run += delta;
-        l_run *= alpha;
-        l_run1 *= alpha;
+      // st = c s - m_run already.  The max follows when a row outgrows it by ATTN_THR (the deferred rescale of attention_tile.h)
+      // or on the first tile.
+      if (fresh || __any(mt > ATTN_THR)) {
+        const auto [delta, alpha] = rescale_pre(mt, fresh, m_run, l_run, l_run1);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -270,17 +250,7 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[t][r] = __builtin_amdgcn_exp2f(st[t][r]);
     } else {
-      if (__any((mt - m_run) * c_exp > THR)) {
-        const float m_new = fmaxf(m_run, mt);
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c_exp);
-        m_run = m_new;
-        l_run *= alpha;
-        l_run1 *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
-      }
+      attn_rescale_raw(mt, c_exp, m_run, l_run, l_run1, ot);
       const float mc = -m_run * c_exp;
       const f32x2_t c2v = {c_exp, c_exp}, mc2 = {mc, mc};
 #pragma unroll
@@ -298,25 +268,17 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int t = ks >> 1, h8 = (ks & 1) * 8;
-      union { u32x4_t u; opx8_t v; } pf;
+      u32x4_t pf;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const uint32_t pk = pack_op2(st[t][h8 + 2 * e], st[t][h8 + 2 * e + 1]);
-        pf.u[e] = pk;  // (bit_cast of the scalar, not of the vector element: clang reads element 0 for the latter)
-        if constexpr (SUM == 0) {  // row sum of the rounded P (exactly what the PV MFMA multiplies)
-          if (e & 1) l_run1 = dot2_ones_op(pk, l_run1);
-          else l_run = dot2_ones_op(pk, l_run);
-        } else {  // plain adds on the fp32 P.  NOT inline asm: its operands are v_exp results, and hipcc pads the
-                  // transcendental-result hazard only for instructions it emits itself (an asm v_add read stale values)
-          l_run += st[t][h8 + 2 * e];
-          l_run1 += st[t][h8 + 2 * e + 1];
-        }
+        pf[e] = pk;
+        // row sum of the rounded P (exactly what the PV MFMA multiplies), from the scalar pk, not from pf[e]: clang's bit_cast of a
+        // vector element reads element 0
+        if (e & 1) l_run1 = dot2_ones_op(pk, l_run1);
+        else l_run = dot2_ones_op(pk, l_run);
       }
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const opx8_t vf = *(const opx8_t*)(lds + fa[ks] + TILE_BYTES + dt * 4096);
-        ot[dt] = wvn_mfma_32x32x16(vf, pf.v, ot[dt], 0, 0, 0);
-      }
+      pv_group(lds + TILE_BYTES, fa[ks], pf, ot);
     }
     if constexpr (PRE) __builtin_amdgcn_s_setprio(0);
     if constexpr (TIMING) {
@@ -336,13 +298,7 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   auto compute_tile_lazy = [&](int kv0, int stage, int t_issue, auto tail_tag) {
     constexpr bool MAYBE_TAIL = decltype(tail_tag)::value;
     unsigned fa[4];
-    unsigned so = (unsigned)(stage * 2 * TILE_BYTES);
-    asm volatile("" : "+s"(so));
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      fa[s] = rdo[s] + so;
-      asm volatile("" : "+v"(fa[s]));
-    }
+    attn_tile_addresses(rdo, (unsigned)(stage * 2 * TILE_BYTES), fa);
     f32x16_t st[2];
     auto qk = [&]() {
 #pragma unroll
@@ -364,12 +320,13 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
           if constexpr (QSPLIT == 2) st[t] = mx_correction<true>(k8, ql8, st[t], 1);   // k_h8 x q_l8 (carries 2^12)
 #endif
         }
+      // (attn_mask_tail written in place: st is a capture here, and the by-value function changes the compiled lazy kernels)
       if (MAYBE_TAIL && kv0 + KVB > ntok) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int key = kv0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const int key = kv0 + t * 32 + attn_key_of(r, hi);
             if (key >= ntok) st[t][r] = -1e30f;
           }
       }
@@ -386,13 +343,9 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
           const float e0 = __builtin_amdgcn_exp2f(st[t][h8 + 2 * e]), e1 = __builtin_amdgcn_exp2f(st[t][h8 + 2 * e + 1]);
           const uint32_t pk = pack_op2(e0, e1);
           pfu[ks][e] = pk;
-          if constexpr (SUM == 0) {   // row sums of the ROUNDED P: one v_dot2c per pair
-            if (e & 1) s1 = dot2_ones_op(pk, s1);
-            else s0 = dot2_ones_op(pk, s0);
-          } else {                    // plain fp32 adds on the unrounded P (this file is compiled with -fno-slp-vectorize: packed
-            s0 += e0;                 // v_pk_add_f32 beside MFMAs costs more than two scalar adds, MI355X_MICROARCH.md)
-            s1 += e1;
-          }
+          // row sums of the ROUNDED P: one v_dot2c per pair
+          if (e & 1) s1 = dot2_ones_op(pk, s1);
+          else s0 = dot2_ones_op(pk, s0);
         }
       }
     };
@@ -407,20 +360,7 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
     if (!fresh) expsum();
     if (fresh || __any(s0 + s1 > ALARM)) {
       if (!fresh) qk();   // the exponentials overwrote the scores
-      float ma = max3f(st[0][0], st[0][1], st[0][2]), mb = max3f(st[1][0], st[1][1], st[1][2]);
-      ma = max3f(ma, st[0][3], st[0][4]); mb = max3f(mb, st[1][3], st[1][4]);
-#pragma unroll
-      for (int r = 5; r < 15; r += 2) { ma = max3f(ma, st[0][r], st[0][r + 1]); mb = max3f(mb, st[1][r], st[1][r + 1]); }
-      float mt = max3f(ma, mb, st[0][15]);
-      mt = fmaxf(mt, st[1][15]);
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
-      mt = max3f(mt, __uint_as_float(sw[0]), __uint_as_float(sw[1]));
-      const float delta = fresh ? mt : fmaxf(mt, 0.f);
-      const float alpha = fresh ? 1.f : __builtin_amdgcn_exp2f(-delta);
-      fresh = false;
-      m_run += delta;
-      l_run *= alpha;
-      l_run1 *= alpha;
+      const auto [delta, alpha] = rescale_pre(attn_row_max(st), fresh, m_run, l_run, l_run1);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -438,15 +378,7 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
     __builtin_amdgcn_sched_barrier(0);
     // ---- O^T += V^T P^T ----
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      union { u32x4_t u; opx8_t v; } pf;
-      pf.u = pfu[ks];
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) {
-        const opx8_t vf = *(const opx8_t*)(lds + fa[ks] + TILE_BYTES + dt * 4096);
-        ot[dt] = wvn_mfma_32x32x16(vf, pf.v, ot[dt], 0, 0, 0);
-      }
-    }
+    for (int ks = 0; ks < 4; ++ks) pv_group(lds + TILE_BYTES, fa[ks], pfu[ks], ot);
     __builtin_amdgcn_s_setprio(0);
   };
 
@@ -455,25 +387,25 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
   // The last tile (the only one that may need masking) is peeled: with both instantiations of compute_tile inside one
   // loop body hipcc gave the O^T accumulators different registers on the two paths and copied all 32 of them twice per
   // tile (32 v_mov_b64 that also wait for the PV MFMAs to drain).
-  for (int t = 0; t + 1 < nt; ++t) {
+  // in_flight: how many DMA instructions of younger tiles may stay outstanding; returns the cycles waited (TIMING, else 0)
+  auto tile_ready = [&](auto in_flight) -> long long {
     const long long w0 = now();
-    if (t + NST - 2 < nt) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (NST - 2)) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(in_flight)::value) : "memory");
     __builtin_amdgcn_s_barrier();
-    if constexpr (TIMING) tm[0] += now() - w0;
+    if constexpr (TIMING) return now() - w0;
+    return 0;
+  };
+  for (int t = 0; t + 1 < nt; ++t) {
+    if (t + NST - 2 < nt) tm[0] += tile_ready(std::integral_constant<int, 4 * (NST - 2)>{});
+    else tm[0] += tile_ready(std::integral_constant<int, 0>{});
     // (the next tile's DMA is requested inside compute_tile, after the QK^T MFMAs have been issued: the four DMA
     // instructions cost the wave a few hundred cycles of issue time, which then overlap the matrix pipe's work)
     if constexpr (LAZY) compute_tile_lazy(t * KVB, t % NST, t + NST - 1 < nt ? t + NST - 1 : -1, std::false_type{});
     else compute_tile(t * KVB, t % NST, t + NST - 1 < nt ? t + NST - 1 : -1, std::false_type{});
   }
-  {
-    const long long w0 = now();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if constexpr (TIMING) tm[0] += now() - w0;
-    if constexpr (LAZY) compute_tile_lazy((nt - 1) * KVB, (nt - 1) % NST, -1, std::true_type{});
-    else compute_tile((nt - 1) * KVB, (nt - 1) % NST, -1, std::true_type{});
-  }
+  tm[0] += tile_ready(std::integral_constant<int, 0>{});
+  if constexpr (LAZY) compute_tile_lazy((nt - 1) * KVB, (nt - 1) % NST, -1, std::true_type{});
+  else compute_tile((nt - 1) * KVB, (nt - 1) % NST, -1, std::true_type{});
 
   if constexpr (TIMING) {
     if (lane == 0 && dbg) {
@@ -482,9 +414,7 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
     }
   }
   // ---- normalise and store: out[b*ntok_s + q][head*64 + d] ----
-  l_run += l_run1;
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.0f / l_tot;
+  const float inv = attn_inv_row_sum(l_run, l_run1);
   const int qi = q0 + l31;
   if (out_lo && out_frag == 2) {
     // (uniform) the MX operand planes of the projection (csrc/gemm_n384_x3.hip, gemm_n384_mx_pair_kernel): per element h = fp16(o) as FRAGMENT-MAJOR
@@ -498,7 +428,7 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
       const float keep = qi < ntok ? inv : 0.f;
       const size_t m = (size_t)b * ntok_s + qi;
       const int nks = heads * 4;
-      op16_t* fb = out + (((m >> 5) * nks + head * 4) * 64 + hi * 32 + (m & 31)) * 8;
+      op16_t* fb = out + frag_major_offset(m, nks, head, hi);
       unsigned char* l8 = (unsigned char*)out_lo + (((m >> 5) * heads + head) * 2 * 64 + hi * 32 + (m & 31)) * 16;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
@@ -534,8 +464,8 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
       // gemm_a384_x3.hip's EPI_GELU_FRAG; the projection's weight carries the same column permutation)
       const size_t m = (size_t)b * ntok_s + qi;
       const int nks = heads * 4;
-      op16_t* fb = out + (((m >> 5) * nks + head * 4) * 64 + hi * 32 + (m & 31)) * 8;
-      op16_t* fl = out_lo + (((m >> 5) * nks + head * 4) * 64 + hi * 32 + (m & 31)) * 8;
+      op16_t* fb = out + frag_major_offset(m, nks, head, hi);
+      op16_t* fl = out_lo + frag_major_offset(m, nks, head, hi);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -545,8 +475,9 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
           for (int e = 0; e < 4; ++e) {
             const int r = 4 * (2 * u + (e >> 1)) + 2 * (e & 1);      // g = 2 u + (e >> 1), elements 2 (e & 1), + 1
             const float a = ot[dt][r] * inv, c = ot[dt][r + 1] * inv;
-            oh[e] = pack_bf16x2(a, c);
-            olo[e] = pack_bf16x2(a - __uint_as_float(oh[e] << 16), c - __uint_as_float(oh[e] & 0xffff0000u));
+            const Bf16Split o2 = attn_split_bf16x2(a, c);
+            oh[e] = o2.hi;
+            olo[e] = o2.lo;
           }
           *(u32x4_t*)(fb + (2 * dt + u) * 512) = oh;
           *(u32x4_t*)(fl + (2 * dt + u) * 512) = olo;
@@ -561,8 +492,9 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
             const float a = ot[dt][4 * g + 2 * e] * inv, c = ot[dt][4 * g + 2 * e + 1] * inv;
-            oh[e] = pack_bf16x2(a, c);
-            olo[e] = pack_bf16x2(a - __uint_as_float(oh[e] << 16), c - __uint_as_float(oh[e] & 0xffff0000u));
+            const Bf16Split o2 = attn_split_bf16x2(a, c);
+            oh[e] = o2.hi;
+            olo[e] = o2.lo;
           }
           *(u32x2_t*)(og + dt * 32 + 8 * g + 4 * hi) = oh;
           *(u32x2_t*)(ol + dt * 32 + 8 * g + 4 * hi) = olo;
@@ -583,86 +515,58 @@ __global__ __launch_bounds__(256, OCC) void attention_bf16_kernel(const op16_t* 
 
 long long* g_attn_dbg = nullptr;  // set by wvn_debug_attention_timing (scripts/attn_timing.py)
 
-constexpr int ATTN_DEFAULT = 1;
-int g_attn_variant = ATTN_DEFAULT;   // 0: exact per-tile row max, 1: lazy (alarm on the row sums; what ships: -4 % attention time)
+bool g_attn_lazy = true;   // the pre-scaled form: true = lazy (alarm on the row sums; what ships: -4 % attention time), false = exact per-tile row max
 int g_attn_qsplit_form = 2;   // two-plane q: 2 = the second plane on a scaled e5m2 MFMA (round 6, fp16 build), 1 = both planes on fp16 MFMAs (round 4)
 
-// form: the form of the two-plane q (read only when q_lo is set): g_attn_qsplit_form for the product's launches, the caller's own for
-// wvn_debug_attention_planes
-void launch_pre(bool xcd, dim3 grid, hipStream_t st, const op16_t* q, const op16_t* k, const op16_t* vt, op16_t* out,
-                int heads, int nbh, int nqb, int ntok, int ntok_s, int npad, op16_t* out_lo, const op16_t* q_lo, int out_frag, int form) {
-  if (q_lo && WVN_OPERAND_F16 && form == 2) {   // two-plane q, the second plane on ONE scaled e5m2 MFMA per sub-tile (round 6); 148 registers: three
-    // workgroups per CU (forced to four -- 128 registers, 68 bytes of scratch -- it runs 14 % slower: 31.0 against 27.2 ms of attention per step)
-    if (xcd)
-      hipLaunchKernelGGL((attention_bf16_kernel<2, true, 3, false, true, 0, true, 2>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                         nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, q_lo, out_frag);
-    else
-      hipLaunchKernelGGL((attention_bf16_kernel<2, false, 3, false, true, 0, true, 2>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                         nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, q_lo, out_frag);
-    return;
-  }
-  if (q_lo) {   // two-plane q: the lazy form with 16 more registers -- three workgroups per CU
-    if (xcd)
-      hipLaunchKernelGGL((attention_bf16_kernel<2, true, 3, false, true, 0, true, 1>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                         nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, q_lo, out_frag);
-    else
-      hipLaunchKernelGGL((attention_bf16_kernel<2, false, 3, false, true, 0, true, 1>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                         nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, q_lo, out_frag);
-    return;
-  }
-  // 2-stage ring, 4 workgroups per CU (the pre-scaled kernel needs 128 VGPRs: 11.96 ms per step against 12.28 for 3 stages /
-  // 3 workgroups and 13.2 for 4 stages / 2); row sums by v_dot2c_f32_bf16 on the packed P (plain fp32 adds, which hipcc packs
-  // into v_pk_add_f32, measured 12.0 ms per step against 11.7).  The same arithmetic with and without the XCD block order:
-  // results must not depend on the batch size (tests/test_gpu_attention_xcd.py).
-  if (g_attn_variant == 2) {   // lazy max, row sums by scalar fp32 adds
-    if (xcd)
-      hipLaunchKernelGGL((attention_bf16_kernel<2, true, 4, false, true, 1, true>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                         nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, nullptr, out_frag);
-    else
-      hipLaunchKernelGGL((attention_bf16_kernel<2, false, 4, false, true, 1, true>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                         nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, nullptr, out_frag);
-    return;
-  }
-  if (g_attn_variant == 1) {
-    if (xcd)
-      hipLaunchKernelGGL((attention_bf16_kernel<2, true, 4, false, true, 0, true>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                         nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, nullptr, out_frag);
-    else
-      hipLaunchKernelGGL((attention_bf16_kernel<2, false, 4, false, true, 0, true>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                         nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, nullptr, out_frag);
-    return;
-  }
-  if (xcd)
-    hipLaunchKernelGGL((attention_bf16_kernel<2, true, 4, false, true>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                       nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, nullptr, out_frag);
-  else
-    hipLaunchKernelGGL((attention_bf16_kernel<2, false, 4, false, true>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh,
-                       nqb, ntok, ntok_s, npad, 1.f, nullptr, out_lo, nullptr, out_frag);
+// what a launch hands the kernel, filled once by wvn_attention_bf16_launch
+struct AttnLaunch {   // (the kernel's parameters, in its order, behind the grid and the stream)
+  dim3 grid; hipStream_t st;
+  const op16_t *q, *k, *vt; op16_t* out;
+  int heads, nbh, nqb, ntok, ntok_s, npad; float c_exp; long long* dbg; op16_t* out_lo; const op16_t* q_lo; int out_frag;
+};
+
+// xcd picks the XCDMAP instantiation: the same arithmetic with and without the XCD block order, results must not depend on the
+// batch size (tests/test_gpu_attention_xcd.py).  The instrumented (TIMING) kernel exists in the XCD order only.
+template <int NST, int OCC, bool TIMING, bool PRE, bool LAZY, int QSPLIT>
+void launch(bool xcd, const AttnLaunch& a) {
+  auto go = [&](auto xcdmap) {
+    hipLaunchKernelGGL((attention_bf16_kernel<NST, decltype(xcdmap)::value, OCC, TIMING, PRE, LAZY, QSPLIT>), a.grid, dim3(256), 0, a.st, a.q,
+                       a.k, a.vt, a.out, a.heads, a.nbh, a.nqb, a.ntok, a.ntok_s, a.npad, a.c_exp, a.dbg, a.out_lo, a.q_lo, a.out_frag);
+  };
+  if constexpr (TIMING) go(std::true_type{});
+  else if (xcd) go(std::true_type{});
+  else go(std::false_type{});
 }
 
-template <int NST, int OCC>
-void launch_v(bool xcd, dim3 grid, hipStream_t st, const op16_t* q, const op16_t* k, const op16_t* vt, op16_t* out,
-              int heads, int nbh, int nqb, int ntok, int ntok_s, int npad, float c_exp, op16_t* out_lo) {
-  if (g_attn_dbg) {
-    hipLaunchKernelGGL((attention_bf16_kernel<NST, true, OCC, true>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh, nqb,
-                       ntok, ntok_s, npad, c_exp, g_attn_dbg, out_lo, nullptr, 0);
-    return;
-  }
-  if (xcd)
-    hipLaunchKernelGGL((attention_bf16_kernel<NST, true, OCC>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh, nqb, ntok,
-                       ntok_s, npad, c_exp, nullptr, out_lo, nullptr, 0);
-  else
-    hipLaunchKernelGGL((attention_bf16_kernel<NST, false, OCC>), grid, dim3(256), 0, st, q, k, vt, out, heads, nbh, nqb, ntok,
-                       ntok_s, npad, c_exp, nullptr, out_lo, nullptr, 0);
+// pre-scaled q.  form: the form of the two-plane q (read only when q_lo is set): g_attn_qsplit_form for the product's launches, the
+// caller's own for wvn_debug_attention_planes
+void launch_pre(bool xcd, const AttnLaunch& a, int form) {
+  // two-plane q, the second plane on ONE scaled e5m2 MFMA per sub-tile (round 6); 148 registers: three workgroups per CU (forced to
+  // four -- 128 registers, 68 bytes of scratch -- it runs 14 % slower: 31.0 against 27.2 ms of attention per step)
+  if (a.q_lo && WVN_OPERAND_F16 && form == 2) return launch<2, 3, false, true, true, 2>(xcd, a);
+  // two-plane q: the lazy form with 16 more registers -- three workgroups per CU
+  if (a.q_lo) return launch<2, 3, false, true, true, 1>(xcd, a);
+  // 2-stage ring, 4 workgroups per CU (the pre-scaled kernel needs 128 VGPRs: 11.96 ms per step against 12.28 for 3 stages /
+  // 3 workgroups and 13.2 for 4 stages / 2)
+  if (g_attn_lazy) return launch<2, 4, false, true, true, 0>(xcd, a);
+  launch<2, 4, false, true, false, 0>(xcd, a);
+}
+
+// raw q: 3-stage ring, 3 workgroups / CU
+void launch_v(bool xcd, const AttnLaunch& a) {
+  if (a.dbg) return launch<3, 3, true, false, false, 0>(xcd, a);
+  launch<3, 3, false, false, false, 0>(xcd, a);
 }
 
 }  // namespace
 
 void WVN_OPSYM(wvn_attention_bf16_set_debug)(long long* dbg) { g_attn_dbg = dbg; }
+// v >= 16 (17 / 18): the form of the two-plane q.  Otherwise the single-plane pre-scaled form: 0 = exact per-tile row max, anything
+// else (1, a negative "back to the default", a value this library does not know) = the lazy form, which is the default.
 void WVN_OPSYM(wvn_attention_bf16_set_variant)(int v) {
-  if (v >= 16) { g_attn_qsplit_form = v - 16; return; }   // 17 / 18: the form of the two-plane q (wvn_debug_attention_variant)
-  g_attn_variant = v < 0 ? ATTN_DEFAULT : v;
-}  // < 0: back to the default
+  if (v >= 16) { g_attn_qsplit_form = v - 16; return; }
+  g_attn_lazy = v != 0;
+}
 
 // scale > 0: q holds the raw projections.  scale == 0: q is pre-multiplied by softmax_scale * log2(e) (EPI_QKV with
 // q_scale set), the kernel with the running max folded into the S^T MFMA chain runs.
@@ -675,17 +579,15 @@ int WVN_OPSYM(wvn_attention_bf16_launch)(const op16_t* q, const op16_t* k, const
   if (!q || !k || !vt || !out || npad % QB != 0 || npad < ntok) return WVN_ERR_ARG;
   const int nqb = ceil_div(ntok, QB), nbh = B * heads;
   if ((size_t)nbh * npad * DH * 2 >= (1ull << 32)) return WVN_ERR_ARG;  // 32-bit buffer offsets
-  const float c_exp = scale * 1.44269504088896340736f;
-  dim3 grid(nqb * nbh);
   const bool xcd = (nbh % 8) == 0;  // the XCD decode needs whole groups of 8 (frame, head) pairs
-  if (scale == 0.f && !g_attn_dbg) {
-    launch_pre(xcd, grid, st, q, k, vt, out, heads, nbh, nqb, ntok, ntok_s, npad, out_lo, q_lo, out_frag,
-               qsplit_form < 0 ? g_attn_qsplit_form : qsplit_form);
-    WVN_LAUNCH_CHECK();
-    return WVN_OK;
-  }
-  if (scale == 0.f || q_lo) return WVN_ERR_ARG;
-  launch_v<3, 3>(xcd, grid, st, q, k, vt, out, heads, nbh, nqb, ntok, ntok_s, npad, c_exp, out_lo);  // raw-q form: 3-stage ring, 3 workgroups / CU
+  const bool pre = scale == 0.f && !g_attn_dbg;
+  if (!pre && (scale == 0.f || q_lo)) return WVN_ERR_ARG;
+  // (the pre-scaled kernels do not read c_exp; the raw-q form has neither a second q plane nor fragment-major output)
+  const AttnLaunch a = {dim3(nqb * nbh), st, q, k, vt, out, heads, nbh, nqb, ntok, ntok_s, npad,
+                        pre ? 1.f : scale * 1.44269504088896340736f, pre ? nullptr : g_attn_dbg, out_lo, pre ? q_lo : nullptr,
+                        pre ? out_frag : 0};
+  if (pre) launch_pre(xcd, a, qsplit_form < 0 ? g_attn_qsplit_form : qsplit_form);
+  else launch_v(xcd, a);
   WVN_LAUNCH_CHECK();
   return WVN_OK;
 }

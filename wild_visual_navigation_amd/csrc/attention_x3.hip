@@ -12,19 +12,15 @@
 // bf16 kernel's tiles, every fragment one conflict-free ds_read_b128.  V^T planes use the bf16 kernel's token permutation
 // (bits 2 and 3 of the token index swapped inside aligned groups of 16); the exact-mode QKV epilogue (gemm_x3.hip) writes it.
 // Keys >= ntok are masked by score; K / V^T padding must be finite.  Output: hi / lo planes [B * ntok_s, heads * 64] for the
-// projection GEMM.
+// projection GEMM.  What the two kernels share of the scheme is in attention_tile.h.
 #include <type_traits>
 
-#include "common.h"
+#include "attention_tile.h"
 #include "wvn_internal.h"
 
 namespace {
 
-constexpr int QB = 128, KVB = 64, DH = 64;
-constexpr int TILE_BYTES = KVB * DH * 2;  // 8 KB per plane tile
 constexpr int NST = 2;
-
-__device__ inline float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
 template <bool XCDMAP>
 __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const bf16_t* __restrict__ q_hi, const bf16_t* __restrict__ q_lo,
@@ -37,15 +33,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const bf16_t* __re
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
-  int bh, qb;
-  if constexpr (XCDMAP) {  // nbh % 8 == 0 (checked by the launcher): all query blocks of a (frame, head) on one XCD
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    bh = (idx / nqb) * 8 + xcd;
-    qb = idx % nqb;
-  } else {
-    bh = blockIdx.x / nqb;
-    qb = blockIdx.x - bh * nqb;
-  }
+  const auto [bh, qb] = attn_block<XCDMAP>(nqb);
   const int b = bh / heads, head = bh - b * heads;
   const int q0 = qb * QB + wave * 32;
 
@@ -56,23 +44,18 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const bf16_t* __re
       __builtin_amdgcn_make_buffer_rsrc((void*)k_lo, 0, kv_bytes, 0x00020000),
       __builtin_amdgcn_make_buffer_rsrc((void*)vt_hi, 0, kv_bytes, 0x00020000),
       __builtin_amdgcn_make_buffer_rsrc((void*)vt_lo, 0, kv_bytes, 0x00020000)};
-  unsigned koff[2], voff[2];
+  AttnDmaOffset src[2];
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int row = (wave * 2 + u) * 8 + (lane >> 3);          // key (K tile) or d (V^T tile)
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);           // source chunk that lands in LDS chunk lane & 7
-    koff[u] = (unsigned)((((size_t)bh * npad + row) * DH + chunk * 8) * 2);   // + kv0 * 128
-    voff[u] = (unsigned)((((size_t)bh * DH + row) * npad + chunk * 8) * 2);   // + kv0 * 2
-  }
+  for (int u = 0; u < 2; ++u) src[u] = attn_dma_offset(bh, npad, (wave * 2 + u) * 8 + (lane >> 3), lane);
   auto issue = [&](int t) {
     unsigned char* dst = lds + (t % NST) * 4 * TILE_BYTES + wave * 2048;
     const unsigned ks = __builtin_amdgcn_readfirstlane(t * KVB * DH * 2), vs = __builtin_amdgcn_readfirstlane(t * KVB * 2);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[0], (__attribute__((address_space(3))) void*)(dst + u * 1024), 16, koff[u], ks, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[1], (__attribute__((address_space(3))) void*)(dst + TILE_BYTES + u * 1024), 16, koff[u], ks, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[2], (__attribute__((address_space(3))) void*)(dst + 2 * TILE_BYTES + u * 1024), 16, voff[u], vs, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[3], (__attribute__((address_space(3))) void*)(dst + 3 * TILE_BYTES + u * 1024), 16, voff[u], vs, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[0], (__attribute__((address_space(3))) void*)(dst + u * 1024), 16, src[u].k, ks, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[1], (__attribute__((address_space(3))) void*)(dst + TILE_BYTES + u * 1024), 16, src[u].k, ks, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[2], (__attribute__((address_space(3))) void*)(dst + 2 * TILE_BYTES + u * 1024), 16, src[u].v, vs, 0, 0);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[3], (__attribute__((address_space(3))) void*)(dst + 3 * TILE_BYTES + u * 1024), 16, src[u].v, vs, 0, 0);
     }
   };
   const int nt = (ntok + KVB - 1) / KVB;
@@ -81,15 +64,12 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const bf16_t* __re
   // ---- Q^T fragments (B operand): query l31, d = 16 s + 8 hi .. + 7 ----
   const size_t qoff = ((size_t)bh * npad + q0 + l31) * DH + hi * 8;
   bf16x8_t qh[4], ql[4];
+  attn_load_q(q_hi + qoff, qh);
+  attn_load_q(q_lo + qoff, ql);
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    qh[s] = *(const bf16x8_t*)(q_hi + qoff + s * 16);
-    ql[s] = *(const bf16x8_t*)(q_lo + qoff + s * 16);
-  }
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {  // consume the loads here, not inside the tile loop (their vmcnt wait would drain the DMA queue there)
-    asm volatile("" : "+v"(qh[s]));
-    asm volatile("" : "+v"(ql[s]));
+    qh[s] = attn_used(qh[s]);
+    ql[s] = attn_used(ql[s]);
   }
 
   f32x16_t ot[2];
@@ -99,22 +79,14 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const bf16_t* __re
     for (int r = 0; r < 16; ++r) ot[dt][r] = 0.f;
   float m_run = -1e30f, l_run = 0.f, l_run1 = 0.f;
 
-  const unsigned rd_row = l31 * 128;
-  const int xorc = (l31 >> 1) & 7;
   unsigned rdo[4];
 #pragma unroll
-  for (int s = 0; s < 4; ++s) rdo[s] = rd_row + (((2 * s + hi) ^ xorc) << 4);
+  for (int s = 0; s < 4; ++s) rdo[s] = attn_read_offset(l31, hi, s);
 
   auto compute_tile = [&](int kv0, int stage, int t_issue, auto tail_tag) {
     constexpr bool MAYBE_TAIL = decltype(tail_tag)::value;
     unsigned fa[4];
-    unsigned so = (unsigned)(stage * 4 * TILE_BYTES);
-    asm volatile("" : "+s"(so));
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      fa[s] = rdo[s] + so;
-      asm volatile("" : "+v"(fa[s]));
-    }
+    attn_tile_addresses(rdo, (unsigned)(stage * 4 * TILE_BYTES), fa);
     // ---- S^T = K Q^T, three products per fragment pair (small terms first) ----
     f32x16_t st[2];
 #pragma unroll
@@ -134,37 +106,10 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const bf16_t* __re
     __builtin_amdgcn_sched_barrier(0);
     if (MAYBE_TAIL && kv0 + KVB > ntok) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = kv0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          if (key >= ntok) st[t][r] = -1e30f;
-        }
+      for (int t = 0; t < 2; ++t) st[t] = attn_mask_tail(st[t], kv0 + t * 32, ntok, hi);
     }
     // ---- online softmax (lane = query; the two half-waves share the running max) ----
-    float ma = max3f(st[0][0], st[0][1], st[0][2]), mb = max3f(st[1][0], st[1][1], st[1][2]);
-    ma = max3f(ma, st[0][3], st[0][4]); mb = max3f(mb, st[1][3], st[1][4]);
-#pragma unroll
-    for (int r = 5; r < 15; r += 2) { ma = max3f(ma, st[0][r], st[0][r + 1]); mb = max3f(mb, st[1][r], st[1][r + 1]); }
-    float mt = max3f(ma, mb, st[0][15]);
-    mt = fmaxf(mt, st[1][15]);
-    {
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mt), __float_as_uint(mt), false, false);
-      mt = max3f(mt, __uint_as_float(sw[0]), __uint_as_float(sw[1]));
-    }
-    // deferred, wave-uniform rescale (P bounded by 2^THR instead of 1: harmless in fp32, cancels in O / l)
-    constexpr float THR = 6.0f;
-    if (__any((mt - m_run) * c_exp > THR)) {
-      const float m_new = fmaxf(m_run, mt);
-      const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c_exp);
-      m_run = m_new;
-      l_run *= alpha;
-      l_run1 *= alpha;
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
-    }
+    attn_rescale_raw(attn_row_max(st), c_exp, m_run, l_run, l_run1, ot);
     const float mc = -m_run * c_exp;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -179,9 +124,9 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const bf16_t* __re
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float p0 = st[t][h8 + 2 * e], p1 = st[t][h8 + 2 * e + 1];
-        const uint32_t hw = pack_bf16x2(p0, p1);
-        ph.u[e] = hw;
-        pl.u[e] = pack_bf16x2(p0 - __uint_as_float(hw << 16), p1 - __uint_as_float(hw & 0xffff0000u));
+        const Bf16Split p = attn_split_bf16x2(p0, p1);
+        ph.u[e] = p.hi;
+        pl.u[e] = p.lo;
         l_run += p0;
         l_run1 += p1;
       }
@@ -209,9 +154,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const bf16_t* __re
   compute_tile((nt - 1) * KVB, (nt - 1) % NST, -1, std::true_type{});
 
   // ---- normalise, split, store: out[b*ntok_s + q][head*64 + d] ----
-  l_run += l_run1;
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.0f / l_tot;
+  const float inv = attn_inv_row_sum(l_run, l_run1);
   const int qi = q0 + l31;
   if (qi < ntok) {
     const size_t o = ((size_t)b * ntok_s + qi) * (heads * DH) + head * DH;
@@ -223,9 +166,9 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const bf16_t* __re
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const float a = ot[dt][4 * g + 2 * e] * inv, c = ot[dt][4 * g + 2 * e + 1] * inv;
-          const uint32_t hw = pack_bf16x2(a, c);
-          oh[e] = hw;
-          ol[e] = pack_bf16x2(a - __uint_as_float(hw << 16), c - __uint_as_float(hw & 0xffff0000u));
+          const Bf16Split o2 = attn_split_bf16x2(a, c);
+          oh[e] = o2.hi;
+          ol[e] = o2.lo;
         }
         *(u32x2_t*)(out_hi + o + dt * 32 + 8 * g + 4 * hi) = oh;
         *(u32x2_t*)(out_lo + o + dt * 32 + 8 * g + 4 * hi) = ol;

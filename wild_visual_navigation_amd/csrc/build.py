@@ -29,7 +29,7 @@ HOST_SOURCES = ["jpeg_host.cpp"]
 HOST_FLAGS = ["-x", "c++", "-O3", "-std=c++17", "-fPIC", "-Wall", "-pthread"]
 # the kernels of the 16-bit-operand speed path are compiled twice (operand.h): bf16 operands, and fp16 operands (-> <name>_f16.o)
 DUAL_OPERAND = ["gemm_bf16.hip", "gemm_a384.hip", "gemm_n384.hip", "mlp_fused.hip", "qkv_fused.hip", "gemm_proj.hip", "attention_bf16.hip"]
-HEADERS = ["common.h", "operand.h", "mlp_device.h", "mlp_tile_device.h", "mlp_train_device.h", "rnvp_device.h", "simple_gcn_device.h", "split_operand.h", "mx_operand.h", "tile_epilogue.h", "wvn_internal.h", "jpeg_host.h", os.path.join("..", "..", "include", "wvn_hip.h")]
+HEADERS = ["common.h", "operand.h", "mlp_device.h", "mlp_tile_device.h", "mlp_train_device.h", "rnvp_device.h", "simple_gcn_device.h", "split_operand.h", "mx_operand.h", "tile_epilogue.h", "attention_tile.h", "wvn_internal.h", "jpeg_host.h", os.path.join("..", "..", "include", "wvn_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mcode-object-version=5", "-Wall",
          "-Wno-unused-function"]
 # bit-exact integer outputs need un-fused multiply/add in the k-means kernels (see stego.hip)
