@@ -1459,6 +1459,62 @@ int wvn_grid_carrot(const float* sdf, const float* elevation, int N, double cos_
                     float center_force_factor, const int* discs, int n_discs, float cx, float cy, float resolution, int* goal_cell,
                     float* goal, float* masked, void* stream);
 
+/* Elevation from depth: the elevation and variance layers from the depth images and point clouds of one callback (the geometric half
+ * of elevation_mapping_cupy; csrc/elevation.hip).  accumulate (any number of calls, both forms) then finalise: one launch each, integer
+ * atomics only, no host synchronisation; tests/elevation_ref.py states them in numpy and the results are that statement BIT FOR BIT,
+ * whatever the order of the points and of the sensors -- every point is judged against the layers as they were on entry.
+ *
+ * Sources: `points` [B][Pmax][3] fp32 in the sensor frame with `counts` [B] int32 (NULL: every slot is a point), or `depth` [B][H][W],
+ * WVN_GRID_DEPTH_F32 metres or WVN_GRID_DEPTH_U16 millimetres (0, NaN, inf: no point), with the scaled 4 x 4 intrinsics as for
+ * wvn_grid_fuse_images: pixel (v, u) is ((u - K[0][2]) (z / K[0][0]), (v - K[1][2]) (z / K[1][1]), z), formed on load.  `poses`
+ * [B][4][4]: pose_sensor_in_map.  All device pointers.
+ *
+ * A point is rejected (first match) when a coordinate is not finite, its squared range d2 is below min_valid_distance^2, it is more than
+ * max_height_range above its sensor, more than fmaxf(L - ramp_b, 0) ramp_a + ramp_c above it (L: horizontal distance to the sensor), or
+ * its nearest cell is outside the map.  It is gated (the cell's outlier count += 1) when the cell's elevation h is finite and
+ * |q_z - h| > mahalanobis_thresh sqrtf(variance).  Otherwise it is an inlier of noise v = sensor_noise_factor d2 and enters the cell's
+ * integer sums with the weight floor(min(1 / v, 4096 - 1/256) 256) and the height rint((q_z - z_ref) 16384); an inlier with
+ * |q_z - z_ref| > 128 or a zero weight is dropped ("unrepresentable").  With at most WVN_GRID_ELEVATION_MAX_POINTS point slots per call
+ * (B Pmax, B H W; more is refused) the 64-bit sums cannot overflow; a caller that accumulates several calls before one finalise keeps
+ * their total within the same bound.  WVN_GRID_ELEVATION_CLEAR_RAYS: every point that passed rejection walks towards its sensor in
+ * steps of one resolution (at most max_ray_length) and a cell under the ray, other than its own, whose elevation is finite and higher
+ * than the ray by more than clear_margin is counted as contradicted.
+ *
+ * finalise, per cell, in fp64: the information-form Kalman update of (elevation, variance) with the cell's sums, variance +=
+ * outlier_variance x outliers, clamped to max_variance; with CLEAR_RAYS a cell without an inlier and with at least clear_min_rays
+ * contradicting rays becomes unknown: elevation NaN, variance = initial_variance, the C image `layers` (HOST array of device pointers,
+ * as for wvn_grid_fuse_images; C may be 0) NaN, hits 0.  `stats` int32 [WVN_GRID_ELEVATION_STATS] (device): the points of the calls
+ * since the last finalise by class -- invalid, near, high, ramp, outside, gated, unrepresentable, inliers.
+ *
+ * `z_ref`: one fp32 ON THE DEVICE, the height the fixed-point sums are relative to (e.g. &poses[11], sensor 0's t_z: nothing is read back
+ * to choose it); accumulate and finalise of one callback take the same value.
+ * `workspace`: wvn_grid_elevation_workspace_bytes(N) bytes (0 for N out of range), 8-byte aligned (its records take 64-bit atomics),
+ * zero before the first call; finalise leaves it zero.
+ * WVN_ERR_ARG before any launch: a null pointer (counts excepted), a workspace that is not 8-byte aligned, N, B, H, W, Pmax, C or dtype out of range, more than
+ * WVN_GRID_ELEVATION_MAX_POINTS point slots, unknown flags, a resolution or sensor_noise_factor that is not positive and finite, a NaN
+ * parameter, a negative min_valid_distance, mahalanobis_thresh, outlier_variance or max_ray_length, max_ray_length / resolution
+ * above 2^20, max_variance <= 0, clear_min_rays < 1. */
+#define WVN_GRID_ELEVATION_MAX_POINTS 4194304
+#define WVN_GRID_ELEVATION_STATS 8
+#define WVN_GRID_DEPTH_F32 0
+#define WVN_GRID_DEPTH_U16 1
+#define WVN_GRID_ELEVATION_CLEAR_RAYS 1
+typedef struct {
+  float sensor_noise_factor, mahalanobis_thresh, outlier_variance, min_valid_distance, max_height_range;
+  float ramp_a, ramp_b, ramp_c;   /* ramped_height_range_a / _b / _c of anymal_parameters.yaml */
+  float initial_variance, max_variance, max_ray_length, clear_margin;
+  int clear_min_rays;
+} wvn_grid_elevation_params;
+size_t wvn_grid_elevation_workspace_bytes(int N);
+int wvn_grid_elevation_accumulate_points(const float* points, const int* counts, int B, int Pmax, const float* poses,
+                                         const float* elevation, const float* variance, int N, float cx, float cy, float resolution,
+                                         const wvn_grid_elevation_params* params, const float* z_ref, int flags, void* workspace, void* stream);
+int wvn_grid_elevation_accumulate_depth(const void* depth, int dtype, int B, int H, int W, const float* intrinsics, const float* poses,
+                                        const float* elevation, const float* variance, int N, float cx, float cy, float resolution,
+                                        const wvn_grid_elevation_params* params, const float* z_ref, int flags, void* workspace, void* stream);
+int wvn_grid_elevation_finalise(float* elevation, float* variance, float* const* layers, int C, int* hits, int N,
+                                const wvn_grid_elevation_params* params, const float* z_ref, int flags, void* workspace, int* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,20 @@ DRAW_LINE, DRAW_LINE2, DRAW_DISC = 0, 1, 2
 # include/wvn_hip.h: WVN_GRID_* limits and the `unknown` modes of wvn_grid_sdf
 GRID_MAX_N, GRID_MAX_CHANNELS, GRID_MAX_CAMERAS, GRID_MAX_DISCS = 4096, 4, 64, 8
 GRID_UNKNOWN = {"obstacle": 0, "free": 1, "neither": 2}
+# include/wvn_hip.h: WVN_GRID_ELEVATION_* / WVN_GRID_DEPTH_*
+GRID_ELEVATION_MAX_POINTS = 1 << 22
+GRID_ELEVATION_STATS = ("invalid", "near", "high", "ramp", "outside", "gated", "unrepresentable", "inliers")
+GRID_DEPTH_F32, GRID_DEPTH_U16 = 0, 1
+GRID_ELEVATION_CLEAR_RAYS = 1
+
+
+class GridElevationParams(C.Structure):
+    """include/wvn_hip.h: wvn_grid_elevation_params."""
+    _fields_ = [(n, C.c_float) for n in ("sensor_noise_factor", "mahalanobis_thresh", "outlier_variance", "min_valid_distance",
+                                         "max_height_range", "ramp_a", "ramp_b", "ramp_c", "initial_variance", "max_variance",
+                                         "max_ray_length", "clear_margin")] + [("clear_min_rays", C.c_int)]
+
+
 MLP_KIND_DOUBLE = 1   # include/wvn_hip.h: WVN_MLP_KIND_DOUBLE (MlpDesc.reserved)
 
 
@@ -332,6 +346,10 @@ _SIGNATURES = {
     "wvn_grid_fuse_images": ([_p, _i, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _p, _p, _f, _f, _f, _f, _p], _i),
     "wvn_grid_sdf": ([_p, _i, _f, _i, _f, _p, _p, _p], _i),
     "wvn_grid_carrot": ([_p, _p, _i, C.c_double, C.c_double, _f, _f, _p, _i, _f, _f, _f, _p, _p, _p, _p], _i),
+    "wvn_grid_elevation_workspace_bytes": ([_i], _sz),
+    "wvn_grid_elevation_accumulate_points": ([_p, _p, _i, _i, _p, _p, _p, _i, _f, _f, _f, _p, _p, _i, _p, _p], _i),
+    "wvn_grid_elevation_accumulate_depth": ([_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _f, _f, _f, _p, _p, _i, _p, _p], _i),
+    "wvn_grid_elevation_finalise": ([_p, _p, _p, _i, _p, _i, _p, _p, _i, _p, _p, _p], _i),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

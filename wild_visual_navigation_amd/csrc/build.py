@@ -22,7 +22,7 @@ SOURCES = [
     "attention_x3.hip", "attention_f32.hip",
     "segments.hip", "stego.hip", "stego_linear.hip", "mlp.hip", "mlp_train.hip", "double_mlp.hip", "pixel_mlp.hip", "rnvp.hip", "rnvp_train.hip", "segment_predict.hip", "simple_gcn.hip", "simple_gcn_train.hip", "supervision.hip", "slic.hip", "slic_connectivity.hip", "wire.hip", "random_pixels.hip", "dense_sift.hip",
     "dense_crf.hip", "dense_crf_permutohedral.hip", "overlay.hip", "draw.hip", "resnet.hip", "pyramid_pool.hip", "metrics.hip",
-    "jpeg.hip", "rectify.hip", "grid_map.hip",
+    "jpeg.hip", "rectify.hip", "grid_map.hip", "elevation.hip",
 ]
 # plain C++ without device code (the host stage of the JPEG ingest: parser + Huffman decoder), compiled by the same driver as C++
 HOST_SOURCES = ["jpeg_host.cpp"]
@@ -40,6 +40,7 @@ EXTRA = {"stego.hip": ["-ffp-contract=off"], "stego_linear.hip": ["-ffp-contract
          "overlay.hip": ["-ffp-contract=off"],   # the two multiplications by 255 are rounded on their own: the picture is defined bit for bit
          "draw.hip": ["-ffp-contract=off"],   # the polygon scanline of the 2-pixel line is Pillow's fp32 arithmetic, one operation at a time
          "grid_map.hip": ["-ffp-contract=off"],   # projection, ray walk, fusion and carrot score are fp32, one rounding per operation
+         "elevation.hip": ["-ffp-contract=off"],   # rejection, gate and fixed-point conversion in fp32, the fusion in fp64: one rounding per operation
          "metrics.hip": ["-ffp-contract=off"],  # the binned AUROC is a fixed sequence of fp64 operations, each rounded on its own
          "attention_bf16.hip": ["-fno-honor-nans"] + os.environ.get("WVN_ATTN_FLAGS", "").split(),
          "attention_x3.hip": ["-fno-honor-nans"], "mlp_fused.hip": os.environ.get("WVN_MLP_FLAGS", "").split()}

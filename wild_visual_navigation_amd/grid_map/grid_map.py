@@ -1,7 +1,8 @@
 """TraversabilityGridMap and SmartCarrot: what the reference leaves to elevation_mapping_cupy (the ``sem_wvn_*_traversability`` image
 subscribers with ``image_channel_fusions: exponential`` and the ``mask_elevation_semantics`` plugin of
 wild_visual_navigation_anymal/config/elevation_mapping_cupy) and to wild_visual_navigation_ros/scripts/smart_carrot.py, on the three
-kernels of csrc/grid_map.hip.  Every layer and every result lives on the device; nothing here reads one back.
+kernels of csrc/grid_map.hip, and the elevation layer itself from depth images and point clouds on the two kernels of
+csrc/elevation.hip (add_depth / add_points).  Every layer and every result lives on the device; nothing here reads one back.
 
 Grid convention (smart_carrot.py:140-150): N = round(length / resolution) cells a side, axis 0 = map x, axis 1 = map y, cell (i, j)
 centred at (cx + (i - N/2) r, cy + (j - N/2) r); a layer is fp32 [N,N] and NaN means unknown."""
@@ -25,7 +26,11 @@ def layer_to_message(layer) -> torch.Tensor:
 class TraversabilityGridMap:
     def __init__(self, length: float = 8.0, resolution: float = 0.04, device="cuda",
                  layers=("visual_traversability", "visual_confidence"), alpha: float = 0.5, min_depth: float = 0.1, max_range=None,
-                 occlusion_margin: float = 0.05, center=(0.0, 0.0)):
+                 occlusion_margin: float = 0.05, center=(0.0, 0.0), time_variance: float = 1e-4, **elevation_params):
+        """``elevation_params``: the noise and range parameters of add_points / add_depth under the names of the reference's
+        anymal_parameters.yaml (ops.GRID_ELEVATION_DEFAULTS: sensor_noise_factor, mahalanobis_thresh, outlier_variance,
+        min_valid_distance, max_height_range, ramped_height_range_a / _b / _c, initial_variance, max_variance, max_ray_length) and
+        clear_margin, clear_min_rays for the ray clearing."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.WvnError(f"TraversabilityGridMap: device must be a GPU (got {self.device}); the HIP path has no CPU fallback")
@@ -44,6 +49,12 @@ class TraversabilityGridMap:
                         for name in ("elevation",) + self.layer_names + ("sdf",)}
         self.hits = torch.zeros(self.N, self.N, dtype=torch.int32, device=self.device)
         self.sdf_d2 = torch.zeros(self.N, self.N, dtype=torch.int32, device=self.device)
+        self.elevation_params = ops.grid_elevation_params(**elevation_params)
+        self.time_variance = float(time_variance)
+        self.initial_variance, self.max_variance = self.elevation_params.initial_variance, self.elevation_params.max_variance
+        self._layers["variance"] = torch.full((self.N, self.N), self.initial_variance, dtype=torch.float32, device=self.device)
+        self._elevation_workspace = None      # allocated by the first add_points / add_depth; the kernels leave it zero
+        self._elevation_stats = torch.zeros(len(_lib.GRID_ELEVATION_STATS), dtype=torch.int32, device=self.device)
 
     # ---- layers ----
     def __getitem__(self, name: str) -> torch.Tensor:
@@ -57,15 +68,62 @@ class TraversabilityGridMap:
     def __contains__(self, name: str) -> bool:
         return name in self._layers or name in ("elevation_with_semantics", "hits")
 
-    def set_elevation(self, elevation: torch.Tensor) -> None:
-        """The elevation layer from any source (fp32 [N,N] in the grid convention, NaN = unknown)."""
+    def set_elevation(self, elevation: torch.Tensor, variance=None) -> None:
+        """The elevation layer from any source (fp32 [N,N] in the grid convention, NaN = unknown).  The finite cells take ``variance``
+        (default: initial_variance clamped to max_variance, i.e. no confidence in the supplied height), the others initial_variance."""
         if tuple(elevation.shape) != (self.N, self.N):
             raise _lib.WvnError(f"set_elevation: expected [{self.N},{self.N}], got {tuple(elevation.shape)}")
         self._layers["elevation"].copy_(elevation.to(self.device, torch.float32))
+        known = min(self.initial_variance, self.max_variance) if variance is None else float(variance)
+        e = self._layers["elevation"]
+        v = self._layers["variance"]          # in place, like the elevation: a caller that holds gm["variance"] keeps seeing the layer
+        v.fill_(self.initial_variance)
+        v.masked_fill_(torch.isfinite(e), known)
+
+    # ---- elevation from depth (csrc/elevation.hip) ----
+    def _add(self, op, *source, **kw):
+        if self._elevation_workspace is None:
+            self._elevation_workspace = ops.grid_elevation_workspace(self.N, self.device)
+        self._elevation_stats = op(*source, self._layers["elevation"], self._layers["variance"], [self._layers[n] for n in self.layer_names],
+                                   self.hits, self.center, self.resolution, params=self.elevation_params,
+                                   workspace=self._elevation_workspace, **kw)
+
+    def add_points(self, points: torch.Tensor, pose_sensor_in_map: torch.Tensor, counts=None, z_ref=None, clear_rays: bool = False) -> None:
+        """Fuse point clouds into the elevation and variance layers: points [B,Pmax,3] (or [P,3] with one [4,4] pose) fp32 in the sensor
+        frames, ``counts`` [B] int32 on the GPU for padded clouds.  All sensors of the callback in two launches; every point is judged
+        against the map as it was on entry, so the order of points and sensors does not matter.  ``z_ref``: the height the
+        fixed-point sums are relative to (default: sensor 0's t_z, taken on the device); points further than 128 m from it in z are
+        dropped.  ``clear_rays``: cells whose elevation contradicts a ray and that received no inlier become unknown."""
+        if points.dim() == 2:
+            points = points[None]
+        pose = pose_sensor_in_map if pose_sensor_in_map.dim() == 3 else pose_sensor_in_map[None]
+        self._add(ops.grid_elevation_points, points, pose, counts=counts, z_ref=z_ref, clear_rays=clear_rays)
+
+    def add_depth(self, depth: torch.Tensor, intrinsics: torch.Tensor, pose_cam_in_world: torch.Tensor, z_ref=None,
+                  clear_rays: bool = False) -> None:
+        """The same from depth images [B,H,W] (or [H,W]), fp32 metres or uint16 millimetres (ROS 32FC1 / 16UC1; 0, NaN, inf: no
+        point), with the scaled intrinsics [B,4,4] as for fuse_images.  The points are formed on load; no cloud is written."""
+        if depth.dim() == 2:
+            depth = depth[None]
+        B = depth.shape[0]
+        K = intrinsics if intrinsics.dim() == 3 else intrinsics[None]
+        pose = pose_cam_in_world if pose_cam_in_world.dim() == 3 else pose_cam_in_world[None]
+        self._add(ops.grid_elevation_depth, depth, K.expand(B, 4, 4) if K.shape[0] != B else K, pose, z_ref=z_ref, clear_rays=clear_rays)
+
+    def update_variance(self) -> None:
+        """elevation_mapping_cupy's update_variance: var = min(var + time_variance, max_variance) on the known cells (torch plumbing)."""
+        v = self._layers["variance"]
+        grown = torch.clamp(v + self.time_variance, max=self.max_variance)
+        torch.where(torch.isfinite(self._layers["elevation"]), grown, v, out=v)      # in place: gm["variance"] stays the same tensor
+
+    @property
+    def elevation_stats(self) -> dict:
+        """The points of the last add_points / add_depth by class (reads eight int32 from the device: on demand only)."""
+        return dict(zip(_lib.GRID_ELEVATION_STATS, self._elevation_stats.tolist()))
 
     def move_to(self, x: float, y: float) -> None:
         """Re-centre the map on (x, y) snapped to the cell raster: every layer is shifted by whole cells, vacated cells become NaN
-        (hits 0).  Torch plumbing, no kernel."""
+        (hits 0, variance initial_variance).  Torch plumbing, no kernel."""
         r, N = self.resolution, self.N
         si, sj = int(round((float(x) - self.center[0]) / r)), int(round((float(y) - self.center[1]) / r))
         if si == 0 and sj == 0:
@@ -79,7 +137,7 @@ class TraversabilityGridMap:
             return out
 
         for name in self._layers:
-            self._layers[name] = shift(self._layers[name], float("nan"))
+            self._layers[name] = shift(self._layers[name], self.initial_variance if name == "variance" else float("nan"))
         self.hits = shift(self.hits, 0)
         self.sdf_d2 = shift(self.sdf_d2, 0)
 

@@ -2008,3 +2008,121 @@ def grid_carrot(sdf: torch.Tensor, elevation: torch.Tensor, yaw: float, center, 
                                     float(center_force_factor), table, len(discs), float(center[0]), float(center[1]), float(resolution),
                                     ptr(cell), ptr(goal), ptr(masked), stream()), "wvn_grid_carrot")
     return cell, goal, masked
+
+
+# ---- elevation from depth (include/wvn_hip.h: wvn_grid_elevation_*; csrc/elevation.hip) ----
+# anymal_parameters.yaml of the reference's elevation_mapping_cupy configuration; clear_margin and clear_min_rays are this project's own
+GRID_ELEVATION_DEFAULTS = dict(sensor_noise_factor=0.05, mahalanobis_thresh=2.0, outlier_variance=0.01, min_valid_distance=0.5,
+                               max_height_range=1.0, ramped_height_range_a=0.3, ramped_height_range_b=1.0, ramped_height_range_c=0.2,
+                               initial_variance=1000.0, max_variance=100.0, max_ray_length=10.0, clear_margin=0.05, clear_min_rays=1)
+
+
+def grid_elevation_params(**kw) -> "_lib.GridElevationParams":
+    unknown = set(kw) - set(GRID_ELEVATION_DEFAULTS)
+    if unknown:
+        raise _lib.WvnError(f"grid_elevation: unknown parameters {sorted(unknown)}")
+    p = dict(GRID_ELEVATION_DEFAULTS, **kw)
+    return _lib.GridElevationParams(p["sensor_noise_factor"], p["mahalanobis_thresh"], p["outlier_variance"], p["min_valid_distance"],
+                                    p["max_height_range"], p["ramped_height_range_a"], p["ramped_height_range_b"],
+                                    p["ramped_height_range_c"], p["initial_variance"], p["max_variance"], p["max_ray_length"],
+                                    p["clear_margin"], int(p["clear_min_rays"]))
+
+
+def grid_elevation_workspace(N: int, device) -> torch.Tensor:
+    """The zeroed integer workspace of an N x N map (the kernels leave it zero: allocate it once per map)."""
+    nbytes = lib().wvn_grid_elevation_workspace_bytes(int(N))
+    if nbytes == 0:
+        raise _lib.WvnError(f"grid_elevation_workspace: {N} cells a side; 1 to {_lib.GRID_MAX_N}")
+    return torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def _grid_elevation(who, launch, poses, elevation, variance, layers, hits, z_ref, clear_rays, params, workspace, B):
+    N = _grid_layer(elevation, "elevation", who)
+    _grid_layer(variance, "variance", who, N=N)
+    _grid_layer(hits, "hits", who, torch.int32, N)
+    layers = list(layers)
+    if len(layers) > _lib.GRID_MAX_CHANNELS:
+        raise _lib.WvnError(f"{who}: {len(layers)} image layers; at most {_lib.GRID_MAX_CHANNELS}")
+    for k, t in enumerate(layers):
+        _grid_layer(t, f"layers[{k}]", who, N=N)
+    require_cuda(poses, "pose_sensor_in_map")
+    if tuple(poses.shape) != (B, 4, 4):
+        raise _lib.WvnError(f"{who}: pose_sensor_in_map must be [{B},4,4] (got {tuple(poses.shape)})")
+    poses = poses.to(torch.float32).contiguous()
+    if z_ref is None:
+        z_ref = poses[0, 2, 3:4]       # sensor 0's t_z, read by the kernels where it lies
+    elif not isinstance(z_ref, torch.Tensor):
+        z_ref = torch.full((1,), float(z_ref), dtype=torch.float32, device=elevation.device)
+    if not z_ref.is_cuda or z_ref.dtype != torch.float32 or z_ref.numel() != 1:
+        raise _lib.WvnError(f"{who}: z_ref must be a number or one fp32 on the GPU")
+    if workspace is None:
+        workspace = grid_elevation_workspace(N, elevation.device)
+    need = lib().wvn_grid_elevation_workspace_bytes(N)
+    if not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+        raise _lib.WvnError(f"{who}: the workspace must be a contiguous GPU tensor of at least {need} bytes")
+    params = grid_elevation_params() if params is None else params
+    flags = _lib.GRID_ELEVATION_CLEAR_RAYS if clear_rays else 0
+    stats = torch.empty(len(_lib.GRID_ELEVATION_STATS), dtype=torch.int32, device=elevation.device)
+    table = (C.c_void_p * max(len(layers), 1))(*[ptr(t) for t in layers])
+    with torch.cuda.device(elevation.device):
+        launch(poses, N, C.byref(params), ptr(z_ref), flags, ptr(workspace))
+        check(lib().wvn_grid_elevation_finalise(ptr(elevation), ptr(variance), table, len(layers), ptr(hits), N, C.byref(params), ptr(z_ref),
+                                                flags, ptr(workspace), ptr(stats), stream()), "wvn_grid_elevation_finalise")
+    return stats
+
+
+def grid_elevation_points(points: torch.Tensor, pose_sensor_in_map: torch.Tensor, elevation: torch.Tensor, variance: torch.Tensor, layers,
+                          hits: torch.Tensor, center, resolution: float, counts=None, z_ref=None, clear_rays: bool = False, params=None,
+                          workspace=None) -> torch.Tensor:
+    """Fuse the point clouds of one callback into the elevation and variance layers, in place (include/wvn_hip.h:
+    wvn_grid_elevation_accumulate_points + wvn_grid_elevation_finalise).  points [B,Pmax,3] fp32 in the sensor frames, ``counts`` [B]
+    int32 on the GPU (None: every slot is a point), pose_sensor_in_map [B,4,4]; ``layers`` / ``hits``: the image layers and hit counts
+    that ray clearing resets.  ``z_ref``: None (sensor 0's t_z, taken on the device), a number, or one fp32 on the GPU.  Two launches,
+    nothing is read back -> the class counters, int32 [8] on the GPU in the order of _lib.GRID_ELEVATION_STATS."""
+    who = "grid_elevation_points"
+    require_cuda(points, "points")
+    if points.dtype != torch.float32 or points.dim() != 3 or points.shape[2] != 3:
+        raise _lib.WvnError(f"{who}: points must be fp32 [B,Pmax,3] (got {points.dtype} {tuple(points.shape)})")
+    B, Pmax, _ = points.shape
+    if B * Pmax > _lib.GRID_ELEVATION_MAX_POINTS:
+        raise _lib.WvnError(f"{who}: {B * Pmax} point slots; at most {_lib.GRID_ELEVATION_MAX_POINTS} per call (the 64-bit sums' bound)")
+    points = points.contiguous()
+    if counts is not None:
+        require_cuda(counts, "counts")
+        if counts.dtype != torch.int32 or tuple(counts.shape) != (B,):
+            raise _lib.WvnError(f"{who}: counts must be int32 [{B}] (got {counts.dtype} {tuple(counts.shape)})")
+        counts = counts.contiguous()
+
+    def launch(poses, N, p, z, flags, ws):
+        check(lib().wvn_grid_elevation_accumulate_points(ptr(points), ptr(counts), B, Pmax, ptr(poses), ptr(elevation), ptr(variance), N,
+                                                         float(center[0]), float(center[1]), float(resolution), p, z, flags, ws, stream()),
+              "wvn_grid_elevation_accumulate_points")
+
+    return _grid_elevation(who, launch, pose_sensor_in_map, elevation, variance, layers, hits, z_ref, clear_rays, params, workspace, B)
+
+
+def grid_elevation_depth(depth: torch.Tensor, intrinsics: torch.Tensor, pose_cam_in_world: torch.Tensor, elevation: torch.Tensor,
+                         variance: torch.Tensor, layers, hits: torch.Tensor, center, resolution: float, z_ref=None, clear_rays: bool = False,
+                         params=None, workspace=None) -> torch.Tensor:
+    """The same from depth images [B,H,W], fp32 metres or uint16 millimetres (0, NaN, inf: no point), with the scaled intrinsics
+    [B,4,4] as for grid_fuse_images; the points are formed on load (wvn_grid_elevation_accumulate_depth)."""
+    who = "grid_elevation_depth"
+    require_cuda(depth, "depth")
+    if depth.dtype not in (torch.float32, torch.uint16) or depth.dim() != 3:
+        raise _lib.WvnError(f"{who}: depth must be fp32 or uint16 [B,H,W] (got {depth.dtype} {tuple(depth.shape)})")
+    B, H, W = depth.shape
+    if B * H * W > _lib.GRID_ELEVATION_MAX_POINTS:
+        raise _lib.WvnError(f"{who}: {B * H * W} pixels; at most {_lib.GRID_ELEVATION_MAX_POINTS} per call (the 64-bit sums' bound)")
+    require_cuda(intrinsics, "intrinsics")
+    if tuple(intrinsics.shape) != (B, 4, 4):
+        raise _lib.WvnError(f"{who}: intrinsics must be [{B},4,4] (got {tuple(intrinsics.shape)})")
+    K = intrinsics.to(torch.float32).contiguous()
+    depth = depth.contiguous()
+    dtype = _lib.GRID_DEPTH_U16 if depth.dtype == torch.uint16 else _lib.GRID_DEPTH_F32
+
+    def launch(poses, N, p, z, flags, ws):
+        check(lib().wvn_grid_elevation_accumulate_depth(ptr(depth), dtype, B, H, W, ptr(K), ptr(poses), ptr(elevation), ptr(variance), N,
+                                                        float(center[0]), float(center[1]), float(resolution), p, z, flags, ws, stream()),
+              "wvn_grid_elevation_accumulate_depth")
+
+    return _grid_elevation(who, launch, pose_cam_in_world, elevation, variance, layers, hits, z_ref, clear_rays, params, workspace, B)
